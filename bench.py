@@ -7,7 +7,13 @@ device-resident (B, H, W, 12) float64 out (the reference's dtype, mixed_density_
 Workload = BASELINE.json configs[1]: 640x480, 12 channels, 50 000 events per window (the reference's
 window size, gen1_2yolo.py:41), batch of 32 windows.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the builder's HIP-event
+roofline).  Everything else the line can carry -- the pipelined figure, the GWD wall time, the sweep, the precompute
+pipeline, the GW extension, the box's fill / copy rates, live PMC traffic, the CPU baseline and, for N > 1, the per-rank
+legs -- runs only with --full (and its --no-* switches still drop single legs there).  --dump-outputs DIR writes what the
+last timed step handed its caller (see dump_outputs) as .npy files; the inputs are seeded, so two builds can be compared.
 
 For N > 1 the driver launches it under ``python -m torch.distributed.run --nproc-per-node N``; run as a plain
 ``python bench.py --gpus N`` it re-launches ITSELF that way (one rank per GPU, rendezvous on 127.0.0.1), so
@@ -48,6 +54,11 @@ def parse():
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--events", type=int, default=EVENTS_PER_WINDOW)
     ap.add_argument("--out-dtype", choices=["f64", "f32"], default="f64")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's output of the last timed step to DIR as .npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (pipelined figure, GWD, sweep, precompute, GW extension, "
+                         "fill / copy rates, live PMC traffic, CPU baseline, per-rank legs); the --no-* switches below act on these")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gwd", action="store_true")
     ap.add_argument("--gwd-pairs", type=int, default=144,
@@ -81,7 +92,28 @@ def parse():
     ap.add_argument("--pipeline", action="store_true",
                     help="overlap the binning pass of step k+1 with the builder of step k on a second HIP stream "
                          "(two resident batches alternate); default: bin + build back to back on one stream")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and os.environ.get("EVREP_BENCH_DRYRUN") == "1":
+        ap.error("--dump-outputs: a dry run computes no outputs")
+    return args
+
+
+DUMP_SAMPLE = 3000000   # elements of the seeded sample: with the last window (29.5 MB in float64) <= 53.5 MB in all
+
+
+def dump_outputs(out_dir, out):
+    """What the last timed step handed its caller, the (B, H, W, 12) output tensor, in its own dtype: the whole last
+    window (optimized_last_window.npy, (H, W, 12)) and the flat tensor at fixed positions (optimized_sample.npy: the
+    sorted distinct values of np.random.default_rng(0).integers(0, B*H*W*12, DUMP_SAMPLE)).  The tensor itself is
+    0.94 GB in float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    flat = out.reshape(-1)
+    idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), size=DUMP_SAMPLE))
+    arrays = {"optimized_last_window": out[-1], "optimized_sample": flat[torch.from_numpy(idx).to(out.device)]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
 
 
 def cpu_baseline(events_per_window, budget_s=12.0, threads_budget_s=6.0):
@@ -635,6 +667,8 @@ def main():
         per_rank_ms = [float(x.item()) / max(args.steps, 1) * 1e3 for x in every]
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     el = max(float(t.item()), 1e-9)
+    if args.dump_outputs and rank == 0:     # before any later leg writes into the output tensor again
+        dump_outputs(args.dump_outputs, outs[(args.steps - 1) % nbuf])
 
     elem = 8 if dtype == torch.float64 else 4
     alg_bytes = B * (16 * N + elem * H * W * C)  # read every event once, write every output once
@@ -700,9 +734,10 @@ def main():
                              "build (k_mdes main launch + hot launch)": builder_ms * 1e3,
                              "resident_batches_rotated": nbatch,
                              "resident_event_MB": nbatch * B * N * 16 / 1e6}
-        ach = achievable_rates(device)
-        result["roofline"].update(ach)
-        result["roofline"]["frac_of_achievable"] = achieved / ach["achievable_GBps"]
+        if args.full:
+            ach = achievable_rates(device)
+            result["roofline"].update(ach)
+            result["roofline"]["frac_of_achievable"] = achieved / ach["achievable_GBps"]
         tr = os.path.join(ROOT, "profiles", "traffic.json")
         if os.path.exists(tr):
             try:
@@ -715,7 +750,7 @@ def main():
                         % trj[key].get("source")
             except Exception:
                 pass
-    if not dry and pipe is None and world == 1 and not args.no_pipelined_value:
+    if args.full and not dry and pipe is None and world == 1 and not args.no_pipelined_value:
         # the overlapped counterpart of `value`: the same steps over the same resident batches with
         # the binning pass of step k+1 on a second HIP stream beside the builder of step k.  A second, LABELLED figure:
         # `value` stays the back-to-back form on one stream.
@@ -741,21 +776,21 @@ def main():
                                "algorithmic_GBps_whole_step": alg_bytes * ksteps / pel / 1e9,
                                "whole_step_frac_of_8TBps": alg_bytes * ksteps / pel / 1e9 / HBM_PEAK_GBPS,
                                "over_value": (B * N * ksteps / pel) / result["value"]}
-    if not args.no_gwd:   # while the GPU is still warm: the CPU baseline below idles it for ~20 s
+    if args.full and not args.no_gwd:   # while the GPU is still warm: the CPU baseline below idles it for ~20 s
         result["gwd"] = gwd_leg(rank, world, args.gwd_pairs, device, dry)
-    if world > 1 and not (args.no_sweep and args.no_precompute):
+    if args.full and world > 1 and not (args.no_sweep and args.no_precompute):
         # every rank, its own GPU: config 3's sweep + its share of config 5 (a scaling run measures every config, r06)
         result["per_rank"] = per_rank_legs(rank, world, device, dry)
-    if rank == 0 and world == 1 and not dry and not args.no_sweep:
+    if args.full and rank == 0 and world == 1 and not dry and not args.no_sweep:
         result["sweep"] = sweep_leg(device)
-    if rank == 0 and world == 1 and not dry and not args.no_precompute:
+    if args.full and rank == 0 and world == 1 and not dry and not args.no_precompute:
         try:
             result["precompute"] = precompute_leg(device)
         except Exception as e:      # a full /dev/shm must not cost the bench line
             result["precompute"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if rank == 0 and world == 1 and not dry and not args.no_gw_extension:   # single-GPU leg: not part of a scaling run
+    if args.full and rank == 0 and world == 1 and not dry and not args.no_gw_extension:   # single-GPU leg: not part of a scaling run
         result["gw_extension"] = gw_extension_leg(device)
-    if not dry and rank == 0 and world == 1 and not args.no_live_traffic and B == BATCH and N == EVENTS_PER_WINDOW:
+    if args.full and not dry and rank == 0 and world == 1 and not args.no_live_traffic and B == BATCH and N == EVENTS_PER_WINDOW:
         live = live_traffic("k_mdes_f64" if elem == 8 else "k_mdes_f32")   # last GPU leg: two profiler passes, ~40 s
         if live is not None:
             result["roofline"]["traffic"] = live["hbm_bytes_per_launch"]
@@ -764,7 +799,7 @@ def main():
             result["roofline"]["traffic_source"] = ("collected in this run: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE "
                                                     "(two separate passes of tools/pmc_workload.py), calibrated on a 1 GiB fill "
                                                     "and a 1 GiB copy of the same process as MI355X_MICROARCH.md prescribes")
-    if rank == 0 and not args.no_cpu_baseline and not dry:
+    if args.full and rank == 0 and not args.no_cpu_baseline and not dry:
         # rank 0's host cores, after the timed region and every GPU leg (the other ranks wait at the barrier below)
         result["cpu_baseline"] = cpu_baseline(N)
     elif rank == 0:

@@ -25,7 +25,7 @@ def _json_lines(out):
 
 
 def test_self_launch_two_ranks_gloo():
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--gwd-pairs", "7"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--gwd-pairs", "7", "--full"],
                        env=_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
@@ -45,11 +45,22 @@ def test_self_launch_two_ranks_gloo():
 
 
 def test_single_rank_dry_run_prints_one_line():
-    r = subprocess.run([sys.executable, BENCH, "--steps", "2", "--warmup", "0", "--gwd-pairs", "3"],
+    r = subprocess.run([sys.executable, BENCH, "--steps", "2", "--warmup", "0", "--gwd-pairs", "3", "--full"],
                        env=_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     (res,) = _json_lines(r.stdout)
     assert res["n_gpus"] == 1 and res["gwd"]["n_ranks"] == 1
+
+
+def test_plain_run_leaves_the_other_legs_to_full():
+    # a plain run times the steps and prints the headline only; every other leg waits for --full
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1"],
+                       env=_env(), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    (res,) = _json_lines(r.stdout)
+    assert res["n_gpus"] == 2 and res["steps"] == 3 and res["warmup"] == 1 and "ms_per_step" in res
+    assert res["cpu_baseline"] is None
+    assert not {"gwd", "per_rank", "sweep", "precompute", "gw_extension", "pipelined"} & set(res), sorted(res)
 
 
 def test_world_size_mismatch_is_an_error():

@@ -8,13 +8,13 @@
 set -x
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/final; rm -rf $O; mkdir -p $O
 cd $R
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gw-extension --no-live-traffic --no-sweep --no-precompute > $O/bench_driver_flags.json 2>> $O/bench.err
-timeout 900 python bench.py --out-dtype f32 --no-cpu-baseline --no-gwd --no-gw-extension --no-live-traffic --no-sweep --no-precompute > $O/bench_f32.json 2>> $O/bench.err
-timeout 900 python bench.py --pacing 0 --no-cpu-baseline --no-gwd --no-gw-extension --no-live-traffic --no-sweep --no-precompute > $O/bench_unpaced.json 2>> $O/bench.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-gw-extension --no-live-traffic --no-sweep --no-precompute > $O/bench_driver_flags.json 2>> $O/bench.err
+timeout 900 python bench.py --out-dtype f32 --full --no-cpu-baseline --no-gwd --no-gw-extension --no-live-traffic --no-sweep --no-precompute > $O/bench_f32.json 2>> $O/bench.err
+timeout 900 python bench.py --pacing 0 --full --no-cpu-baseline --no-gwd --no-gw-extension --no-live-traffic --no-sweep --no-precompute > $O/bench_unpaced.json 2>> $O/bench.err
 timeout 300 python tools/experiments/pacing.py ergo64 8 0 600 650 680 690 700 720 750 > $O/pacing.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o bench -- python $R/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-live-traffic --no-sweep --no-precompute --no-pipelined-value > $O/kt.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o bench -- python $R/bench.py --steps 200 --warmup 20 --full --no-cpu-baseline --no-live-traffic --no-sweep --no-precompute --no-pipelined-value > $O/kt.log 2>&1
 timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -o pmc_fetch -- python $R/tools/pmc_workload.py > $O/fetch.log 2>&1
 timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -o pmc_write -- python $R/tools/pmc_workload.py > $O/write.log 2>&1
 timeout 600 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU --kernel-trace --output-format csv -d $O/sq -o pmc_sq -- python $R/tools/pmc_workload.py > $O/sq.log 2>&1
