@@ -3191,12 +3191,16 @@ __global__ __launch_bounds__(kWave, HOT ? 4 : EVREP_ES_WAVES) void k_event_stack
 // --------------------------------------------------------------------------------------------
 constexpr int kMaxSlices = 8;
 
-// exp(x) for the time surface's argument range (x = (t_last - t_cut)/tau - ... in [-64, 0]):
+// exp(x) for the time surface's arguments: x = (m - t_cut) / tau, anywhere from well below the underflow at -745.13 to 0
+// (and beyond, on windows whose timestamps are not ascending):
 // n = rint(x*log2 e), r = x - n*ln2 (two-part ln2), degree-12 Taylor polynomial in r (|r| <= 0.347,
 // truncation 1e-16), exponent patched in.  ~20 float64 instructions instead of the ~110 of the
-// general libm path, relative error < 4e-16 on this range (the parity budget is 1e-5).
+// general libm path, relative error < 4e-16 wherever exp(x) is a normal number (the parity budget is 1e-5).
+// Below -708.4 the result is subnormal, as libm's is: ldexp rounds p * 2^n once into the subnormal
+// range (gradual underflow, within 1 ulp = 2^-1074 of libm), down to 0 beyond -745.13 (exp(x) < 2^-1075).
+// Above 709.78 ldexp overflows to inf, as libm does.
 __device__ inline double exp_neg_range(double x) {
-    if (x < -700.0) return 0.0;
+    if (x < -746.0) return 0.0;   // (keeps n, and the ldexp exponent, in range; exp(x) rounds to 0 below -745.14)
     const double n = rint(x * 1.4426950408889634);
     double r = fma(n, -6.93147180369123816490e-01, x);
     r = fma(n, -1.90821492927058770002e-10, r);
@@ -3216,12 +3220,22 @@ __device__ inline double exp_neg_range(double x) {
     return ldexp(p, (int)n);
 }
 
+// d / tau rounded as the reference's float64 division rounds it, from the reciprocal: q = d * (1/tau), then one step on the
+// exact residual d - q * tau (Markstein: with 1/tau correctly rounded, the corrected q is the correctly rounded quotient).
+// Two FMAs instead of a division.  A subnormal exp(x) carries the relative error of x's last bit times |x| (~1e-13 at
+// x = -709, i.e. tens of 2^-1074 steps): the argument must be the reference's own to the last bit.  (The factorised form's
+// E = exp((t - tref) / tau) keeps the plain product: it is only used while E is a normal float64, where 1e-13 is in budget.)
+__device__ inline double div_tau(double d, double tau, double inv_tau) {
+    const double q = d * inv_tau;
+    return fma(fma(-q, tau, d), inv_tau, q);
+}
+
 struct TsCuts {
     int32_t idx[kMaxSlices];   // searchsorted(t_norm, s+1, 'left')  (or the caller's indices)
     int32_t tcut[kMaxSlices];  // t[idx[s]]
     int32_t live[kMaxSlices];  // 1 iff the sequential scan reaches this slice (strictly increasing idx)
     int32_t tref;              // reference time of the factorised exponentials: the last live cut's timestamp
-    int32_t direct;            // 1: the window spans more than 600 tau -- exponentials are taken per slice, unfactorised
+    int32_t direct;            // 1: exponentials are taken per slice, unfactorised (see k_ts_cuts)
     int32_t pad[6];
     double bg[2 * kMaxSlices];  // value of an untouched (pixel, polarity) entry of slice s, already scaled
     double fac[kMaxSlices];    // exp((tref - tcut[s]) / tau) * scale
@@ -3232,13 +3246,29 @@ static_assert(sizeof(TsCuts) == kTsCutsBytes, "TsCuts");
 // grid (B), 64 threads.  indices == nullptr: the dispatcher's searchsorted cuts; otherwise DEVICE
 // int32 [B, S] event indices as ToTimesurface.__call__(events, indices) receives them.
 #ifdef EVREP_TU_BUILDERS   // (compiled by the one translation unit that launches it)
-static __global__ void k_ts_cuts(const int4 *__restrict__ ev, const int64_t *__restrict__ off, int S,
+static __global__ void k_ts_cuts(BinView bv, const int4 *__restrict__ ev, const int64_t *__restrict__ off, int S,
                           const int32_t *__restrict__ indices, double tau, double scale, TsCuts *__restrict__ cuts,
                           const double *__restrict__ tf) {
     const int b = blockIdx.x, s = threadIdx.x;
     __shared__ int sidx[kMaxSlices];
     const int64_t beg = off[b];
     const int64_t n = off[b + 1] - beg;
+    // the window's time range from the binning pass (any event order): bounds every E = exp((t - tref) / tau) below.  Only
+    // t.min() / t.max(): after the key-sorted pass one lane per block run and two reductions, else the published WindowMeta
+    int32_t wtmin = INT32_MAX, wtmax = INT32_MIN;
+    if (bv.fused) {
+        const int nb = min((int)(((uint32_t)n + (1u << bv.chunk_shift) - 1u) >> bv.chunk_shift), bv.nblk);
+        for (int k = s; k < nb; k += kWave) {
+            const int2 q = *reinterpret_cast<const int2 *>(bv.stats + (size_t)b * bv.nblk + k);
+            wtmin = min(wtmin, q.x);
+            wtmax = max(wtmax, q.y);
+        }
+        wtmin = wave_min(wtmin);
+        wtmax = wave_max(wtmax);
+    } else if (n > 0) {
+        wtmin = bv.meta[b].tmin;
+        wtmax = bv.meta[b].tmax;
+    }
     if (s < S) {
         int idx = 0, tc = 0;
         if (n > 0) {
@@ -3282,7 +3312,7 @@ static __global__ void k_ts_cuts(const int4 *__restrict__ ev, const int64_t *__r
             // untouched pixels are not zero: exp((-(3 tau + 1) - t_i) / tau)  (time_surface.py:26-29,68-72);
             // slices the scan never reaches stay exactly 0
             double v = 0.0;
-            if (k < S && alive) v = exp_neg_range((-(tau * 3.0 + 1.0) - cuts[b].tcutf[k]) * (1.0 / tau)) * scale;
+            if (k < S && alive) v = exp_neg_range((-(tau * 3.0 + 1.0) - cuts[b].tcutf[k]) / tau) * scale;
             cuts[b].bg[2 * k] = v;
             cuts[b].bg[2 * k + 1] = v;
         }
@@ -3290,16 +3320,22 @@ static __global__ void k_ts_cuts(const int4 *__restrict__ ev, const int64_t *__r
         // only (one exponential per EVENT, formed by the builder's digest), the second on the slice only (here)
         int tref = 0;
         for (int k = 0; k < kMaxSlices; ++k) if (k < S && cuts[b].live[k]) tref = cuts[b].tcut[k];  // cut times ascend
-        int direct = 0;
+        // The factorised form is exact to an ulp or two only while every factor is a normal float64: the per-slice form is
+        // taken when a live cut lies more than 600 tau from tref (fac would overflow, or underflow where the cut times do
+        // not ascend), or when some event of the window lies more than 700 tau before tref (its E would be subnormal or 0:
+        // exp(x) leaves the normal range below -708.4) or more than 700 tau after it (E would overflow).
+        int direct = 0, nlive = 0;
         for (int k = 0; k < kMaxSlices; ++k) {
             double f = 0.0;
             if (k < S && cuts[b].live[k]) {
-                const double x = ((double)tref - (double)cuts[b].tcut[k]) * (1.0 / tau);
-                if (x > 600.0) direct = 1;
+                const double x = ((double)tref - (double)cuts[b].tcut[k]) / tau;
+                if (x > 600.0 || x < -600.0) direct = 1;
                 f = exp(x) * scale;
+                ++nlive;
             }
             cuts[b].fac[k] = f;
         }
+        if (nlive > 0 && (((double)wtmin - (double)tref) / tau < -700.0 || ((double)wtmax - (double)tref) / tau > 700.0)) direct = 1;
         cuts[b].tref = tref;
         cuts[b].direct = tf ? 1 : direct;   // float timestamps: exponentials per slice
     }
@@ -3353,8 +3389,8 @@ __global__ __launch_bounds__(kWave, HOT ? 4 : EVREP_TS_WAVES) void k_time_surfac
         const UnitRecs u = unit_front<OutT, HOT, false>(bv, off, H, W, nchunk, uc, w, g, uid, part, visit);
         if (u.deferred) return;
         OutT *dst = out + (((size_t)g.b * H + g.row) * (size_t)W + g.c0) * C;
-        // (m - t_i) / tau is evaluated as (m - t_i) * (1/tau): one rounding of 1/tau instead of a float64
-        // division per exponential; the surface moves by < 1e-15 relative (budget 1e-5)
+        // (m - t_i) / tau is evaluated from 1/tau with one FMA correction (div_tau): the reference's correctly rounded quotient,
+        // without a float64 division per exponential
         const double inv_tau = 1.0 / tau;
         // exp((m - t_s)/tau) = exp((m - tref)/tau) * fac[s]: ONE exponential per event, formed by the digest -- one record per
         // lane, all lanes at once -- instead of two per slice and touched pixel inside the per-pixel code (12 per pixel for the
@@ -3373,7 +3409,7 @@ __global__ __launch_bounds__(kWave, HOT ? 4 : EVREP_TS_WAVES) void k_time_surfac
         const OutT *bg = w.bg;
         auto digest = [&](const Rec &r) -> Rec {
             if (!fact) return r;
-            const double E = exp_neg_range(((double)r.z - (double)tref) * inv_tau);
+            const double E = exp_neg_range(((double)r.z - (double)tref) * inv_tau);   // (normal: k_ts_cuts' direct flag)
             return make_int4(__double2loint(E), r.y, __double2hiint(E), r.w);
         };
         // pass 2 of a pixel: the slices' values from the timestamp memory each cut saw (snap: INT32_MIN = never written)
@@ -3390,13 +3426,13 @@ __global__ __launch_bounds__(kWave, HOT ? 4 : EVREP_TS_WAVES) void k_time_surfac
                         if (__any(snap0[q] != INT32_MIN)) {
                             double m0 = (double)snap0[q];
                             if (tw) m0 = snap0[q] != INT32_MIN ? gload_f64(tw + snap0[q]) : 0.0;   // the caller's float64 time of that event
-                            const double e0 = exp_neg_range((m0 - tc) * inv_tau) * scale;
+                            const double e0 = exp_neg_range(div_tau(m0 - tc, tau, inv_tau)) * scale;
                             if (snap0[q] != INT32_MIN) v0 = (OutT)e0;
                         }
                         if (__any(snap1[q] != INT32_MIN)) {
                             double m1 = (double)snap1[q];
                             if (tw) m1 = snap1[q] != INT32_MIN ? gload_f64(tw + snap1[q]) : 0.0;
-                            const double e1 = exp_neg_range((m1 - tc) * inv_tau) * scale;
+                            const double e1 = exp_neg_range(div_tau(m1 - tc, tau, inv_tau)) * scale;
                             if (snap1[q] != INT32_MIN) v1 = (OutT)e1;
                         }
                     }
@@ -3525,7 +3561,7 @@ __global__ __launch_bounds__(kWave, 4) void k_time_surface_stream(BinView bv, co
             for (int q = 0; q < SM; ++q) q0 += (q < nlive && idx[q] < (int)rank) ? 1 : 0;
             unsigned long long key = (unsigned long long)rank + 1ull;
             if (!byrank) {   // one exponential per event: E > 0, and E grows with t, so its bits order as the events do
-                const double E = exp_neg_range(((double)(int32_t)q8.x - (double)tref) * inv_tau);
+                const double E = exp_neg_range(((double)(int32_t)q8.x - (double)tref) * inv_tau);   // (normal: k_ts_cuts' direct flag)
                 key = (unsigned long long)__double_as_longlong(E) + 1ull;   // (+ 1: an E that underflowed to +0 still marks the entry as touched)
             }
             if (have && q0 < nlive) atomicMax(words + (px * 2u + (uint32_t)(p & 1)) * (uint32_t)S + (uint32_t)q0, key);
@@ -3577,11 +3613,11 @@ __global__ __launch_bounds__(kWave, 4) void k_time_surface_stream(BinView bv, co
                     if (q < nlive) {
                         const double tc = gload_f64(&cp->tcutf[q]);
                         if (__any(last[0][q] != 0ull)) {
-                            const double e0 = exp_neg_range((tm[0][q] - tc) * inv_tau) * scale;
+                            const double e0 = exp_neg_range(div_tau(tm[0][q] - tc, tau, inv_tau)) * scale;
                             if (last[0][q]) v0 = (OutT)e0;
                         }
                         if (__any(last[1][q] != 0ull)) {
-                            const double e1 = exp_neg_range((tm[1][q] - tc) * inv_tau) * scale;
+                            const double e1 = exp_neg_range(div_tau(tm[1][q] - tc, tau, inv_tau)) * scale;
                             if (last[1][q]) v1 = (OutT)e1;
                         }
                     }
@@ -4136,9 +4172,12 @@ __global__ __launch_bounds__(kWave, HOT ? 4 : (CM <= 8 ? EVREP_VOXEL_WAVES : 1))
                     double p = (double)ec.w;
                     if (mode == 1 && ec.w == 0) p = -1.0;
                     const double bpos = __hiloint2double(ec.z, ec.y);
-                    // flat time span (0/0): the reference yields NaN garbage.  Mode 2 truncates toward zero
-                    // (astype("int32"), utils.py:67), so an event up to one bin before t0_us still lands in bin 0
-                    if (!(bpos > (mode == 2 ? -1.0 : -0.0) && bpos < 1.0e9) && !(bpos == 0.0)) continue;
+                    // flat time span (0/0): the reference yields NaN garbage.  Modes 0 and 2 truncate toward zero
+                    // (astype("int"), gromov_wasserstein.py:73; astype("int32"), utils.py:67), so an event up to one bin before
+                    // t0 still lands in bin 0 (mode 0: a window whose timestamps wrapped, t[-1] < t[0]).  A position <= -1 (an
+                    // unsorted window with events a whole bin before t[0]) is still dropped, where the reference indexes from the
+                    // end of the bin axis (blim + bins) or raises
+                    if (!(bpos > (mode == 1 ? -0.0 : -1.0) && bpos < 1.0e9) && !(bpos == 0.0)) continue;
                     const int bi = (int)bpos;
                     const int blim = bi + pass;
                     if (blim < bins) {
@@ -4266,7 +4305,7 @@ __global__ __launch_bounds__(kWave, EVREP_VS_WAVES) void k_voxel_stream(const in
         return p;
     };
     auto px_of = [&](const Rec8 &q) -> uint32_t { return ((q.y & 511u) - (uint32_t)c0) & 511u; };
-    const double lowlim = mode == 2 ? -1.0 : -0.0;
+    const double lowlim = mode == 1 ? -0.0 : -1.0;   // (see k_voxel)
     // one batch of one pass: lane holds (have, pixel, bin position, polarity) of one record; lanes are in array order
     auto apply = [&](int pass, bool have, uint32_t px, double bpos, int p) {
         double pd = (double)p;
@@ -4533,7 +4572,7 @@ static __global__ __launch_bounds__(kVhThreads) void k_voxel_hot(const int4 *__r
             const int4 *evw = ev + beg;
             const int c0 = g.c0;
             const Rec8 *__restrict__ s8 = reinterpret_cast<const Rec8 *>(bv.sorted);
-            const double lowlim = mode == 2 ? -1.0 : -0.0;
+            const double lowlim = mode == 1 ? -0.0 : -1.0;   // (see k_voxel)
             auto src_of = [&](uint32_t j) -> uint32_t {    // the address of record j of the unit in the block runs
                 if (nb <= kBsChainBlocks) {
                     uint32_t sx = (uint32_t)__builtin_amdgcn_readlane((int)src0, 0);

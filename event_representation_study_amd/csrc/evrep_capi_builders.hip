@@ -85,7 +85,9 @@ int evrep_time_surface_ftime(const evrep_plan *plan, const int32_t *events, cons
     if (out_dtype != EVREP_F64 && out_dtype != EVREP_F32) return EVREP_EINVAL;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     TsCuts *cuts = WS(TsCuts, off_cuts);
-    k_ts_cuts<<<plan->B, 64, 0, stream>>>(reinterpret_cast<const int4 *>(events), offsets, slices, indices, tau, scale, cuts, tf);
+    // (the window statistics as a stream builder reads them: after the key-sorted pass, the block statistics of every run)
+    k_ts_cuts<<<plan->B, 64, 0, stream>>>(bin_view(plan, events, workspace, true), reinterpret_cast<const int4 *>(events), offsets,
+                                          slices, indices, tau, scale, cuts, tf);
     LAUNCH_CHECK("k_ts_cuts");
     if (plan->reserved == 2 && tf == nullptr && !(premap & 2) && ((plan->flags & EVREP_PLAN_X_TS_STREAM) || ts_stream_wins(plan, out_dtype)) && !(plan->flags & EVREP_PLAN_X_TS_ORDERED) && plan->W <= 512 * 8) {
         // after the key-sorted pass: the streaming form (k_time_surface_stream) -- one launch, every unit, no hot list

@@ -296,7 +296,7 @@ int oracle_time_surface(const int32_t *ev, int64_t n, int H, int W, int S, doubl
  * ascending k - 1 smallest kept so far, and the largest of the k is dropped by the pixel's NEXT event.  (The scalar
  * introselect of other numpy builds only swaps the maximum to the end: the same values in another order whenever the
  * timestamps are not ascending.)  On time-sorted input every new dt is the smallest: a k-deep FIFO, newest first.
- * Then float32: clamp to 5e8, log(v+1) - log(151), floor 0.
+ * Then float32: clamp to 5e8, log(v+1) - log(151), floor 0 (a NaN, from a wrapped dt <= -2, stays NaN).
  * out is (Hf, Wf, 2k) float32: pos[0..k), neg[0..k).
  * ------------------------------------------------------------------------------------------- */
 int oracle_tore(const int32_t *x, const int32_t *y, const int32_t *ts, const int32_t *pol, int64_t n,
@@ -305,6 +305,9 @@ int oracle_tore(const int32_t *x, const int32_t *y, const int32_t *ts, const int
     if (k <= 0 || Hf <= 0 || Wf <= 0) return ORACLE_EARG;
     double *fifo = (double *)malloc(sizeof(double) * hw * 2 * k);
     for (int64_t q = 0; q < hw * 2 * k; ++q) fifo[q] = INFINITY;
+    /* an int32 sample time (the dispatcher's ts[-1], an np.int32) minus the int32 ts array is int32 arithmetic in numpy
+     * (tore.py:20,35): T - ts wraps past INT32_MAX, to a negative dt that sorts first and whose log is NaN */
+    const int int32_T = T == floor(T) && T >= (double)INT32_MIN && T <= (double)INT32_MAX;
     for (int pass = 0; pass < 2; ++pass) { /* the reference handles all positives, then all negatives */
         for (int64_t i = 0; i < n; ++i) {
             if (!((double)ts[i] < T)) continue;
@@ -316,7 +319,7 @@ int oracle_tore(const int32_t *x, const int32_t *y, const int32_t *ts, const int
             if (c < 0) c += Wf;
             double *f = fifo + ((r * Wf + c) * 2 + (is_pos ? 0 : 1)) * k;
             /* w = [dt] + f[:k-1], sorted ascending (insertion of dt into the sorted k - 1 kept values) */
-            double dt = T - (double)ts[i];
+            double dt = int32_T ? (double)(int32_t)(uint32_t)((int64_t)T - (int64_t)ts[i]) : T - (double)ts[i];
             int j = k - 1;
             while (j > 0 && f[j - 1] > dt) { f[j] = f[j - 1]; --j; }
             f[j] = dt;

@@ -75,6 +75,28 @@ def _build_all(eng, wins, H, W, monkeypatch, ordered):
     return res
 
 
+def _ni_stream(eng, wins, H, W, monkeypatch):
+    """n_imagenet's acc_all / acc_exp under the forced stream forms, on the windows as the oracle reads them: p mapped to
+    -1 / +1 (parse_event) and the normalised time (t - t[0]) / (t[-1] - t[0]) in float64 (imagenet.py:198-199)."""
+    for name in ORDERED:
+        monkeypatch.delenv(name, raising=False)
+    for name in ("EVREP_X_MDES_STREAM", "EVREP_X_TS_STREAM"):
+        monkeypatch.setenv(name, "1")
+    ni, tn = [], []
+    for ev in wins:
+        e = ev.copy()
+        e[:, 3] = np.where(ev[:, 3] > 0, 1, -1)
+        ni.append(e)
+        t = ev[:, 2].astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tn.append((t - t[0]) / (t[-1] - t[0]) if len(t) else t)
+    eb = eng.EventBatch.from_numpy(ni, H, W)
+    tnd = torch.from_numpy(np.concatenate(tn)).to(eb.device)
+    out = {"acc_all": eb.polstats(tnd, [1, 2, 1, 2, 1, 2], [0, 0, 1, 1, 2, 2]), "acc_exp": eb.polstats(tnd, [1, 2], [4, 4], tau=0.3)}
+    eb.check_built("n_imagenet streams")
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
 @pytest.mark.parametrize("kind", ["uniform", "clustered", "escaped", "dense", "sweeps", "sweeps19"])
 def test_stream_builders_equal_ordered_builders_and_oracle(kind, monkeypatch, oracle):
     from event_representation_study_amd import engine as eng
@@ -91,11 +113,26 @@ def test_stream_builders_equal_ordered_builders_and_oracle(kind, monkeypatch, or
             assert np.array_equal(got[k] == 0, ref[k] == 0)          # dead slices stay exactly 0
         else:
             assert_bit_equal(got[k], ref[k], "%s stream vs ordered (%s)" % (k, kind))
+    acc = _ni_stream(eng, wins, H, W, monkeypatch)
     for b, ev in enumerate(wins):
         if ev.shape[0] == 0:
             assert not got["ergo64"][b].any() and not got["es"][b].any()
             continue
         assert_bit_equal(got["ergo64"][b], oracle.ergo12(ev, H, W), "ergo12 stream vs oracle (%s, window %d)" % (kind, b))
+        # the outputs the streams were otherwise checked on only against the ordered kernels (voxel12, tonic's ToVoxelGrid
+        # scaled by 255, has no oracle entry point: it stays pinned to the ordered kernel above)
+        tag = "stream vs oracle (%s, window %d)" % (kind, b)
+        assert_bit_equal(got["ergo32"][b], oracle.ergo12(ev, H, W).astype(np.float32), "ergo32 " + tag)
+        assert_bit_equal(got["voxel"][b], oracle.voxel(ev, H, W, 5), "voxel " + tag)
+        assert_bit_equal(np.ascontiguousarray(np.moveaxis(got["evl"][b], -1, 0)).astype(np.float32), oracle.evl_voxel(ev, H, W, 9),
+                         "evl " + tag)
+        np.testing.assert_allclose(got["tore_bbox"][b], oracle.tore_bbox(ev, 6), rtol=1e-6, atol=1e-6, err_msg="tore bbox " + tag)
+        rows = ev.astype(np.float64)
+        rows[:, 3] = np.where(ev[:, 3] > 0, 1.0, -1.0)
+        np.testing.assert_array_equal(np.moveaxis(acc["acc_all"][b], -1, 0), oracle.nimagenet_acc("acc_all", rows, H, W),
+                                      err_msg="acc_all " + tag)
+        np.testing.assert_allclose(np.moveaxis(acc["acc_exp"][b], -1, 0), oracle.nimagenet_acc("acc_exp", rows, H, W),
+                                   rtol=1e-6, atol=1e-7, err_msg="acc_exp " + tag)
         assert_bit_equal(got["es"][b], oracle.event_stack(ev, H, W), "event_stack stream vs oracle (%s, window %d)" % (kind, b))
         want = oracle.tore(ev[:, 0] + 1, ev[:, 1] + 1, ev[:, 2], ev[:, 3], ev[-1, 2], 6, (H, W))
         np.testing.assert_allclose(got["tore"][b], want, rtol=1e-6, atol=1e-6)

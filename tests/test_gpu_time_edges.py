@@ -1,0 +1,228 @@
+"""-m gpu: every builder at the edges of the int32 time axis, against the oracle, under every binning pass and with the stream
+and the ordered forms forced.
+
+The windows (tests/time_edges_windows.py, the same seeds as tests/golden/time_edges.npz, which pins the oracle to the reference
+on them): timestamps at INT32_MIN / INT32_MAX (the binning pass's sentinels), negative times, a window crossing 0, a window whose
+t_last - t0 overflows int32, a recording cast to int32 across 2^31, all-equal and two-valued timestamps; and time-surface windows
+of 590 ... 4 600 tau at tau = 1 ms and 50 ms, 6 and 8 slices, on both sides of the factorised form's switch and of float64's
+subnormal range.  Each batch holds an ordinary window beside them.  Every output tensor is handed in pre-filled with NaN, so an
+element a kernel never writes shows up.
+
+The time surface in float64: exactly 0 where, and only where, the oracle is 0; rtol 1e-12 where the oracle's value is a normal
+float64; an absolute error of at most 4 * 2^-1074 where it is subnormal.  In float32: the oracle cast to float32, 1e-6
+relative, the same zero pattern."""
+import numpy as np
+import pytest
+import torch
+
+from conftest import assert_bit_equal
+from time_edges_windows import EDGE_H, EDGE_W, SLICES, TAUS, TS_H, TS_W, edge_windows, ts_tau_windows
+
+from event_representation_study_amd import _lib
+from event_representation_study_amd.synthetic import make_events
+
+pytestmark = pytest.mark.gpu
+
+_X = dict(_lib._ENV_FLAGS)
+PATHS = {
+    "auto": 0, "classic": _lib.PLAN_NO_KEY_PASS, "key_sorted": _lib.PLAN_FORCE_KEY_SORTED, "three_kernel": _lib.PLAN_THREE_KERNEL,
+    "streams": _X["EVREP_X_MDES_STREAM"] | _X["EVREP_X_TS_STREAM"],
+    "ordered": sum(_X[k] for k in ("EVREP_X_VOXEL_ORDERED", "EVREP_X_TORE_ORDERED", "EVREP_X_POLSTATS_ORDERED",
+                                   "EVREP_X_ESTACK_ORDERED", "EVREP_X_MDES_ORDERED", "EVREP_X_TS_ORDERED")),
+}
+MDES_SBN = ([0, 3, 5, 1], ["timestamp", "count_neg", "polarity", "timestamp_pos"], ["mean", "sum", "variance", "max"])
+MDES_SBT = ([0, 2, 5, 7], ["timestamp", "timestamp_pos", "count", "timestamp_neg"], ["max", "mean", "sum", "variance"])
+TINY = np.finfo(np.float64).tiny          # 2^-1022, the smallest normal float64
+SUB_ULP = np.float64(2.0 ** -1074)
+
+
+def _batch(eng, wins, H, W, flags):
+    offs = np.zeros(len(wins) + 1, dtype=np.int64)
+    np.cumsum([w.shape[0] for w in wins], out=offs[1:])
+    ev = torch.from_numpy(np.concatenate(wins)).cuda()
+    return eng.EventBatch(ev, torch.from_numpy(offs), H, W, plan_flags=flags)
+
+
+def _nan(eb, C, dtype=torch.float64):
+    return torch.full((eb.B, eb.H, eb.W, C), float("nan"), dtype=dtype, device=eb.device)
+
+
+def _where(a, i, C):
+    """flat index of a (H, W, C) tensor -> "(y, x, slice s, polarity p)" for the failure message."""
+    y, x, c = np.unravel_index(i, a.shape)
+    return "(y %d, x %d, slice %d, p %d)" % (y, x, c // 2, c % 2) if C else "(y %d, x %d, c %d)" % (y, x, c)
+
+
+def check_ts64(got, want, what):
+    assert got.shape == want.shape and got.dtype == np.float64, what
+    g, w = got.reshape(-1), want.reshape(-1)
+    nan = np.isnan(w)
+    bad = np.flatnonzero(np.isnan(g) != nan)
+    inf = np.isinf(w)
+    bad = np.union1d(bad, np.flatnonzero(inf & (g != w)))
+    fin = np.isfinite(w)
+    bad = np.union1d(bad, np.flatnonzero(fin & ((g == 0) != (w == 0))))
+    normal = fin & (np.abs(w) >= TINY)
+    with np.errstate(invalid="ignore", over="ignore"):
+        bad = np.union1d(bad, np.flatnonzero(normal & ~(np.abs(g - w) <= 1e-12 * np.abs(w))))
+        sub = fin & (w != 0) & (np.abs(w) < TINY)
+        bad = np.union1d(bad, np.flatnonzero(sub & ~(np.abs(g - w) <= 4 * SUB_ULP)))
+    if bad.size:
+        i = int(bad[0])
+        raise AssertionError("%s: %d of %d elements off, first at %s: got %r, oracle %r"
+                             % (what, bad.size, w.size, _where(want, i, True), g[i], w[i]))
+
+
+def check_ts32(got, want64, what):
+    want = want64.astype(np.float32)
+    assert got.shape == want.shape and got.dtype == np.float32, what
+    g, w = got.reshape(-1), want.reshape(-1)
+    bad = np.flatnonzero(np.isnan(g) != np.isnan(w))
+    fin = np.isfinite(w)
+    bad = np.union1d(bad, np.flatnonzero(np.isinf(w) & (g != w)))
+    bad = np.union1d(bad, np.flatnonzero(fin & ((g == 0) != (w == 0))))
+    with np.errstate(invalid="ignore", over="ignore"):
+        err = np.abs(g.astype(np.float64) - w.astype(np.float64))
+        bad = np.union1d(bad, np.flatnonzero(fin & ~(err <= 1e-6 * np.abs(w.astype(np.float64)) + 2.0 ** -149)))
+    if bad.size:
+        i = int(bad[0])
+        raise AssertionError("%s: %d of %d elements off, first at %s: got %r, oracle %r"
+                             % (what, bad.size, w.size, _where(want, i, True), g[i], w[i]))
+
+
+@pytest.mark.parametrize("slices", SLICES)
+@pytest.mark.parametrize("tau", TAUS)
+def test_time_surface_across_the_exponent_range(oracle, tau, slices):
+    """Spans of 590 ... 4 600 tau, cut times 695 ... 750 tau after 0: values and backgrounds that are normal, subnormal and 0,
+    under the factorised and the per-slice form, in every path."""
+    from event_representation_study_amd import engine as eng
+    named = ts_tau_windows(tau)
+    names = list(named) + ["ordinary"]
+    wins = list(named.values()) + [make_events(2500, TS_W, TS_H, seed=77)]
+    want = [oracle.time_surface(ev, TS_H, TS_W, slices=slices, tau=float(tau)) for ev in wins]
+    for path, flags in PATHS.items():
+        eb = _batch(eng, wins, TS_H, TS_W, flags)
+        g64 = eb.time_surface(slices, float(tau), out=_nan(eb, 2 * slices)).cpu().numpy()
+        g32 = eb.time_surface(slices, float(tau), dtype=torch.float32, out=_nan(eb, 2 * slices, torch.float32)).cpu().numpy()
+        eb.check_built("time surface")
+        for b, name in enumerate(names):
+            tag = "time surface tau %d, %d slices, window %s, %s" % (tau, slices, name, path)
+            check_ts64(g64[b], want[b], tag + " (float64)")
+            check_ts32(g32[b], want[b], tag + " (float32)")
+
+
+def _ni(ev):
+    """n_imagenet reads p in {-1, +1} (parse_event) and its own normalised time, float64 (imagenet.py:198-199)."""
+    e = ev.copy()
+    e[:, 3] = np.where(ev[:, 3] > 0, 1, -1)
+    t = ev[:, 2].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tn = (t - t[0]) / (t[-1] - t[0])
+    return e, e.astype(np.float64), tn
+
+
+def test_every_builder_at_the_int32_edges(oracle):
+    from event_representation_study_amd import engine as eng
+    H, W = EDGE_H, EDGE_W
+    named = edge_windows()
+    names = list(named) + ["ordinary"]
+    wins = list(named.values()) + [make_events(3000, W, H, seed=78, polarity="01")]
+    ni = [_ni(ev) for ev in wins]
+
+    def voxel_or_none(ev):      # compute_repr on a window of one timestamp: the reference raises, the builder's grid is unspecified
+        try:
+            return oracle.voxel(ev, H, W, 5)
+        except oracle.OracleIndexError:
+            return None
+
+    want = []
+    with np.errstate(all="ignore"):      # the flat window's 0 / 0, the wrapped window's exp overflow: the reference's too
+        for ev, (nev, rows, _) in zip(wins, ni):
+            ref = oracle.ergo12(ev, H, W)
+            want.append({
+                "ergo12": ref, "ergo12_f32": ref.astype(np.float32), "event_stack": oracle.event_stack(ev, H, W),
+                "ts": oracle.time_surface(ev, H, W), "voxel": voxel_or_none(ev), "evl": oracle.evl_voxel(ev, H, W, 9),
+                "tore": oracle.tore(ev[:, 0] + 1, ev[:, 1] + 1, ev[:, 2], ev[:, 3], ev[-1, 2], 6, (H, W)),
+                "tore_bbox": oracle.tore_bbox(ev, 6),
+                "mdes_sbn": oracle.mdes(ev, H, W, *MDES_SBN), "mdes_sbt": oracle.mdes_sbt(ev, H, W, *MDES_SBT),
+                "acc_all": oracle.nimagenet_acc("acc_all", rows, H, W), "acc_exp": oracle.nimagenet_acc("acc_exp", rows, H, W),
+            })
+    tn = torch.from_numpy(np.concatenate([t for _, _, t in ni])).cuda()
+    voxel12 = None
+    for path, flags in PATHS.items():
+        eb = _batch(eng, wins, H, W, flags)
+        st = eb.status()
+        for b, name in enumerate(names):
+            assert bool(st[b] & _lib.ST_UNSORTED) == (name == "wrap"), (name, path, int(st[b]))
+            assert bool(st[b] & _lib.ST_FLAT_TIME) == (name == "flat"), (name, path, int(st[b]))
+        got = {
+            "ergo12": eb.optimized(out=_nan(eb, 12)), "ergo12_f32": eb.optimized(dtype=torch.float32, out=_nan(eb, 12, torch.float32)),
+            "event_stack": eb.event_stack(out=_nan(eb, 12, torch.float32)),
+            "ts": eb.time_surface(out=_nan(eb, 12)), "ts32": eb.time_surface(dtype=torch.float32, out=_nan(eb, 12, torch.float32)),
+            "voxel": eb.voxel(5, out=_nan(eb, 5)), "evl": eb.voxel(9, mode=2, out=_nan(eb, 9)),
+            "tore": eb.tore(6, frame_mode=2, out=_nan(eb, 12, torch.float32)),
+            "mdes_sbn": eb.mdes(*MDES_SBN, out=_nan(eb, 4)), "mdes_sbt": eb.mdes(*MDES_SBT, out=_nan(eb, 4), stacking="SBT"),
+            "voxel12": eb.voxel(12, mode=1, scale=255.0, out=_nan(eb, 12)),
+        }
+        got = {k: v.cpu().numpy() for k, v in got.items()}
+        bbox = [t.cpu().numpy() for t in eb.tore(6, frame_mode=0, out=_nan(eb, 12, torch.float32))]
+        eb.check_built("edge windows")
+        eb_ni = _batch(eng, [e for e, _, _ in ni], H, W, flags)
+        acc_all = eb_ni.polstats(tn, [1, 2, 1, 2, 1, 2], [0, 0, 1, 1, 2, 2], out=_nan(eb_ni, 6, torch.float32)).cpu().numpy()
+        acc_exp = eb_ni.polstats(tn, [1, 2], [4, 4], tau=0.3, out=_nan(eb_ni, 2, torch.float32)).cpu().numpy()
+        # tonic's ToVoxelGrid (mode 1) has no oracle entry point: every element written, the same grid under every path
+        assert not np.isnan(got["voxel12"]).any(), "voxel12 unwritten elements, " + path
+        if voxel12 is None:
+            voxel12 = got["voxel12"]
+        assert_bit_equal(got["voxel12"], voxel12, "voxel12 %s vs %s" % (path, next(iter(PATHS))))
+        for b, name in enumerate(names):
+            r, tag = want[b], "window %s, %s" % (name, path)
+            for k in ("ergo12", "ergo12_f32", "event_stack", "voxel", "mdes_sbn", "mdes_sbt"):
+                if k == "mdes_sbt" and name == "wrap":     # (see test_mdes_sbt_on_a_window_that_is_not_ascending)
+                    assert not np.isnan(got[k][b]).any(), "%s unwritten elements, %s" % (k, tag)
+                elif r[k] is not None:
+                    assert_bit_equal(got[k][b], r[k], "%s %s" % (k, tag))
+                else:           # (the flat window's compute_repr: the reference raises; the grid must still be written)
+                    assert not np.isnan(got[k][b]).any(), "%s unwritten elements, %s" % (k, tag)
+            assert_bit_equal(np.ascontiguousarray(np.moveaxis(got["evl"][b], -1, 0)).astype(np.float32), r["evl"], "evl " + tag)
+            check_ts64(got["ts"][b], r["ts"], "time surface " + tag)
+            check_ts32(got["ts32"][b], r["ts"], "time surface f32 " + tag)
+            if name != "wide":     # (see test_tore_where_t_minus_ts_wraps_int32)
+                np.testing.assert_allclose(got["tore"][b], r["tore"], rtol=1e-6, atol=1e-6, err_msg="tore " + tag)
+                np.testing.assert_allclose(bbox[b], r["tore_bbox"], rtol=1e-6, atol=1e-6, err_msg="tore bbox " + tag)
+            np.testing.assert_array_equal(np.moveaxis(acc_all[b], -1, 0), r["acc_all"], err_msg="acc_all " + tag)
+            np.testing.assert_allclose(np.moveaxis(acc_exp[b], -1, 0), r["acc_exp"], rtol=1e-6, atol=1e-7, err_msg="acc_exp " + tag)
+
+
+@pytest.mark.xfail(strict=True, reason="the TORE builders form T - ts in int64; the reference's int32 T - ts wraps past INT32_MAX "
+                                       "(tore.py:20,35), which reorders the k-vectors and gives NaN -- not implemented yet")
+def test_tore_where_t_minus_ts_wraps_int32(oracle):
+    """The `wide` window (INT32_MIN + 1 ... INT32_MAX): TORE at T = t[-1] against the oracle, which follows the reference's
+    int32 wraparound (pinned by tests/golden/time_edges.npz)."""
+    from event_representation_study_amd import engine as eng
+    ev = edge_windows()["wide"]
+    H, W = EDGE_H, EDGE_W
+    with np.errstate(all="ignore"):
+        want = oracle.tore(ev[:, 0] + 1, ev[:, 1] + 1, ev[:, 2], ev[:, 3], ev[-1, 2], 6, (H, W))
+    assert np.isnan(want).any()
+    for path, flags in PATHS.items():
+        got = _batch(eng, [ev], H, W, flags).tore(6, frame_mode=2, out=_nan_shape((1, H, W, 12))).cpu().numpy()[0]
+        np.testing.assert_allclose(got, want, rtol=1e-6, atol=1e-6, err_msg="tore wide, " + path)
+
+
+@pytest.mark.xfail(strict=True, reason="k_mdes_sbt_windows cuts the SBT windows as rank ranges between t[0] and t[-1]; on a window "
+                                       "that is not ascending the reference's windows are masks on t - t.min() -- not implemented yet")
+def test_mdes_sbt_on_a_window_that_is_not_ascending(oracle):
+    """The `wrap` window (an int64 recording cast to int32 across 2^31): MDES with SBT stacking against the oracle, which
+    follows the reference's boolean masks (pinned by tests/golden/time_edges_more.npz)."""
+    from event_representation_study_amd import engine as eng
+    ev = edge_windows()["wrap"]
+    H, W = EDGE_H, EDGE_W
+    want = oracle.mdes_sbt(ev, H, W, *MDES_SBT)
+    for path, flags in PATHS.items():
+        got = _batch(eng, [ev], H, W, flags).mdes(*MDES_SBT, stacking="SBT").cpu().numpy()[0]
+        assert_bit_equal(got, want, "mdes SBT wrap, " + path)
+
+
+def _nan_shape(shape):
+    return torch.full(shape, float("nan"), dtype=torch.float32, device="cuda:0")
