@@ -79,7 +79,16 @@ SYMBOLS = {
     "evrep_otmi_scratch_bytes": (ctypes.c_size_t, [_i32]),
     "evrep_otmi_event_clouds": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
     "evrep_otmi_rep_clouds": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "evrep_filter_pixel_fsm": (ctypes.c_int, [_PP, _vp, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp]),
+    "evrep_filter_background": (ctypes.c_int, [_PP, _vp, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _vp]),
+    "evrep_filter_mask_gather": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp]),
+    "evrep_filter_cell_map": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "evrep_filter_compact_scratch_bytes": (ctypes.c_size_t, [_i32, _i64]),
+    "evrep_filter_compact": (ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
+# evrep_filter_pixel_fsm kinds
+FILTER_REFRACTORY, FILTER_CONTRAST, FILTER_CHANGE_MAP = 0, 1, 2
+FILTER_MAX_RADIUS = 4
 
 # evrep_plan_init_ex flags.  The C library reads no environment variable; the A/B switches of the tests and tools
 # are translated here, when a plan is made.

@@ -366,6 +366,120 @@ class EventBatch:
                                            self._sp()), "evrep_est_voxel")
         return out
 
+    # ------------------------------------------------------------------ event filters (ev-licious tools/filters.py)
+    # Each filter returns (keep, state): keep = (total,) uint8 device tensor, one byte per event in array order; state = the
+    # reference's per-pixel state array as a (B, H, W) device tensor, updated IN PLACE when it was handed in -- hand it to
+    # the next window of the same recording to carry the filter on.  No call waits for the device; with t_base the copy of the
+    # window time bases (B * 8 bytes of pageable host memory) is staged by the HIP runtime before the call returns.
+    def _filter_state(self, state, dtype, fill):
+        shape = (self.B, self.H, self.W)
+        if state is None:
+            return torch.full(shape, fill, dtype=dtype, device=self.device)
+        if tuple(state.shape) != shape or state.dtype != dtype or not state.is_contiguous() or state.device != self.device:
+            raise ValueError("state must be a contiguous %s tensor of shape %r on %s" % (dtype, shape, self.device))
+        return state
+
+    def _t_base(self, t_base):
+        """None -> NULL; else one absolute int64 time per window (a scalar serves every window), kept alive on the batch."""
+        if t_base is None:
+            self._t_base_host = None
+            return ctypes.c_void_p(None)
+        tb = np.ascontiguousarray(np.broadcast_to(np.asarray(t_base, dtype=np.int64).reshape(-1), (self.B,)))
+        self._t_base_host = tb
+        return tb.ctypes.data_as(ctypes.c_void_p)
+
+    def _filter_fsm(self, kind, param, state, dtype, fill, t_base=None):
+        if not float(param) > 0:
+            raise ValueError("the filter parameter must be positive")
+        self.bin()
+        state = self._filter_state(state, dtype, fill)
+        keep = torch.empty(self.total, dtype=torch.uint8, device=self.device)
+        with self._dev():
+            check(self.lib.evrep_filter_pixel_fsm(*self._args(), int(kind), float(param), self._t_base(t_base), _ptr(state),
+                                                  _ptr(keep), self._sp()), "evrep_filter_pixel_fsm")
+        return keep, state
+
+    def filter_refractory(self, period, state=None, t_base=None):
+        """RefractoryPeriod (utils.py:193-200): an event passes iff t - last >= period; only a passing event sets last.
+        state: (B, H, W) float64 absolute times, -inf at rest; t_base: absolute time of t == 0 of every window's t column."""
+        return self._filter_fsm(_lib.FILTER_REFRACTORY, period, state, torch.float64, -np.inf, t_base)
+
+    def filter_contrast(self, factor, state=None):
+        """ContrastThresholdIncrease (utils.py:184-191): activity += p; passes iff |activity| >= factor, then activity = 0.
+        state: (B, H, W) int32.  p must be in {-1, +1}, as in the reference's Events."""
+        return self._filter_fsm(_lib.FILTER_CONTRAST, factor, state, torch.int32, 0)
+
+    def filter_background(self, depth_us, radius, state=None, t_base=None):
+        """BackgroundActivity (utils.py:170-179), 1 <= radius <= 4.  state: (B, H, W) float64 = the reference's `timestamps`."""
+        self.bin()
+        state = self._filter_state(state, torch.float64, -np.inf)
+        keep = torch.empty(self.total, dtype=torch.uint8, device=self.device)
+        with self._dev():
+            check(self.lib.evrep_filter_background(*self._args(), float(depth_us), int(radius), self._t_base(t_base), _ptr(state),
+                                                   _ptr(keep), self._sp()), "evrep_filter_background")
+        return keep, state
+
+    def filter_resize(self, height, width, state=None):
+        """resize_to_resolution's event selection (utils.py:110-158) -> (keep, state, cells): cells = a new EventBatch of
+        the SAME events with the coordinates (x // fx, y // fy) on the (H // fy) x (W // fx) sensor, so
+        ``cells.compacted(keep)`` is the down-sampled stream.  state: (B, H // fy, W // fx) float32 change map."""
+        fx, fy = int(self.W / int(width)), int(self.H / int(height))
+        if fx < 1 or fy < 1 or self.W % fx or self.H % fy or self.W // fx != int(width) or self.H // fy != int(height):
+            raise ValueError("the sensor %dx%d is not %dx%d whole cells of %dx%d pixels (the reference's change map is "
+                             "(height, width): it raises IndexError)" % (self.W, self.H, int(width), int(height), fx, fy))
+        ev = torch.empty_like(self.events)
+        if self.total:
+            with self._dev():
+                check(self.lib.evrep_filter_cell_map(_ptr(self.events), self.total, self.H, self.W, fy, fx, _ptr(ev), self._sp()),
+                      "evrep_filter_cell_map")
+        cells = EventBatch(ev, self.offsets_host, self.H // fy, self.W // fx,
+                           max_events_per_window=int(self.plan.max_events_per_window), plan_flags=int(self.plan.flags))
+        cells._pinned_stream = self._pinned_stream
+        keep, state = cells._filter_fsm(_lib.FILTER_CHANGE_MAP, fx * fy, state, torch.float32, 0.0)
+        return keep, state, cells
+
+    def filter_mask(self, mask):
+        """HotPixel.insert (filters.py:53): keep[i] = mask[b, y, x].  mask: (B, H, W) or (H, W) bool / uint8 device tensor."""
+        m = mask.to(self.device)
+        if m.dtype != torch.uint8:          # (the kernel reads any non-zero byte as True)
+            m = m.ne(0).to(torch.uint8)
+        if m.dim() == 2:
+            m = m.unsqueeze(0).expand(self.B, -1, -1)
+        m = m.contiguous()
+        if tuple(m.shape) != (self.B, self.H, self.W):
+            raise ValueError("mask must be (B, H, W) or (H, W)")
+        keep = torch.empty(self.total, dtype=torch.uint8, device=self.device)
+        if self.total:
+            with self._dev():
+                check(self.lib.evrep_filter_mask_gather(_ptr(self.events), _ptr(self.offsets), self.B, self.H, self.W,
+                                                        int(self.plan.max_events_per_window), _ptr(m), _ptr(keep), self._sp()),
+                      "evrep_filter_mask_gather")
+        return keep, m
+
+    def pixel_counts(self):
+        """Events per pixel -> (B, H, W) float32 (the COUNT accumulator of evrep_polstats; HotPixel.calibrate's np.add.at)."""
+        tn = torch.zeros(self.total, dtype=torch.float64, device=self.device)
+        return self.polstats(tn, [0], [0])[..., 0]
+
+    def compacted(self, keep):
+        """The kept rows of every window, in order, as a new EventBatch on the same device and stream (ready for
+        .optimized() / .tore() / ...).  The compaction and the new offsets are formed on the device; ONE host
+        synchronisation follows: the read of the new offsets, which sizes the new batch's plan."""
+        if keep.dtype != torch.uint8 or keep.numel() != self.total or keep.device != self.device or not keep.is_contiguous():
+            raise ValueError("keep must be a contiguous uint8 tensor with one entry per event on %s" % self.device)
+        off_out = torch.zeros(self.B + 1, dtype=torch.int64, device=self.device)
+        ev_out = torch.empty((max(self.total, 1), 4), dtype=torch.int32, device=self.device)
+        if self.total:
+            scratch = torch.empty(int(self.lib.evrep_filter_compact_scratch_bytes(self.B, self.total)), dtype=torch.uint8,
+                                  device=self.device)
+            with self._dev():
+                check(self.lib.evrep_filter_compact(_ptr(self.events), _ptr(self.offsets), self.B, _ptr(keep), _ptr(ev_out),
+                                                    _ptr(off_out), _ptr(scratch), self._sp()), "evrep_filter_compact")
+        off_host = off_out.cpu()
+        out = EventBatch(ev_out[: int(off_host[-1])], off_host, self.H, self.W, plan_flags=int(self.plan.flags))
+        out._pinned_stream = self._pinned_stream
+        return out
+
 
 class BinBuildPipeline:
     """Throughput path for a STREAM of batches: the binning pass of batch k+1 runs on a side HIP stream

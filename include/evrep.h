@@ -351,6 +351,55 @@ int evrep_entropic_gw(const double *C1, int64_t n, const double *C2, int64_t m, 
                       int32_t loss, double epsilon, int32_t outer_iters, int32_t sinkhorn_iters, int32_t precision,
                       void *scratch, double *T_out, double *gw_out, void *stream);
 
+/* The ev-licious event filters (ev-licious/src/evlicious/tools/filters.py:23-109, tools/utils.py:110-200) on the device.
+ * Every filter writes keep DEVICE uint8 [total_events]: one byte per event in ARRAY order, 1 = the event passes; an event
+ * outside the frame (the reference raises IndexError) is dropped and touches no state.  `state` DEVICE [B,H,W] is the
+ * reference's per-pixel state array: read as the incoming state, overwritten with the outgoing one, so successive windows of
+ * one recording chain calls; the windows of one batch are independent.  t_base HOST int64 [B]: the absolute time of t == 0
+ * of each window's int32 t column (NULL: 0); it is copied with hipMemcpyAsync into the workspace (the slot evrep_time_surface
+ * keeps its cuts in during a call): a PAGEABLE array is staged by the HIP runtime before the call returns and may be released
+ * then (the call may wait for that staging); a PINNED array must stay unchanged until `stream` has reached the copy.  All of
+ * them need a plan whose binning pass has run on this workspace.  The library cannot tell (a plan is read-only host data, so
+ * EVREP_ENOTBINNED is not returned): on an unbinned or foreign workspace the result is UNDEFINED -- where the kernels find
+ * the stream's offsets inconsistent with the window they leave every event dropped and the state untouched.  They give the
+ * same mask under every binning pass; after the key-sorted pass (reserved == 2) they run the per-key column sort first.
+ *
+ * evrep_filter_pixel_fsm: the sequential per-pixel filters, `kind`:
+ *   EVREP_FILTER_REFRACTORY  RefractoryPeriod (utils.py:193-200): an event passes iff t - last >= param (the period), and only
+ *                            a passing event sets last = t.  state float64, absolute time, -inf at rest.
+ *   EVREP_FILTER_CONTRAST    ContrastThresholdIncrease (utils.py:184-191): activity += p; passes iff |activity| >= param (the
+ *                            factor), then activity = 0.  state int32.  The reference's Events hold p in {-1, +1}.
+ *   EVREP_FILTER_CHANGE_MAP  resize_to_resolution's change map (utils.py:143-158) over a batch of CELL coordinates
+ *                            (evrep_filter_cell_map): change += p * 1.0 / param (param = fx * fy; float64 sum rounded to float32),
+ *                            passes iff |change| >= 1, then change -= p.  state float32.
+ *   param must be > 0.  t_base is only read by EVREP_FILTER_REFRACTORY.
+ * evrep_filter_background: BackgroundActivity (utils.py:170-179): event i is dropped iff t_last > 0 and t - t_last > depth with
+ *   t_last = timestamps[y, x] before the update; every event then writes t into rows [max(y - r, 0), y + r), columns
+ *   [max(x - r, 0), x + r).  Evaluated in closed form: t_last = t of the latest earlier event j (array order) with
+ *   x - r + 1 <= x_j <= x + r and y - r + 1 <= y_j <= y + r, else the incoming state.  1 <= radius <= EVREP_FILTER_MAX_RADIUS,
+ *   depth > 0.  state float64 [B,H,W] in / out = the reference's `timestamps`, absolute time, -inf at rest.
+ * evrep_filter_mask_gather: HotPixel.insert (filters.py:53): keep[i] = mask[b, y, x] != 0; mask DEVICE uint8 [B,H,W].
+ * evrep_filter_cell_map: events_out[i] = (x // fx, y // fy, t, p), the cells of resize_to_resolution (utils.py:150-151);
+ *   out-of-frame events get (-1, -1).  events_out DEVICE int32 [total,4].
+ * evrep_filter_compact: STABLE compaction of the kept rows of all B windows: events_out DEVICE int32 [>= kept,4] (total rows
+ *   always suffice), offsets_out DEVICE int64 [B+1]; the sizes are read on the device, nothing returns to the host.  scratch
+ *   DEVICE of evrep_filter_compact_scratch_bytes(B, total) bytes, 16-byte aligned, no initialisation needed. */
+#define EVREP_FILTER_REFRACTORY 0
+#define EVREP_FILTER_CONTRAST 1
+#define EVREP_FILTER_CHANGE_MAP 2
+#define EVREP_FILTER_MAX_RADIUS 4
+int evrep_filter_pixel_fsm(const evrep_plan *plan, const int32_t *events, const int64_t *offsets, void *workspace, int32_t kind,
+                           double param, const int64_t *t_base, void *state, uint8_t *keep, void *stream);
+int evrep_filter_background(const evrep_plan *plan, const int32_t *events, const int64_t *offsets, void *workspace, double depth,
+                            int32_t radius, const int64_t *t_base, double *state, uint8_t *keep, void *stream);
+int evrep_filter_mask_gather(const int32_t *events, const int64_t *offsets, int32_t B, int32_t H, int32_t W,
+                             int64_t max_events_per_window, const uint8_t *mask, uint8_t *keep, void *stream);
+int evrep_filter_cell_map(const int32_t *events, int64_t total, int32_t H, int32_t W, int32_t fy, int32_t fx, int32_t *events_out,
+                          void *stream);
+size_t evrep_filter_compact_scratch_bytes(int32_t B, int64_t total);
+int evrep_filter_compact(const int32_t *events, const int64_t *offsets, int32_t B, const uint8_t *keep, int32_t *events_out,
+                         int64_t *offsets_out, void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
