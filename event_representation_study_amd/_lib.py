@@ -85,7 +85,13 @@ SYMBOLS = {
     "evrep_filter_cell_map": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     "evrep_filter_compact_scratch_bytes": (ctypes.c_size_t, [_i32, _i64]),
     "evrep_filter_compact": (ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "evrep_time_to_index": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    "evrep_windows_gather": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
+# evrep_windows_gather: rebase modes, per-window status bits, limits
+REBASE_NONE, REBASE_FIRST, REBASE_GIVEN = 0, 1, 2
+WST_BAD_RANGE, WST_T_OVERFLOW, WST_BAD_OFFSETS = 1, 2, 4
+WINDOWS_MAX_QUERIES, WINDOWS_MAX_B = 1 << 30, 1 << 24
 # evrep_filter_pixel_fsm kinds
 FILTER_REFRACTORY, FILTER_CONTRAST, FILTER_CHANGE_MAP = 0, 1, 2
 FILTER_MAX_RADIUS = 4

@@ -69,6 +69,7 @@ class EventBatch:
         nbytes = int(self.lib.evrep_workspace_bytes(ctypes.byref(self.plan)))
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self._binned = False
+        self.t_base = None      # numpy int64 (B,): absolute time of t == 0 per window, set by DeviceRecording.windows; no builder reads it
         # The per-sample wrappers (representations/_common.py) keep one pooled batch per (host thread, device, stream) and only use
         # it there: they pin the stream pointer and skip the device guard (torch.cuda.current_stream() + torch.cuda.device() cost
         # ~8 us per call of the ~100 us a sample takes).  None: look both up per call, as every other user must.

@@ -6,7 +6,8 @@ every precomputed representation in: ``fh.create_dataset("repr", data=rep.astype
 (ev-YOLOv6/yolov6/data/gen4/precompute_reps.py:432-435), read back by ``gen4_2yolo.py:383-386`` with plain h5py.
 Layout: superblock version 0, version-1 object headers, an old-style root group (symbol-table message -> v1 B-tree
 -> symbol-table node -> local heap), a version-3 contiguous data layout.  The header is a pure function of
-(name, shape, dtype), so a writer thread emits ``header + array bytes`` with two writes.
+(name, shape, dtype), so a writer thread emits ``header + array bytes`` with two writes.  ``write_tree_file`` writes a
+nested dict of arrays as old-style groups of contiguous datasets (small Gen1 / ev-licious shaped containers).
 
 READ (``File``): what h5py's defaults (libver "earliest") produce, which is how the reference's inputs are made --
 Gen1 / gen4 event datasets (precompute_reps.py:307-308,408-409) and ev-licious ``events/{x,y,p,t}``
@@ -122,6 +123,65 @@ def write_dataset_file(path, name, array, data_align=4096):
     with open(path, "wb") as f:
         f.write(head)
         f.write(memoryview(a).cast("B") if a.size else b"")
+
+
+def write_tree_file(path, tree):
+    """Write a nested dict -- name -> dict (a group) or array (a contiguous dataset; 0-d arrays are scalars) -- as a new HDF5
+    file of old-style groups: the shape of the reference's Gen1 and ev-licious containers (``<recording>/events/{x, y, t, p,
+    height, width}``).  The same structures as ``dataset_file_header`` (superblock 0, version-1 object headers, one symbol-table
+    node per group), so a group holds at most 8 links (2 x the leaf K of 4 the superblock declares)."""
+    out = bytearray(b"\x00" * 96)
+
+    def place(data, align=8):
+        out.extend(b"\x00" * (-len(out) % align))
+        addr = len(out)
+        out.extend(data)
+        return addr
+
+    def dataset(array):
+        a = np.ascontiguousarray(array)
+        if a.dtype.byteorder == ">":
+            a = a.astype(a.dtype.newbyteorder("<"))
+        shape = tuple(np.shape(array))
+        dataspace = struct.pack("<BBBB4x", 1, len(shape), 0, 0) + b"".join(struct.pack("<Q", s) for s in shape)
+        msgs = _msg(0x0001, dataspace) + _msg(0x0003, _datatype_message(a.dtype), flags=1) + \
+            _msg(0x0005, struct.pack("<BBBB", 2, 1, 0, 0), flags=1)
+        data_addr = place(a.tobytes() if a.size else b"\x00" * 8)
+        msgs += _msg(0x0008, struct.pack("<BBQQ", 3, 1, data_addr if a.size else UNDEF, a.nbytes))
+        return place(struct.pack("<BBHII4x", 1, 0, 4, 1, len(msgs)) + msgs)
+
+    def group(links):
+        """-> (object header, B-tree, local heap) addresses; children are written first and linked by their header address"""
+        if len(links) > 8:
+            raise ValueError("a group of write_tree_file holds at most 8 links")
+        names = sorted(links, key=lambda s: s.encode("ascii"))         # a symbol-table node is ordered by name
+        if any(not n or "/" in n for n in names):
+            raise ValueError("a link name must be a single non-empty path component")
+        addrs = [group(links[n])[0] if isinstance(links[n], dict) else dataset(links[n]) for n in names]
+        heap_data, name_off = _pad8(b"\x00"), []
+        for n in names:
+            name_off.append(len(heap_data))
+            heap_data += _pad8(n.encode("ascii") + b"\x00")
+        free_head = len(heap_data)
+        heap_data += struct.pack("<QQ", 1, 16)
+        heap = place(b"HEAP" + struct.pack("<B3xQQQ", 0, len(heap_data), free_head, len(out) + (-len(out) % 8) + 32) + heap_data)
+        snod = b"SNOD" + struct.pack("<BBH", 1, 0, len(names))
+        snod += b"".join(struct.pack("<QQII16x", o, a, 0, 0) for o, a in zip(name_off, addrs))
+        snod = place(snod + b"\x00" * (8 + 2 * 4 * 40 - len(snod)))
+        tree_node = b"TREE" + struct.pack("<BBHQQ", 0, 0, 1 if names else 0, UNDEF, UNDEF) + \
+            struct.pack("<QQQ", 0, snod, name_off[-1] if names else 0)
+        btree = place(tree_node + b"\x00" * (24 + (2 * 16 + 1) * 8 + 2 * 16 * 8 - len(tree_node)))
+        header = place(struct.pack("<BBHII4x", 1, 0, 1, 1, 24) + _msg(0x0011, struct.pack("<QQ", btree, heap)))
+        return header, btree, heap
+
+    root, btree, heap = group(tree)
+    sb = SIGNATURE + struct.pack("<BBBBBBBB", 0, 0, 0, 0, 0, 8, 8, 0) + struct.pack("<HHI", 4, 16, 0)
+    sb += struct.pack("<QQQQ", 0, UNDEF, len(out), UNDEF)
+    sb += struct.pack("<QQII", 0, root, 1, 0) + struct.pack("<QQ", btree, heap)
+    assert len(sb) == 96
+    out[:96] = sb
+    with open(path, "wb") as f:
+        f.write(out)
 
 
 # ------------------------------------------------------------------------------------------------ reader

@@ -400,6 +400,38 @@ size_t evrep_filter_compact_scratch_bytes(int32_t B, int64_t total);
 int evrep_filter_compact(const int32_t *events, const int64_t *offsets, int32_t B, const uint8_t *keep, int32_t *events_out,
                          int64_t *offsets_out, void *scratch, void *stream);
 
+/* Windows cut from a DEVICE-RESIDENT recording (ev-licious/src/evlicious/io/h5_event_handle.py:10-11,52-103,
+ * io/utils/event_handle.py:51-58; ev-YOLOv6/yolov6/data/gen1_2yolo.py:186-198).  The recording is uploaded once as the
+ * structure-of-arrays columns ev-licious' Events hold (io/utils/events.py:7-8): x, y uint16, t int64 ascending, p int8, n
+ * events.  Neither call takes a plan or a workspace, allocates, or waits for the device.
+ *
+ * evrep_time_to_index: out_idx[k] = the first index i with t[i] > queries[k], n if there is none -- numpy's
+ *   searchsorted(t, q, side="right"); with q = ceil(q' + 1e-3) - 1 this is the reference's searchsorted(t, q' + 1e-3) on
+ *   integral microsecond times, ties included.  t DEVICE int64 [n], queries DEVICE int64 [nq], out_idx DEVICE int64 [nq].
+ *   One wavefront per query, a 64-ary search of ceil(log64 n) rounds.  nq <= EVREP_WINDOWS_MAX_QUERIES.
+ * evrep_windows_gather: B source ranges [i0[b], i1[b]) -- they may overlap, repeat or be empty -- into packed int32 rows:
+ *   events_out[dst_offsets[b] + k] = (x[i0[b] + k], y[..], t[..] - base[b], p[..]), rows [dst_offsets[0], dst_offsets[B]).
+ *   i0, i1 DEVICE int64 [B]; dst_offsets DEVICE int64 [B+1], ascending, dst_offsets[b+1] - dst_offsets[b] = i1[b] - i0[b];
+ *   events_out DEVICE int32 [>= dst_offsets[B], 4], 16-byte aligned.  rebase_mode: EVREP_REBASE_NONE base = 0;
+ *   EVREP_REBASE_FIRST base[b] = t[i0[b]] (Gen1's _load_events; 0 for an empty window); EVREP_REBASE_GIVEN base[b] =
+ *   base_in[b], DEVICE int64 [B] (NULL otherwise).  base_out DEVICE int64 [B] receives base[b]; status_out DEVICE uint32 [B]
+ *   receives EVREP_WST_* bits (cleared by the call).  p is copied as stored.  B <= EVREP_WINDOWS_MAX_B.
+ *   EVREP_WST_BAD_RANGE: i0 < 0, i0 > i1 or i1 > n -- nothing of that window is read or written.
+ *   EVREP_WST_T_OVERFLOW: some t - base[b] is outside int32; those rows are written SATURATED (INT32_MAX / INT32_MIN).
+ *   EVREP_WST_BAD_OFFSETS: dst_offsets gives the window more rows than its range holds; the surplus rows are not written. */
+#define EVREP_REBASE_NONE 0
+#define EVREP_REBASE_FIRST 1
+#define EVREP_REBASE_GIVEN 2
+#define EVREP_WST_BAD_RANGE 1u
+#define EVREP_WST_T_OVERFLOW 2u
+#define EVREP_WST_BAD_OFFSETS 4u
+#define EVREP_WINDOWS_MAX_QUERIES (1 << 30)
+#define EVREP_WINDOWS_MAX_B (1 << 24)
+int evrep_time_to_index(const int64_t *t, int64_t n, const int64_t *queries, int64_t nq, int64_t *out_idx, void *stream);
+int evrep_windows_gather(const uint16_t *x, const uint16_t *y, const int64_t *t, const int8_t *p, int64_t n, const int64_t *i0,
+                         const int64_t *i1, const int64_t *dst_offsets, int32_t B, int32_t rebase_mode, const int64_t *base_in,
+                         int32_t *events_out, int64_t *base_out, uint32_t *status_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
