@@ -87,7 +87,13 @@ SYMBOLS = {
     "evrep_filter_compact": (ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "evrep_time_to_index": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "evrep_windows_gather": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "evrep_nimg_prepare_scratch_bytes": (ctypes.c_size_t, [_i32, _i64]),
+    "evrep_nimg_prepare": (ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _f64, _f64, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+# evrep_nimg_prepare: mode flags, per-window parameter flags, per-window status bits
+NIMG_TRAIN, NIMG_P_UINT8 = 1, 2
+AUG_TIME_FLIP, AUG_X_FLIP = 1, 2
+AUG_EMPTY, AUG_FLAT_TIME, AUG_BAD_SLICE = 1, 2, 4
 # evrep_windows_gather: rebase modes, per-window status bits, limits
 REBASE_NONE, REBASE_FIRST, REBASE_GIVEN = 0, 1, 2
 WST_BAD_RANGE, WST_T_OVERFLOW, WST_BAD_OFFSETS = 1, 2, 4

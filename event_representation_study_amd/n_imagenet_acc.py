@@ -92,7 +92,8 @@ def _window(ev, H, W):
 def accumulate_batch(name, event_tensors, height=IMAGE_H, width=IMAGE_W, device="cuda:0"):
     """Batched form: a list of (N_b, 4) float64 event tensors -> (B, C, H, W) float32 CUDA tensor (a
     channel-first VIEW of the builder's (B, H, W, C) output, like the reference's permute(2, 0, 1))."""
-    pol, stat = SPECS[name]
+    if name not in SPECS:
+        raise KeyError(name)
     wins = [_as_f64(e) for e in event_tensors]
     for w in wins:
         if len(w) == 0:
@@ -100,6 +101,13 @@ def accumulate_batch(name, event_tensors, height=IMAGE_H, width=IMAGE_W, device=
     packed = [_window(w, height, width) for w in wins]
     batch = EventBatch.from_numpy([r for r, _ in packed], height, width, device=device)
     tnorm = torch.from_numpy(np.concatenate([t for _, t in packed]) if packed else np.zeros(0)).to(batch.device)
+    return _accumulate(name, batch, tnorm)
+
+
+def _accumulate(name, batch, tnorm):
+    """The part of accumulate_batch behind the upload (n_imagenet_front.accumulate_device enters here with device-made rows):
+    the polstats builder and the two window-level normalisations."""
+    pol, stat = SPECS[name]
     out = batch.polstats(tnorm, pol, stat, tau=EXP_TAU)            # (B, H, W, C) float32
     if name == "acc":          # pos_count / pos_count.max().float()  (:190-191,196-197): float32 / float32
         for c in (0, 2):

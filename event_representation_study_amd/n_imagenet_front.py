@@ -1,0 +1,346 @@
+"""N-ImageNet's event front end and base_augment("train"), on the host under the reference's names and on the device.
+
+What n_imagenet/real_cnn_model/data/imagenet.py does to every sample in front of its accumulators:
+
+    load_event                   :30-57      columns -> float64 rows [x, y, t / 1e6, p]; p goes through uint8, and where no p is
+                                             below -0.5 (always, after uint8) every p <= 0.5 becomes -1
+    parse_event                  :128-163    reshape_event_no_sample (sensor 640x480 -> image 224x224, a float64 multiply) and
+                                             slice_event (:60-84: "idx", "time", "random")
+    base_augment("train")        :1176-1187  random_time_flip, random_flip_events_along_x, random_shift_events (+ crop to the frame)
+
+HOST MIRRORS (same names, same signatures, same in-place side effects on the caller's tensor: the no-flip path mutates it, the
+time flip returns a copy): ``load_event``, ``slice_event``, ``reshape_event_no_sample``, ``parse_event``, ``random_time_flip``,
+``random_flip_events_along_x``, ``random_shift_events``, ``base_augment``.  They are the restatement the CPU tests pin against
+tests/golden/nimg_front.npz, which the reference's own functions wrote.
+
+DEVICE PATH.  ``NImageNetFrontEnd(cfg, mode).prepare(batch)`` runs all of the above for B windows in ONE call of
+``evrep_nimg_prepare`` (csrc/evrep_augment.hip: a count launch, one scan workgroup, a write launch) on the packed int32 rows
+``[x, y, t - base, p as stored]`` of an ``EventBatch`` -- what ``DeviceRecording.windows`` gathers -- and returns an
+``AugmentedBatch``: the kept rows ``[trunc x, trunc y, 0, sign p]`` as a new ``EventBatch`` on the image frame, the float64
+``t`` and ``tnorm`` every accumulator forms (:198-199), the untruncated ``xy``, and per-window counts and status words.  One host
+read of B counts and status words sizes the next plan, as ``EventBatch.compacted`` does.  ``accumulate_device(name, aug)`` then
+builds any of the eleven ``n_imagenet_acc.SPECS`` accumulators from it.  The random parameters are drawn on the host by
+``draw_slice`` / ``draw_augment`` from the global ``random`` / ``np.random`` streams in exactly the order B sequential reference
+calls consume them, so seeding the two generators reproduces the reference's batch.
+
+OUT OF SCOPE.  ``reshape_method`` "sample" and "unique" (``reshape_event_with_sample`` / ``reshape_event_unique`` raise
+NotImplementedError: the first draws a permutation of the whole sample, the second needs a key sort of it and is off by default
+in the reference); device-input forms of DiST, acc_sort and the ``_prep`` wrappers; the ``denoise_*`` options, which the
+reference reads and never uses.  There is no CPU fallback for the device path: without a HIP device it raises ``EvrepError``.
+"""
+import ctypes
+import random
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check
+from .engine import EventBatch, _ptr, _require_gpu, _stream_ptr
+
+SENSOR_H = 480     # imagenet.py:16-21
+SENSOR_W = 640
+IMAGE_H = 224
+IMAGE_W = 224
+TIME_SCALE = 1000000
+MAX_SHIFT = 20     # random_shift_events' default (:1140)
+
+# one evrep_nimg_params per window (include/evrep.h)
+PARAMS_DTYPE = np.dtype([("s0", "<i8"), ("s1", "<i8"), ("t_lo", "<f8"), ("t_hi", "<f8"), ("x_shift", "<i4"), ("y_shift", "<i4"),
+                         ("flags", "<u4"), ("reserved", "<u4")])
+assert PARAMS_DTYPE.itemsize == 48
+
+
+# ---------------------------------------------------------------------------------------------
+# host mirrors
+# ---------------------------------------------------------------------------------------------
+def event_rows(x, y, t, p):
+    """The float64 (N, 4) array load_event forms from the four stored columns (:35-55)."""
+    ev = np.vstack([x, y, t, np.asarray(p).astype(np.uint8)]).T.astype(np.float64)
+    ev[:, 2] /= TIME_SCALE
+    if ev[:, 3].min() >= -0.5:                 # zero polarity (:54-55); uint8 is never negative, so -1 arrives here as 255
+        ev[:, 3][ev[:, 3] <= 0.5] = -1
+    return ev
+
+
+def load_event(event_path, cfg):
+    data = np.load(event_path)
+    if getattr(cfg, "compressed", True):
+        rec = data["event_data"]
+        return event_rows(rec["x"], rec["y"], rec["t"], rec["p"])
+    return event_rows(data["x_pos"], data["y_pos"], data["timestamp"], data["polarity"])
+
+
+def slice_event(event, cfg):
+    method = getattr(cfg, "slice_method", "idx")
+    if method == "idx":
+        return event[getattr(cfg, "slice_start", None):getattr(cfg, "slice_end", None)]
+    if method == "time":
+        start, end = getattr(cfg, "slice_start", None), getattr(cfg, "slice_end", None)
+        return event[(event[:, 2] > start) & (event[:, 2] < end)]
+    if method == "random":
+        s0, s1 = _draw_random_slice(len(event), cfg)
+        return event if (s0, s1) == (0, len(event)) else event[s0:s1]
+    return event
+
+
+def _draw_random_slice(n, cfg):
+    """[s0, s1) of slice_method == "random" (:70-82), consuming Python's `random` as the reference does."""
+    length = getattr(cfg, "slice_length", None)
+    if getattr(cfg, "slice_augment", False) and cfg.mode == "train":
+        width = getattr(cfg, "slice_augment_width", 0)
+        length = random.randint(length - width, length + width)
+    if n > length:
+        start = random.choice(range(n - length + 1))
+        return _resolve(n, start, start + length)
+    return 0, n
+
+
+def _resolve(n, start, end):
+    a, e, _ = slice(start, end).indices(n)
+    return a, max(a, e)
+
+
+def reshape_event_no_sample(event, orig_h, orig_w, new_h, new_w):
+    event[:, 0] *= new_w / orig_w
+    event[:, 1] *= new_h / orig_h
+    return event
+
+
+def reshape_event_with_sample(event, orig_h, orig_w, new_h, new_w):
+    raise NotImplementedError("reshape_method 'sample' is not built (see the module docstring)")
+
+
+def reshape_event_unique(event, orig_h, orig_w, new_h, new_w):
+    raise NotImplementedError("reshape_method 'unique' is not built (see the module docstring)")
+
+
+_RESHAPE = {"no_sample": reshape_event_no_sample, "sample": reshape_event_with_sample, "unique": reshape_event_unique}
+
+
+def parse_event(event_path, cfg):
+    event = torch.from_numpy(load_event(event_path, cfg))
+    if getattr(cfg, "reshape", False):
+        fn = _RESHAPE.get(getattr(cfg, "reshape_method", "no_sample"))
+        if fn is not None:                        # (an unknown method leaves the events as they are, as the reference's chain does)
+            event = fn(event, SENSOR_H, SENSOR_W, IMAGE_H, IMAGE_W)
+    if getattr(cfg, "slice_events", False):
+        event = slice_event(event, cfg)
+    return event
+
+
+def time_flipped(event_tensor):
+    """A reversed COPY with t' = t_last - t and p' = -p (:1168-1172)."""
+    rev = torch.flip(event_tensor, [0])
+    rev[:, 2] = rev[0, 2] - rev[:, 2]
+    rev[:, 3] = -rev[:, 3]
+    return rev
+
+
+def x_flipped_(event_tensor, width):
+    event_tensor[:, 0] = width - 1 - event_tensor[:, 0]
+    return event_tensor
+
+
+def shifted_(event_tensor, x_shift, y_shift, resolution):
+    """In-place shift, then the rows inside the frame as a copy (:1143-1152)."""
+    H, W = resolution
+    event_tensor[:, 0] += x_shift
+    event_tensor[:, 1] += y_shift
+    x, y = event_tensor[:, 0], event_tensor[:, 1]
+    return event_tensor[(x >= 0) & (x < W) & (y >= 0) & (y < H)]
+
+
+def random_shift_events(event_tensor, max_shift=MAX_SHIFT, resolution=(IMAGE_H, IMAGE_W)):
+    x_shift, y_shift = np.random.randint(-max_shift, max_shift + 1, size=(2,))
+    return shifted_(event_tensor, x_shift, y_shift, resolution)
+
+
+def random_flip_events_along_x(event_tensor, resolution=(IMAGE_H, IMAGE_W), p=0.5):
+    if np.random.random() < p:
+        x_flipped_(event_tensor, resolution[1])
+    return event_tensor
+
+
+def random_time_flip(event_tensor, resolution=(IMAGE_H, IMAGE_W), p=0.5):
+    if np.random.random() < p:
+        event_tensor = time_flipped(event_tensor)
+    return event_tensor
+
+
+def base_augment(mode):
+    assert mode in ["train", "eval"]
+    if mode == "eval":
+        return None
+
+    def augment(event):
+        event = random_time_flip(event, resolution=(IMAGE_H, IMAGE_W))
+        event = random_flip_events_along_x(event)
+        return random_shift_events(event)
+    return augment
+
+
+def apply_augment(event_tensor, time_flip, x_flip, x_shift, y_shift, resolution=(IMAGE_H, IMAGE_W)):
+    """base_augment("train") with the draws handed in (the host restatement the device path is tested against)."""
+    if time_flip:
+        event_tensor = time_flipped(event_tensor)
+    if x_flip:
+        x_flipped_(event_tensor, resolution[1])
+    return shifted_(event_tensor, int(x_shift), int(y_shift), resolution)
+
+
+# ---------------------------------------------------------------------------------------------
+# the random parameters of B windows, drawn as B sequential reference calls draw them
+# ---------------------------------------------------------------------------------------------
+def draw_augment(B, mode):
+    """-> dict of (B,) arrays time_flip, x_flip (bool), x_shift, y_shift (int32).  "train": per window np.random.random(),
+    np.random.random(), np.random.randint(-20, 21, size=(2,)), always all three; "eval": nothing is drawn."""
+    assert mode in ["train", "eval"]
+    out = dict(time_flip=np.zeros(B, bool), x_flip=np.zeros(B, bool), x_shift=np.zeros(B, np.int32), y_shift=np.zeros(B, np.int32))
+    if mode == "train":
+        for b in range(B):
+            out["time_flip"][b] = np.random.random() < 0.5
+            out["x_flip"][b] = np.random.random() < 0.5
+            out["x_shift"][b], out["y_shift"][b] = np.random.randint(-MAX_SHIFT, MAX_SHIFT + 1, size=(2,))
+    return out
+
+
+def draw_slice(lengths, cfg):
+    """-> dict of (B,) arrays s0, s1 (int64 rows of the window, Python slice rules resolved), t_lo, t_hi (float64, the strict
+    time predicate; -inf / +inf when unused) for windows of `lengths` events under cfg's slice_* options."""
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    B = lengths.size
+    out = dict(s0=np.zeros(B, np.int64), s1=lengths.copy(), t_lo=np.full(B, -np.inf), t_hi=np.full(B, np.inf))
+    if not getattr(cfg, "slice_events", False):
+        return out
+    method = getattr(cfg, "slice_method", "idx")
+    if method == "time":
+        start, end = getattr(cfg, "slice_start", None), getattr(cfg, "slice_end", None)
+        if start is None or end is None:
+            raise TypeError("slice_method 'time' needs slice_start and slice_end")    # the reference compares a tensor with None
+        out["t_lo"][:], out["t_hi"][:] = float(start), float(end)
+    for b in range(B):
+        n = int(lengths[b])
+        if method == "idx":
+            out["s0"][b], out["s1"][b] = _resolve(n, getattr(cfg, "slice_start", None), getattr(cfg, "slice_end", None))
+        elif method == "random":
+            out["s0"][b], out["s1"][b] = _draw_random_slice(n, cfg)
+    return out
+
+
+def pack_params(slices, augment):
+    """The two dicts -> a (B,) PARAMS_DTYPE array, the table evrep_nimg_prepare reads."""
+    B = len(slices["s0"])
+    par = np.zeros(B, PARAMS_DTYPE)
+    for k in ("s0", "s1", "t_lo", "t_hi"):
+        par[k] = slices[k]
+    par["x_shift"], par["y_shift"] = augment["x_shift"], augment["y_shift"]
+    par["flags"] = np.where(augment["time_flip"], _lib.AUG_TIME_FLIP, 0) | np.where(augment["x_flip"], _lib.AUG_X_FLIP, 0)
+    return par
+
+
+def host_rows(x, y, t, p, par, sx=1.0, sy=1.0, train=True, resolution=(IMAGE_H, IMAGE_W)):
+    """One window through the host mirrors with the parameters of one PARAMS_DTYPE record: the (N', 4) float64 tensor the
+    reference's parse_event + base_augment leave (a stand-in for the files: the columns are handed in)."""
+    ev = torch.from_numpy(event_rows(x, y, t, p))
+    ev[:, 0] *= sx
+    ev[:, 1] *= sy
+    ev = ev[int(par["s0"]):int(par["s1"])]
+    if np.isfinite(par["t_lo"]) or np.isfinite(par["t_hi"]):
+        ev = ev[(ev[:, 2] > float(par["t_lo"])) & (ev[:, 2] < float(par["t_hi"]))]
+    flags = int(par["flags"])
+    if flags & _lib.AUG_TIME_FLIP:
+        ev = time_flipped(ev)
+    if flags & _lib.AUG_X_FLIP:
+        x_flipped_(ev, resolution[1])
+    return shifted_(ev, int(par["x_shift"]), int(par["y_shift"]), resolution) if train else ev
+
+
+# ---------------------------------------------------------------------------------------------
+# the device path
+# ---------------------------------------------------------------------------------------------
+class AugmentedBatch:
+    """What evrep_nimg_prepare leaves: ``batch`` (EventBatch of the kept rows [trunc x, trunc y, 0, sign p] on the image frame),
+    ``t`` / ``tnorm`` (float64, one per kept row), ``xy`` (float64 (kept, 2), untruncated), ``status`` (numpy uint32 (B,),
+    _lib.AUG_EMPTY / AUG_FLAT_TIME / AUG_BAD_SLICE), ``counts`` (numpy int64 (B,))."""
+
+    def __init__(self, batch, t, tnorm, xy, status, counts):
+        self.batch, self.t, self.tnorm, self.xy, self.status, self.counts = batch, t, tnorm, xy, status, counts
+
+
+class NImageNetFrontEnd:
+    """parse_event's reshape and slice + base_augment(mode) for B windows in one device call.  cfg: the reference's config
+    object (attributes reshape, reshape_method, slice_events, slice_method, slice_start, slice_end, slice_length, slice_augment,
+    slice_augment_width, mode, all optional as there); mode: "train" or "eval", base_augment's argument."""
+
+    def __init__(self, cfg, mode, sensor=(SENSOR_H, SENSOR_W), image=(IMAGE_H, IMAGE_W)):
+        assert mode in ["train", "eval"]
+        self.cfg, self.mode = cfg, mode
+        self.sensor, self.image = (int(sensor[0]), int(sensor[1])), (int(image[0]), int(image[1]))
+        self.sx = self.sy = 1.0
+        if getattr(cfg, "reshape", False):
+            method = getattr(cfg, "reshape_method", "no_sample")
+            if method in ("sample", "unique"):
+                _RESHAPE[method](None, *self.sensor, *self.image)
+            if method == "no_sample":
+                self.sx, self.sy = self.image[1] / self.sensor[1], self.image[0] / self.sensor[0]   # new_w / orig_w, new_h / orig_h
+        _require_gpu()
+        self.lib = _lib.load()
+
+    def draw(self, lengths):
+        """The (B,) PARAMS_DTYPE table of one batch, consuming `random` and `np.random` as B reference calls do."""
+        lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        return pack_params(draw_slice(lengths, self.cfg), draw_augment(lengths.size, self.mode))
+
+    def prepare(self, batch, t_base=None, params=None, want_xy=True, p_as_uint8=True):
+        """batch: EventBatch of sensor rows [x, y, t - base, p as stored]; t_base: int64 (B,) absolute time of t == 0 per window
+        (default: batch.t_base, else 0); params: a (B,) PARAMS_DTYPE array (default: self.draw); p_as_uint8: read p through
+        uint8 as load_event does (False: rows whose p is what load_event's cast would have left).  -> AugmentedBatch."""
+        B, total, dev = batch.B, batch.total, batch.device
+        lengths = (batch.offsets_host[1:] - batch.offsets_host[:-1]).numpy()
+        par = self.draw(lengths) if params is None else np.ascontiguousarray(params, dtype=PARAMS_DTYPE).reshape(-1)
+        if par.size != B:
+            raise ValueError("one parameter record per window: %d for %d windows" % (par.size, B))
+        if t_base is None:
+            t_base = batch.t_base
+        tb = np.zeros(B, np.int64) if t_base is None else \
+            np.ascontiguousarray(np.broadcast_to(np.asarray(t_base, dtype=np.int64).reshape(-1), (B,)))
+        table = torch.from_numpy(np.concatenate([par.view(np.uint8), tb.view(np.uint8)])).to(dev)       # one small upload
+        rows = max(total, 1)
+        ev_out = torch.empty((rows, 4), dtype=torch.int32, device=dev)
+        f64 = torch.empty(rows * (4 if want_xy else 2), dtype=torch.float64, device=dev)
+        t_out, tn_out = f64[:rows], f64[rows:2 * rows]
+        xy_out = f64[2 * rows:].view(rows, 2) if want_xy else None
+        meta = torch.empty((B + 1) * 8 + B * 4, dtype=torch.uint8, device=dev)      # offsets_out then status_out
+        scratch = torch.empty(int(self.lib.evrep_nimg_prepare_scratch_bytes(B, total)), dtype=torch.uint8, device=dev)
+        flags = (_lib.NIMG_P_UINT8 if p_as_uint8 else 0) | (_lib.NIMG_TRAIN if self.mode == "train" else 0)
+        with torch.cuda.device(dev):
+            check(self.lib.evrep_nimg_prepare(_ptr(batch.events), _ptr(batch.offsets), B, _ptr(table[B * 48:]), _ptr(table),
+                                              float(self.sx), float(self.sy), self.image[0], self.image[1], flags, _ptr(ev_out),
+                                              _ptr(t_out), _ptr(tn_out), _ptr(xy_out) if want_xy else ctypes.c_void_p(None),
+                                              _ptr(meta), _ptr(meta[(B + 1) * 8:]), _ptr(scratch), _stream_ptr()),
+                  "evrep_nimg_prepare")
+        host = meta.cpu().numpy()                                                    # the one synchronisation
+        off = host[:(B + 1) * 8].view(np.int64).copy()
+        status = host[(B + 1) * 8:].view(np.uint32).copy()
+        kept = int(off[-1])
+        out = EventBatch(ev_out[:kept], torch.from_numpy(off), self.image[0], self.image[1], plan_flags=int(batch.plan.flags))
+        return AugmentedBatch(out, t_out[:kept], tn_out[:kept], xy_out[:kept] if want_xy else None, status, np.diff(off))
+
+    def prepare_recording(self, rec, i0, i1, params=None, want_xy=True):
+        """Windows [i0[b], i1[b]) of a DeviceRecording, gathered and prepared on the device (rebased to each window's first
+        event; the absolute times come back through the batch's t_base)."""
+        batch = rec.windows(i0, i1, rebase="first")
+        return self.prepare(batch, t_base=batch.t_base, params=params, want_xy=want_xy)
+
+
+def accumulate_device(name, aug):
+    """One of the eleven n_imagenet_acc.SPECS accumulators from an AugmentedBatch -> (B, C, H, W) float32 device tensor, what
+    accumulate_batch(name, [the host-augmented tensors]) returns.  IndexError for a window without events, as there."""
+    from . import n_imagenet_acc as ni
+    if name not in ni.SPECS:
+        raise KeyError(name)
+    empty = np.flatnonzero(aug.status & _lib.AUG_EMPTY)
+    if empty.size:
+        raise IndexError("empty event tensor (sample %d)" % int(empty[0]))     # event_tensor[0, 2], imagenet.py:178
+    return ni._accumulate(name, aug.batch, aug.tnorm)

@@ -432,6 +432,54 @@ int evrep_windows_gather(const uint16_t *x, const uint16_t *y, const int64_t *t,
                          const int64_t *i1, const int64_t *dst_offsets, int32_t B, int32_t rebase_mode, const int64_t *base_in,
                          int32_t *events_out, int64_t *base_out, uint32_t *status_out, void *stream);
 
+/* N-ImageNet's event front end and base_augment on the device (n_imagenet/real_cnn_model/data/imagenet.py: load_event :30-57,
+ * reshape_event_no_sample :104-108, slice_event :60-84, base_augment("train") :1140-1187), for the B windows of a batch in one
+ * call: a count launch, one scan workgroup, a write launch.  The call takes no plan and no workspace, neither allocates nor
+ * waits for the device, and reads every size on the device.
+ *
+ * evrep_nimg_prepare: events DEVICE int32 [total,4] rows (x, y, t - base, p as stored), 16-byte aligned -- what
+ *   evrep_windows_gather writes --; offsets DEVICE int64 [B+1], ascending; t_base DEVICE int64 [B], the absolute time of t == 0
+ *   per window (NULL: 0); params DEVICE evrep_nimg_params [B].  Per row of window b, every step the reference's float64
+ *   operation as one IEEE operation:
+ *     time      t_s = (double)(t_base[b] + t) / 1e6                                                       (:51)
+ *     polarity  EVREP_NIMG_P_UINT8: p is first read as load_event reads it, through uint8 (p & 0xFF)        (:36)
+ *               if the minimum of p over the WHOLE window (before any slice) is >= -0.5: every p <= 0.5 becomes -1   (:54-55)
+ *     reshape   x_f = (double)x * sx, y_f = (double)y * sy (sx = new_w / orig_w, sy = new_h / orig_h; 1.0 without)  (:105-106)
+ *     slice     rows [s0, s1) of the window AND the strict t_s > t_lo && t_s < t_hi (-inf / +inf when unused)  (:65,69,82)
+ *     time flip EVREP_AUG_TIME_FLIP: the sliced rows leave in reverse order, t' = T - t_s with T the t_s of the last sliced
+ *               row (taken before the crop), p' = -p                                                       (:1168-1172)
+ *     x flip    EVREP_AUG_X_FLIP: x' = (img_w - 1) - x_f                                                   (:1161)
+ *     shift     EVREP_NIMG_TRAIN only: x'' = x' + x_shift, y'' = y_f + y_shift; the row is kept iff 0 <= x'' < img_w and
+ *               0 <= y'' < img_h.  Without EVREP_NIMG_TRAIN (augment=None) nothing is shifted or cropped.  (:1143-1152)
+ *   Per kept row, in output order: events_out DEVICE int32 [>= total,4] = (trunc x'', trunc y'', 0, sign p'); t_out DEVICE
+ *   double [>= total] = t'; tnorm_out DEVICE double [>= total] = (t' - t'_first) / (t'_last - t'_first) over the window's first
+ *   and last output rows (:198-199); xy_out DEVICE double [>= total,2] or NULL = (x'', y'') untruncated, 16-byte aligned.
+ *   Per window: offsets_out DEVICE int64 [B+1]; status_out DEVICE uint32 [B], EVREP_AUG_* bits:
+ *     EVREP_AUG_EMPTY      no row kept;
+ *     EVREP_AUG_FLAT_TIME  t'_last == t'_first: tnorm is NaN there, as the reference's is;
+ *     EVREP_AUG_BAD_SLICE  s0 < 0, s0 > s1 or s1 > the window's rows: nothing of the window is read, no row is kept.
+ *   scratch DEVICE of evrep_nimg_prepare_scratch_bytes(B, total) bytes, 16-byte aligned, no initialisation needed.
+ *   A window holds fewer than 2^31 rows, the batch fewer than 2^32; B <= EVREP_NIMG_MAX_B. */
+typedef struct evrep_nimg_params {
+    int64_t s0, s1;          /* index slice [s0, s1) of the window's rows */
+    double t_lo, t_hi;       /* strict time slice in seconds */
+    int32_t x_shift, y_shift;
+    uint32_t flags;          /* EVREP_AUG_TIME_FLIP | EVREP_AUG_X_FLIP */
+    uint32_t reserved;
+} evrep_nimg_params;
+#define EVREP_NIMG_TRAIN 1u
+#define EVREP_NIMG_P_UINT8 2u
+#define EVREP_AUG_TIME_FLIP 1u
+#define EVREP_AUG_X_FLIP 2u
+#define EVREP_AUG_EMPTY 1u
+#define EVREP_AUG_FLAT_TIME 2u
+#define EVREP_AUG_BAD_SLICE 4u
+#define EVREP_NIMG_MAX_B (1 << 24)
+size_t evrep_nimg_prepare_scratch_bytes(int32_t B, int64_t total);
+int evrep_nimg_prepare(const int32_t *events, const int64_t *offsets, int32_t B, const int64_t *t_base, const evrep_nimg_params *params,
+                       double sx, double sy, int32_t img_h, int32_t img_w, uint32_t mode, int32_t *events_out, double *t_out,
+                       double *tnorm_out, double *xy_out, int64_t *offsets_out, uint32_t *status_out, void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
