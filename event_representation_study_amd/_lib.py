@@ -89,7 +89,13 @@ SYMBOLS = {
     "evrep_windows_gather": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "evrep_nimg_prepare_scratch_bytes": (ctypes.c_size_t, [_i32, _i64]),
     "evrep_nimg_prepare": (ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _f64, _f64, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "evrep_dist_scratch_bytes": (ctypes.c_size_t, [_i32, _i32, _i32]),
+    "evrep_dist": (ctypes.c_int, [_vp, _i32, _i32, _i32, _f64, _f32, _vp, _vp, _vp]),
+    "evrep_dense_rank_scratch_bytes": (ctypes.c_size_t, [_i32, _i64]),
+    "evrep_dense_rank_f32": (ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
 }
+# evrep_dist / evrep_dense_rank_f32: limits
+DIST_MAX_B, RANK_MAX_SEGMENTS = 1 << 20, 1 << 24
 # evrep_nimg_prepare: mode flags, per-window parameter flags, per-window status bits
 NIMG_TRAIN, NIMG_P_UINT8 = 1, 2
 AUG_TIME_FLIP, AUG_X_FLIP = 1, 2

@@ -31,7 +31,9 @@ the surface memory, time_surface.py:67) and does so here; reshape_then_voxel_gri
 
 reshape_then_acc_adj_sort (DiST, :873-999) = the same builder (per-polarity count, latest and earliest time)
 followed by the reference's own image-space statements (count clipping, 5x5 pooling, temporal discount, dense
-rank of the discounted timestamps) as torch ops on the GPU.
+rank of the discounted timestamps) as torch ops on the GPU, one window per call.  dist_batch is its batched form: the same
+builder for B windows, then ONE evrep_dist call (csrc/evrep_dist.hip: clip, 5x5 discount and dense rank as HIP kernels), bit-equal
+to the reference's image; n_imagenet_front.dist_device is the same on device-made rows.
 
 reshape_then_acc_sort (:513-838) is mirrored for strict=False (the "sorted timestamp image": latest time INDEX per
 pixel, from the same builder with the dense time rank as the per-event value) and for strict=True (followed by the dense
@@ -223,6 +225,51 @@ def reshape_then_acc_adj_sort(event_tensor, augment=None, **kwargs):
         halves.append(srt.reshape(H, W))
     res = torch.stack(halves, dim=2).permute(2, 0, 1).float()
     return res if kwargs.get("keep_on_device", False) else res.cpu()
+
+
+DIST_POL, DIST_STAT = [POS, POS, POS, NEG, NEG, NEG], [COUNT, TMAX, TMIN, COUNT, TMAX, TMIN]
+
+
+def _dist(batch, tnorm, clip_rate=CLIP_COUNT_RATE, alpha=DISC_ALPHA):
+    """The part of dist_batch behind the upload (n_imagenet_front.dist_device enters here with device-made rows): the polstats
+    builder, then evrep_dist (csrc/evrep_dist.hip: clip, 5x5 discount, dense rank) on its output.  Nothing waits for the device."""
+    import ctypes
+    from ._lib import check
+    prim = batch.polstats(tnorm, DIST_POL, DIST_STAT)                                   # (B, H, W, 6) float32
+    B, H, W = batch.B, batch.H, batch.W
+    out = torch.empty((B, 2, H, W), dtype=torch.float32, device=batch.device)
+    if B == 0:
+        return out
+    lib = batch.lib
+    nbytes = int(lib.evrep_dist_scratch_bytes(B, H, W))
+    if nbytes == 0:
+        raise ValueError("evrep_dist does not take %d windows of %dx%d" % (B, H, W))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=batch.device)
+    with torch.cuda.device(batch.device):
+        check(lib.evrep_dist(ctypes.c_void_p(prim.data_ptr()), B, H, W, float(clip_rate), float(alpha), ctypes.c_void_p(out.data_ptr()),
+                             ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+              "evrep_dist")
+    return out
+
+
+def dist_batch(event_tensors, height=IMAGE_H, width=IMAGE_W, device="cuda:0"):
+    """DiST for a batch: a list of (N_b, 4) float64 event tensors -> (B, 2, H, W) float32 device tensor, channel 0 positive,
+    channel 1 negative; window b is bit-equal to the reference's reshape_then_acc_adj_sort(event_tensors[b]) (imagenet.py:873-999).
+    The batched sibling of accumulate_batch: one upload, one polstats launch, one evrep_dist call of three launches.
+
+    Windows the reference cannot rank meaningfully are refused on the host, before anything is uploaded: an empty tensor raises
+    IndexError (event_tensor[0, 2], as accumulate_batch does); a tensor whose first and last timestamp agree raises ValueError
+    naming the sample -- its normalised times are NaN, and the order the reference's sort gives NaNs is not a parity target."""
+    wins = [_as_f64(e) for e in event_tensors]
+    for b, w in enumerate(wins):
+        if len(w) == 0:
+            raise IndexError("empty event tensor (sample %d)" % b)
+        if w[-1, 2] == w[0, 2]:
+            raise ValueError("DiST of a window whose first and last timestamp agree (sample %d): its normalised times are NaN" % b)
+    packed = [_window(w, height, width) for w in wins]
+    batch = EventBatch.from_numpy([r for r, _ in packed], height, width, device=device)
+    tnorm = torch.from_numpy(np.concatenate([t for _, t in packed]) if packed else np.zeros(0)).to(batch.device)
+    return _dist(batch, tnorm)
 
 
 TIME_SCALE = 1000000     # imagenet.py:21

@@ -19,13 +19,14 @@ DEVICE PATH.  ``NImageNetFrontEnd(cfg, mode).prepare(batch)`` runs all of the ab
 ``AugmentedBatch``: the kept rows ``[trunc x, trunc y, 0, sign p]`` as a new ``EventBatch`` on the image frame, the float64
 ``t`` and ``tnorm`` every accumulator forms (:198-199), the untruncated ``xy``, and per-window counts and status words.  One host
 read of B counts and status words sizes the next plan, as ``EventBatch.compacted`` does.  ``accumulate_device(name, aug)`` then
-builds any of the eleven ``n_imagenet_acc.SPECS`` accumulators from it.  The random parameters are drawn on the host by
-``draw_slice`` / ``draw_augment`` from the global ``random`` / ``np.random`` streams in exactly the order B sequential reference
+builds any of the eleven ``n_imagenet_acc.SPECS`` accumulators from it, and ``dist_device(aug)`` builds DiST
+(reshape_then_acc_adj_sort) from it: polstats, then evrep_dist, nothing leaving the device.  The random parameters are drawn on the
+host by ``draw_slice`` / ``draw_augment`` from the global ``random`` / ``np.random`` streams in exactly the order B sequential reference
 calls consume them, so seeding the two generators reproduces the reference's batch.
 
 OUT OF SCOPE.  ``reshape_method`` "sample" and "unique" (``reshape_event_with_sample`` / ``reshape_event_unique`` raise
 NotImplementedError: the first draws a permutation of the whole sample, the second needs a key sort of it and is off by default
-in the reference); device-input forms of DiST, acc_sort and the ``_prep`` wrappers; the ``denoise_*`` options, which the
+in the reference); device-input forms of acc_sort and the ``_prep`` wrappers; the ``denoise_*`` options, which the
 reference reads and never uses.  There is no CPU fallback for the device path: without a HIP device it raises ``EvrepError``.
 """
 import ctypes
@@ -344,3 +345,21 @@ def accumulate_device(name, aug):
     if empty.size:
         raise IndexError("empty event tensor (sample %d)" % int(empty[0]))     # event_tensor[0, 2], imagenet.py:178
     return ni._accumulate(name, aug.batch, aug.tnorm)
+
+
+def dist_device(aug):
+    """DiST (reshape_then_acc_adj_sort, imagenet.py:873-999) from an AugmentedBatch -> (B, 2, H, W) float32 device tensor, what
+    n_imagenet_acc.dist_batch([the host-augmented tensors]) returns, bit for bit: aug.batch.polstats(aug.tnorm, ...) and one
+    evrep_dist call, with nothing leaving the GPU (the status words were read by prepare()).
+
+    Windows the reference cannot rank meaningfully are refused: one flagged AUG_EMPTY raises IndexError, as accumulate_device does;
+    one flagged AUG_FLAT_TIME (its kept rows share one timestamp) raises ValueError naming the sample -- its tnorm is NaN, and the
+    order the reference's sort gives NaNs is not a parity target."""
+    from . import n_imagenet_acc as ni
+    empty = np.flatnonzero(aug.status & _lib.AUG_EMPTY)
+    if empty.size:
+        raise IndexError("empty event tensor (sample %d)" % int(empty[0]))     # event_tensor[0, 2], imagenet.py:908
+    flat = np.flatnonzero(aug.status & _lib.AUG_FLAT_TIME)
+    if flat.size:
+        raise ValueError("DiST of a window whose first and last timestamp agree (sample %d): its normalised times are NaN" % int(flat[0]))
+    return ni._dist(aug.batch, aug.tnorm)

@@ -480,6 +480,41 @@ int evrep_nimg_prepare(const int32_t *events, const int64_t *offsets, int32_t B,
                        double sx, double sy, int32_t img_h, int32_t img_w, uint32_t mode, int32_t *events_out, double *t_out,
                        double *tnorm_out, double *xy_out, int64_t *offsets_out, uint32_t *status_out, void *scratch, void *stream);
 
+/* N-ImageNet's DiST image (n_imagenet/real_cnn_model/data/imagenet.py:873-999, reshape_then_acc_adj_sort) for B windows in one
+ * call of three launches, and the dense rank it ends in.  Neither call takes a plan or a workspace, allocates, waits for the
+ * device or reads a size on the host: both may be captured into a graph.
+ *
+ * evrep_dist: prim DEVICE float [B,H,W,6], what evrep_polstats writes for pol = {POS, POS, POS, NEG, NEG, NEG}, stat = {COUNT,
+ *   TMAX, TMIN, COUNT, TMAX, TMIN}; out DEVICE float [B,2,H,W], channel 0 positive, channel 1 negative.  Per (window, polarity)
+ *   image, every step the reference's float32 statement as one IEEE operation (divisions correctly rounded, no FMA):
+ *     clip     th = #{ j : S_j < H*W*clip_rate }, S_j the running number of pixels over the DISTINCT count values in ascending
+ *              order; the float64 product and S_j are compared in float32, as torch compares an int64 tensor with a Python
+ *              float; count = min(count, th).  Exact for any counts.                                           (:897-906)
+ *     stencil  earliest = 1 where count == 0; s = 5x5 sum of count, zero padding; nb = 25 * (s / 25);
+ *              disc = (max5x5(latest) + max5x5(-earliest)) / nb, -inf padding; where count > 0: latest -= alpha * disc;
+ *              latest < 0 -> 0; nb == 1 -> 0.                                                                    (:926-968)
+ *     rank     out = #{distinct values < latest} / #{distinct values} over the image, +0.0 and -0.0 one value.   (:970-990)
+ *   clip_rate >= 0 (the reference: 0.99), alpha (the reference: 3.0).  scratch DEVICE of evrep_dist_scratch_bytes(B, H, W) bytes,
+ *   16-byte aligned, no initialisation needed.  B <= EVREP_DIST_MAX_B; H, W <= EVREP_MAX_DIM.  A NaN in prim (a window whose
+ *   events share one timestamp) is ranked as its bit pattern orders it, which is not what the reference's sort does.
+ * evrep_dense_rank_f32: S segments of float32 keys, segment s = keys [seg_offsets[s], seg_offsets[s+1]); out[i] =
+ *   #{distinct keys of i's segment < keys[i]} / #{distinct keys of the segment}, one correctly rounded float32 division.
+ *   seg_offsets DEVICE int64 [S+1], ascending from seg_offsets[0] >= 0 (a segment may be empty; one whose offsets descend or
+ *   pass seg_offsets[S] is left alone); keys, out DEVICE float [>= seg_offsets[S]]; n_distinct_out DEVICE int32 [S] or NULL;
+ *   scratch DEVICE of evrep_dense_rank_scratch_bytes(S, total) bytes with total >= seg_offsets[S], 16-byte aligned.  One
+ *   workgroup per segment (a stable radix sort of (key, index) pairs through the scratch), so it is meant for many segments of
+ *   up to a few hundred thousand keys; a segment holds fewer than 2^32 keys.  S <= EVREP_RANK_MAX_SEGMENTS.
+ * The *_scratch_bytes functions return 0 for arguments the calls refuse. */
+#define EVREP_DIST_MAX_B (1 << 20)
+#define EVREP_RANK_MAX_SEGMENTS (1 << 24)
+#define EVREP_RANK_MAX_TOTAL ((int64_t)1 << 40)
+size_t evrep_dist_scratch_bytes(int32_t B, int32_t H, int32_t W);
+int evrep_dist(const float *prim, int32_t B, int32_t H, int32_t W, double clip_rate, float alpha, float *out, void *scratch,
+               void *stream);
+size_t evrep_dense_rank_scratch_bytes(int32_t S, int64_t total);
+int evrep_dense_rank_f32(const float *keys, const int64_t *seg_offsets, int32_t S, float *out, int32_t *n_distinct_out,
+                         void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
