@@ -93,7 +93,16 @@ SYMBOLS = {
     "evrep_dist": (ctypes.c_int, [_vp, _i32, _i32, _i32, _f64, _f32, _vp, _vp, _vp]),
     "evrep_dense_rank_scratch_bytes": (ctypes.c_size_t, [_i32, _i64]),
     "evrep_dense_rank_f32": (ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "evrep_time_index_scratch_bytes": (ctypes.c_size_t, [_i32, _i64]),
+    "evrep_time_index": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "evrep_sort_image_scratch_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32]),
+    "evrep_sort_image": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _I32P, _i32, _vp, _vp, _vp, _vp]),
 }
+# evrep_time_index / evrep_sort_image: modes, per-window status bits (NO_INDEX << polarity class), flags, limits
+TIME_INDEX_RAW, TIME_INDEX_RANK = 0, 1
+SORT_EMPTY, SORT_DECREASING, SORT_NO_INDEX = 1, 2, 4
+SORT_STRICT, SORT_USE_IMAGE = 1, 2
+SORT_MAX_B, SORT_MAX_Q = 1 << 20, 16
 # evrep_dist / evrep_dense_rank_f32: limits
 DIST_MAX_B, RANK_MAX_SEGMENTS = 1 << 20, 1 << 24
 # evrep_nimg_prepare: mode flags, per-window parameter flags, per-window status bits

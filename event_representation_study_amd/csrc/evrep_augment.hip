@@ -70,15 +70,6 @@ __device__ inline bool aug_row(const AugArgs &a, const evrep_nimg_params &p, int
     return sliced && x >= 0.0 && x < a.res_w && y >= 0.0 && y < a.res_h;
 }
 
-// the window of concatenated row i among windows [lo, hi]: the last b with off[b] <= i (empty windows are stepped over)
-__device__ inline int aug_find_window(const int64_t *__restrict__ off, int lo, int hi, int64_t i) {
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 __device__ inline void aug_slice(const int64_t *__restrict__ off, int B, int s, int64_t &lo, int64_t &hi) {
     const int64_t first = off[0], n = off[B] - first;
     const int64_t per = (n + kAugSlices - 1) / kAugSlices;
@@ -97,10 +88,10 @@ __global__ __launch_bounds__(kAugThreads) void k_nimg_pass(AugArgs a, uint32_t *
     int64_t lo, hi;
     aug_slice(a.off, a.B, blockIdx.x, lo, hi);
     uint32_t base = WRITE ? slice_cnt[blockIdx.x] : 0u;
-    int b_lo = lo < hi ? aug_find_window(a.off, 0, a.B - 1, lo) : 0;                                  // uniform
+    int b_lo = lo < hi ? find_window(a.off, 0, a.B - 1, lo) : 0;                                  // uniform
     for (int64_t r0 = lo; r0 < hi; r0 += kAugThreads) {                                             // uniform
         const int64_t r_end = min(r0 + kAugThreads, hi) - 1;
-        const int b_hi = aug_find_window(a.off, b_lo, a.B - 1, r_end);                              // uniform
+        const int b_hi = find_window(a.off, b_lo, a.B - 1, r_end);                              // uniform
         const int64_t i = r0 + tid;
         const bool live = i < hi;
         bool keep = false, sliced = false, bad = true;
@@ -109,7 +100,7 @@ __global__ __launch_bounds__(kAugThreads) void k_nimg_pass(AugArgs a, uint32_t *
         double x = 0.0, y = 0.0, ts = 0.0;
         evrep_nimg_params p = {};
         if (live) {
-            b = aug_find_window(a.off, b_lo, b_hi, i);
+            b = find_window(a.off, b_lo, b_hi, i);
             const int64_t beg = a.off[b];
             r = i - beg;
             p = a.par[b];

@@ -166,6 +166,15 @@ __device__ inline int bits_for(int n) {  // bits needed to represent values in [
     return b;
 }
 
+// the window of concatenated row i among windows [lo, hi]: the last b with off[b] <= i (empty windows are stepped over)
+__device__ inline int find_window(const int64_t *__restrict__ off, int lo, int hi, int64_t i) {
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
 // Exclusive scan of one uint32 per thread across a workgroup of NW waves. tmp: >= NW uint32 of LDS.
 // Returns the exclusive prefix; *total receives the workgroup sum.  Contains __syncthreads().
 template <int NW = kWaves>

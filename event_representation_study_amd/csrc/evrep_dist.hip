@@ -24,27 +24,14 @@
 // Nothing here waits for the device or reads a size on the host.
 #pragma once
 #include "evrep_common.h"
+#include "evrep_ranksort.h"                           // kDistThreads, rank_key, rank_pair_sort: shared with evrep_sort.hip
 
 namespace evrep {
 
-constexpr int kDistThreads = 1024;                    // clip and rank: one workgroup of sixteen waves per segment
-constexpr int kDistWaves = kDistThreads / 64;
 constexpr int kClipBins = 4096;                       // count values one sweep of the clip resolves (four bins per thread)
-constexpr int kRankBits = 8, kRankRadix = 1 << kRankBits, kRankPasses = 32 / kRankBits;
-constexpr int kRankItems = 4;                         // pairs per lane and chunk
-constexpr int kRankWaveSpan = 64 * kRankItems;        // consecutive pairs one wave owns in a chunk
-constexpr int kRankChunk = kDistThreads * kRankItems;
 constexpr int kTileH = 16, kTileW = 64, kHalo = 2;    // the stencil's tile; 256 threads, four pixels each
 constexpr int kStencilThreads = 256;
 static_assert(kClipBins == 4 * kDistThreads, "k_dist_clip gives every thread four bins");
-static_assert(kRankRadix <= kDistThreads && kRankPasses % 2 == 0, "the last pass lands in the second pair of buffers");
-
-// float bits -> unsigned key of the same order; -0.0 is +0.0
-__device__ inline uint32_t rank_key(float f) {
-    uint32_t u = __float_as_uint(f);
-    if (u == 0x80000000u) u = 0u;
-    return u ^ ((u & 0x80000000u) ? 0xFFFFFFFFu : 0x80000000u);
-}
 
 // ------------------------------------------------------------------------------------------------------------- stage (a)
 __global__ __launch_bounds__(kDistThreads) void k_dist_clip(const float *__restrict__ prim, int npx, float limit, uint32_t *__restrict__ th_out) {
@@ -180,14 +167,12 @@ struct RankArgs {
     float *out;
     int32_t *n_distinct;        // S entries or nullptr
 };
-// total = offsets[S] (read on the device) or S * uniform_len
-__host__ __device__ inline size_t rank_array_bytes(int64_t total) { return ((size_t)total * sizeof(uint32_t) + 255) & ~(size_t)255; }
+// total = offsets[S] (read on the device) or S * uniform_len; every array holds rank_array_bytes(total) bytes
 
 __global__ __launch_bounds__(kDistThreads) void k_dense_rank(const RankArgs a) {
-    __shared__ uint32_t hist[kRankRadix];                 // a pass's digit histogram, then the running digit bases
-    __shared__ uint32_t wave_cnt[kDistWaves][kRankRadix];
-    __shared__ uint32_t scan_tmp[kDistWaves];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ RankSortLds lds;
+    uint32_t *const scan_tmp = lds.scan_tmp;
+    const int tid = threadIdx.x;
     const int seg = blockIdx.x;
     int64_t o0, n, total;
     if (a.offsets) {
@@ -209,74 +194,7 @@ __global__ __launch_bounds__(kDistThreads) void k_dense_rank(const RankArgs a) {
     uint32_t *const ka = reinterpret_cast<uint32_t *>(a.scratch) + o0, *const ia = reinterpret_cast<uint32_t *>(a.scratch + ab) + o0;
     uint32_t *const kb = reinterpret_cast<uint32_t *>(a.scratch + 2 * ab) + o0, *const ib = reinterpret_cast<uint32_t *>(a.scratch + 3 * ab) + o0;
 
-    for (int pass = 0; pass < kRankPasses; ++pass) {
-        const int shift = pass * kRankBits;
-        const bool to_b = (pass & 1) != 0;                // a, b, a, b: pass 0 reads the caller's keys, the last pass lands in b
-        const uint32_t *ksrc = to_b ? ka : kb, *isrc = to_b ? ia : ib;
-        uint32_t *kdst = to_b ? kb : ka, *idst = to_b ? ib : ia;
-        if (tid < kRankRadix) hist[tid] = 0;
-        __syncthreads();
-        for (int64_t i0 = 0; i0 < n; i0 += kDistThreads) {
-            const int64_t i = i0 + tid;
-            const bool valid = i < n;
-            const uint32_t k = valid ? (pass == 0 ? rank_key(keys[i]) : ksrc[i]) : 0u;
-            const uint32_t d = (k >> shift) & (uint32_t)(kRankRadix - 1);
-            uint32_t r;
-            bool last;
-            wave_match(d, kRankBits, valid, lane, r, last);
-            if (valid && last) atomicAdd(&hist[d], r + 1u);
-        }
-        __syncthreads();
-        uint32_t tot;
-        const uint32_t hv = tid < kRankRadix ? hist[tid] : 0u;
-        const uint32_t ex = block_exclusive_scan<kDistWaves>(hv, scan_tmp, &tot);
-        if (tid < kRankRadix) hist[tid] = ex;             // (block_exclusive_scan ends in a barrier: every hv is read)
-        __syncthreads();
-        for (int64_t c0 = 0; c0 < n; c0 += kRankChunk) {
-            for (int j = lane; j < kRankRadix; j += 64) wave_cnt[wave][j] = 0;       // this wave's row: nobody else reads it now
-            uint32_t k[kRankItems], ix[kRankItems], off[kRankItems];
-#pragma unroll
-            for (int it = 0; it < kRankItems; ++it) {
-                const int64_t i = c0 + (int64_t)wave * kRankWaveSpan + it * 64 + lane;
-                const bool valid = i < n;
-                k[it] = valid ? (pass == 0 ? rank_key(keys[i]) : ksrc[i]) : 0u;
-                ix[it] = valid ? (pass == 0 ? (uint32_t)i : isrc[i]) : 0u;
-                const uint32_t d = (k[it] >> shift) & (uint32_t)(kRankRadix - 1);
-                uint32_t r;
-                bool last;
-                wave_match(d, kRankBits, valid, lane, r, last);
-                __builtin_amdgcn_wave_barrier();
-                const uint32_t before = valid ? wave_cnt[wave][d] : 0u;
-                off[it] = before + r;
-                __builtin_amdgcn_wave_barrier();
-                if (valid && last) wave_cnt[wave][d] = before + r + 1u;
-                __builtin_amdgcn_wave_barrier();
-            }
-            __syncthreads();
-            if (tid < kRankRadix) {                       // the rows become each wave's first destination per digit
-                uint32_t run = hist[tid];
-#pragma unroll
-                for (int w = 0; w < kDistWaves; ++w) {
-                    const uint32_t t = wave_cnt[w][tid];
-                    wave_cnt[w][tid] = run;
-                    run += t;
-                }
-                hist[tid] = run;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int it = 0; it < kRankItems; ++it) {
-                const int64_t i = c0 + (int64_t)wave * kRankWaveSpan + it * 64 + lane;
-                if (i < n) {
-                    const uint32_t d = (k[it] >> shift) & (uint32_t)(kRankRadix - 1);
-                    const uint32_t dst = wave_cnt[wave][d] + off[it];       // < n: the digit bases partition [0, n)
-                    kdst[dst] = k[it];
-                    idst[dst] = ix[it];
-                }
-            }
-        }
-        __syncthreads();                                  // the pairs are in place for every wave of this workgroup
-    }
+    rank_pair_sort([keys](int64_t i) { return rank_key(keys[i]); }, n, ka, ia, kb, ib, lds);
 
     // sorted pairs are in the second buffers.  Heads, their number, then rank / number at every pair's index.
     const uint32_t *ks = kb, *is = ib;

@@ -38,8 +38,15 @@ to the reference's image; n_imagenet_front.dist_device is the same on device-mad
 reshape_then_acc_sort (:513-838) is mirrored for strict=False (the "sorted timestamp image": latest time INDEX per
 pixel, from the same builder with the dense time rank as the per-event value) and for strict=True (followed by the dense
 rank of the per-pixel maxima; bit-exact on goldens that the generator checks not to depend on which of several tied events
-torch_scatter's arg-max names); the denoise options raise the NameError they raise in the reference
+torch_scatter's arg-max names); the quantisation runs in the reference's precision (float32 when strict, float64 otherwise) with a
+true division -- torch's GPU `tensor / python_int` multiplies by the reciprocal, which is off by one ulp for q = 255; the denoise options raise the NameError they raise in the reference
 (density_filter_event_image is never defined there).
+sort_batch is its batched form for every switch (strict, global_time, use_image, neglect_polarity, quantize_sort): ONE
+evrep_time_index call (csrc/evrep_sort.hip: idx = (int64)(t * 1e6) and its consecutive rank per window, a segmented scan over several
+workgroups per window), the same builder for B windows, then ONE evrep_sort_image call (the masked dense rank of the per-pixel
+maxima with the reference's own normalisation and quantisation), bit-equal to the reference's image; strict=True ranks the
+consecutive rank whatever global_time is, so latest indices one microsecond apart stay apart beyond 2^24 us, where the float32
+index reshape_then_acc_sort ranks has merged them.  n_imagenet_front.sort_device is the same on device-made rows.
 The EST quantisation layer is in est.py.
 The product path needs the HIP library and an MI355X; there is no CPU fallback.
 """
@@ -332,14 +339,140 @@ def reshape_then_acc_sort(event_tensor, augment=None, **kwargs):
         elif not bool((srt > 0.0).any()):      # hot_event_sort.max() on an empty selection (:592-594,744-746)
             raise RuntimeError("max(): Expected reduction dim to be specified for input.numel() == 0")
         if q is not None:
+            # the reference quantises a float32 tensor when strict (:588-591) and the float64 output of scatter_max otherwise
+            # (:596), with a true division; torch's GPU `tensor / python_int` multiplies by the reciprocal, a device tensor divides
+            # (the float32 quotient is taken in float64 and rounded once more: 53 bits make that the correctly rounded float32 one)
+            def quant(s, qs, dt=torch.float32 if strict else torch.float64):
+                return (torch.round(s.to(dt) * qs).double() / torch.tensor(qs, dtype=torch.float64, device=s.device)).float()
             if type(q) == int:
-                srt = torch.round(srt * q) / q
+                srt = quant(srt, q)
             elif type(q) == list:
-                srt = torch.stack([torch.round(srt * qs) / qs for qs in q], dim=2)
+                srt = torch.stack([quant(srt, qs) for qs in q], dim=2)
         parts = ([image.unsqueeze(-1)] if use_image else []) + [srt if srt.dim() == 3 else srt.unsqueeze(-1)]
         chans.append(torch.cat(parts, dim=2))
     res = torch.cat(chans, dim=2).permute(2, 0, 1).float()
     return res if kwargs.get("keep_on_device", False) else res.cpu()
+
+
+SORT_MAX_WINDOW = 1 << 24   # strict=True ranks float32 TMAX of the consecutive time rank: exact below 2^24 events per window
+_SORT_EMPTY_TEXT = "max(): Expected reduction dim to be specified for input.numel() == 0"
+
+
+def _sort_options(neglect_polarity, use_image, quantize_sort, denoise_image, denoise_sort):
+    """The option checks sort_batch and n_imagenet_front.sort_device share -> (polarity classes, quantisation list)."""
+    if use_image and denoise_image:
+        raise NameError("name 'density_filter_event_image' is not defined")   # what the reference raises (:556,679)
+    if denoise_sort:
+        raise NameError("name 'density_filter_event_image' is not defined")   # (:609,777)
+    q = quantize_sort
+    if q is not None and type(q) not in (int, list):
+        raise TypeError("quantize_sort is None, an int or a list of ints, not %s" % type(q).__name__)
+    qs = [] if q is None else ([q] if type(q) == int else list(q))
+    if q is not None and not qs:
+        raise ValueError("quantize_sort is an empty list")
+    if any(type(v) != int or v <= 0 or v >= 1 << 31 for v in qs):
+        raise ValueError("quantize_sort holds positive ints")
+    from ._lib import SORT_MAX_Q
+    if len(qs) > SORT_MAX_Q:
+        raise ValueError("quantize_sort holds at most %d sizes" % SORT_MAX_Q)
+    return ([ANY] if neglect_polarity else [POS, NEG]), qs
+
+
+def sort_status_error(status, strict):
+    """The exception the status words of _sort stand for (None: no window is refused), naming the first such sample."""
+    from ._lib import SORT_DECREASING, SORT_EMPTY, SORT_NO_INDEX
+    status = np.asarray(status)
+    for bit, make in ((SORT_EMPTY, lambda b: RuntimeError("%s (sample %d)" % (_SORT_EMPTY_TEXT, b))),
+                      (SORT_DECREASING, lambda b: ValueError("time indices decrease inside the window (sample %d): the sorted "
+                                                             "timestamp image ranks consecutive indices" % b))):
+        hit = np.flatnonzero(status & bit)
+        if hit.size:
+            return make(int(hit[0]))
+    hit = np.flatnonzero(status & (SORT_NO_INDEX | SORT_NO_INDEX << 1)) if not strict else np.zeros(0, np.int64)
+    if hit.size:      # hot_event_sort.max() on an empty selection (:597-599,755-757,766-768)
+        return RuntimeError("%s (sample %d: a polarity class without a positive time index)" % (_SORT_EMPTY_TEXT, int(hit[0])))
+    return None
+
+
+def _sort(batch, t, global_time, strict, classes, qs, use_image):
+    """The part of sort_batch behind the upload (n_imagenet_front.sort_device enters here with device-made rows): one
+    evrep_time_index, one polstats launch, one evrep_sort_image (csrc/evrep_sort.hip) -> ((B, C, H, W) float32, (B,) uint32 status
+    words, both on the device).  Nothing waits for the device.
+
+    strict=True feeds polstats the consecutive rank whatever global_time is: the dense rank of the per-pixel maxima does not change
+    under a strictly increasing map of the indices, and the rank, unlike a raw microsecond index beyond 2^24, is exact in float32."""
+    import ctypes
+    from . import _lib
+    from ._lib import check
+    from .engine import _ptr, _stream_ptr
+    B, H, W, K = batch.B, batch.H, batch.W, len(classes)
+    if B == 0:
+        raise ValueError("no window")
+    lengths = batch.offsets_host[1:] - batch.offsets_host[:-1]
+    if strict and int(lengths.max()) >= SORT_MAX_WINDOW:
+        raise ValueError("strict=True takes windows below %d events (sample %d holds %d)"
+                         % (SORT_MAX_WINDOW, int(lengths.argmax()), int(lengths.max())))
+    if t.dtype != torch.float64 or t.device != batch.device or t.numel() != batch.total or not t.is_contiguous():
+        raise ValueError("one contiguous float64 time per event on %s" % batch.device)
+    lib, dev = batch.lib, batch.device
+    rows = max(batch.total, 1)
+    tval = torch.empty(rows, dtype=torch.float64, device=dev)
+    status = torch.empty(B, dtype=torch.uint32, device=dev)
+    nsort = max(len(qs), 1)
+    out = torch.empty((B, K * (int(bool(use_image)) + nsort), H, W), dtype=torch.float32, device=dev)
+    n_ti, n_img = int(lib.evrep_time_index_scratch_bytes(B, batch.total)), int(lib.evrep_sort_image_scratch_bytes(B, H, W, K))
+    if n_ti == 0 or n_img == 0:
+        raise ValueError("the sorted timestamp image does not take %d windows of %dx%d with %d events" % (B, H, W, batch.total))
+    scratch = torch.empty(max(n_ti, n_img), dtype=torch.uint8, device=dev)
+    mode = _lib.TIME_INDEX_RANK if (global_time or strict) else _lib.TIME_INDEX_RAW
+    with torch.cuda.device(dev):
+        check(lib.evrep_time_index(_ptr(t) if batch.total else _ptr(tval), _ptr(batch.offsets), B, mode, _ptr(tval), _ptr(status),
+                                   _ptr(scratch), _stream_ptr()), "evrep_time_index")
+    prim = batch.polstats(tval[:batch.total], [c for c in classes for _ in (0, 1)], [FLAG, TMAX] * K)      # (B, H, W, 2K) float32
+    flags = (_lib.SORT_STRICT if strict else 0) | (_lib.SORT_USE_IMAGE if use_image else 0)
+    with torch.cuda.device(dev):
+        check(lib.evrep_sort_image(_ptr(prim), B, H, W, K, flags, _lib.int32_array(qs) if qs else None, len(qs), _ptr(out), _ptr(status),
+                                   _ptr(scratch), _stream_ptr()), "evrep_sort_image")
+    return out, status
+
+
+def sort_batch(event_tensors, global_time, neglect_polarity, use_image, strict, quantize_sort=None, denoise_image=False,
+               denoise_sort=False, height=IMAGE_H, width=IMAGE_W, device="cuda:0"):
+    """The sorted timestamp image for a batch: a list of (N_b, 4) float64 event tensors -> (B, C, H, W) float32 device tensor;
+    window b is bit-equal to the reference's reshape_then_acc_sort(event_tensors[b], **kwargs) (imagenet.py:513-838), channels in
+    its order: with neglect_polarity [image?] + sort channels, otherwise [pos image?, pos sort..., neg image?, neg sort...]; one
+    sort channel, or len(quantize_sort) of them for a list.  The batched sibling of dist_batch: one upload, one evrep_time_index,
+    one polstats launch, one evrep_sort_image.  Unlike the reference (and reshape_then_acc_sort here), the caller's time column is
+    NOT overwritten with the time indices.
+
+    Refused on the host, before anything is uploaded: denoise_image with use_image, or denoise_sort, raise the NameError the
+    reference raises; an empty window, and with strict=False a polarity class without a positive time index, raise RuntimeError
+    with the text of the reference's max() of an empty selection; a window whose microsecond indices decrease raises ValueError
+    naming the sample (the reference's consecutive ranks are dense ranks only where they never do); strict=True refuses windows of
+    2^24 events and more."""
+    classes, qs = _sort_options(neglect_polarity, use_image, quantize_sort, denoise_image, denoise_sort)
+    wins = [_as_f64(e) for e in event_tensors]
+    from . import _lib
+    status = np.zeros(len(wins), np.uint32)
+    for b, w in enumerate(wins):
+        if len(w) == 0:
+            status[b] |= _lib.SORT_EMPTY
+            continue
+        idx = (w[:, 2] * TIME_SCALE).astype(np.int64)
+        if (idx[1:] < idx[:-1]).any():
+            status[b] |= _lib.SORT_DECREASING
+        val = (idx != idx[0]) if global_time else (idx > 0)       # the event's value (rank or index) is positive
+        for k, c in enumerate(classes):
+            sel = np.ones(len(w), bool) if c == ANY else (w[:, 3] > 0 if c == POS else w[:, 3] < 0)
+            if not (val & sel).any():
+                status[b] |= _lib.SORT_NO_INDEX << k
+    err = sort_status_error(status, strict)
+    if err is not None:
+        raise err
+    rows = [_window(w, height, width)[0] for w in wins]
+    batch = EventBatch.from_numpy(rows, height, width, device=device)
+    t = torch.from_numpy(np.ascontiguousarray(np.concatenate([w[:, 2] for w in wins]))).to(batch.device)
+    return _sort(batch, t, global_time, strict, classes, qs, use_image)[0]
 
 
 # ---------------------------------------------------------------------------------------------

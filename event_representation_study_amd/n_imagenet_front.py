@@ -19,15 +19,17 @@ DEVICE PATH.  ``NImageNetFrontEnd(cfg, mode).prepare(batch)`` runs all of the ab
 ``AugmentedBatch``: the kept rows ``[trunc x, trunc y, 0, sign p]`` as a new ``EventBatch`` on the image frame, the float64
 ``t`` and ``tnorm`` every accumulator forms (:198-199), the untruncated ``xy``, and per-window counts and status words.  One host
 read of B counts and status words sizes the next plan, as ``EventBatch.compacted`` does.  ``accumulate_device(name, aug)`` then
-builds any of the eleven ``n_imagenet_acc.SPECS`` accumulators from it, and ``dist_device(aug)`` builds DiST
-(reshape_then_acc_adj_sort) from it: polstats, then evrep_dist, nothing leaving the device.  The random parameters are drawn on the
+builds any of the eleven ``n_imagenet_acc.SPECS`` accumulators from it, ``dist_device(aug)`` builds DiST
+(reshape_then_acc_adj_sort) from it: polstats, then evrep_dist, and ``sort_device(aug, ...)`` the sorted timestamp image
+(reshape_then_acc_sort, every switch): evrep_time_index on ``aug.t``, polstats, evrep_sort_image -- nothing leaving the device.  The random parameters are drawn on the
 host by ``draw_slice`` / ``draw_augment`` from the global ``random`` / ``np.random`` streams in exactly the order B sequential reference
 calls consume them, so seeding the two generators reproduces the reference's batch.
 
 OUT OF SCOPE.  ``reshape_method`` "sample" and "unique" (``reshape_event_with_sample`` / ``reshape_event_unique`` raise
 NotImplementedError: the first draws a permutation of the whole sample, the second needs a key sort of it and is off by default
-in the reference); device-input forms of acc_sort and the ``_prep`` wrappers; the ``denoise_*`` options, which the
-reference reads and never uses.  There is no CPU fallback for the device path: without a HIP device it raises ``EvrepError``.
+in the reference); device-input forms of the ``_prep`` wrappers; ``accumulate_device("acc_sort", aug)`` (acc_sort is no
+``SPECS`` accumulator: ``sort_device`` is its device-input form); the ``denoise_*`` options, which the reference reads and never
+defines.  There is no CPU fallback for the device path: without a HIP device it raises ``EvrepError``.
 """
 import ctypes
 import random
@@ -363,3 +365,28 @@ def dist_device(aug):
     if flat.size:
         raise ValueError("DiST of a window whose first and last timestamp agree (sample %d): its normalised times are NaN" % int(flat[0]))
     return ni._dist(aug.batch, aug.tnorm)
+
+
+def sort_device(aug, global_time, neglect_polarity, use_image, strict, quantize_sort=None, denoise_image=False, denoise_sort=False,
+                check=True):
+    """The sorted timestamp image (reshape_then_acc_sort, imagenet.py:513-838) from an AugmentedBatch -> (B, C, H, W) float32 device
+    tensor, what n_imagenet_acc.sort_batch([the host-augmented tensors], ...) returns, bit for bit: evrep_time_index on aug.t,
+    aug.batch.polstats and evrep_sort_image, with no event leaving the GPU.
+
+    Windows flagged AUG_EMPTY are refused from aug.status, before anything is launched (RuntimeError, the text of the reference's
+    max() of an empty selection).  check=True reads the B status words once, at the end, and raises as sort_batch does, naming the
+    sample: ValueError for a window whose time indices decrease, RuntimeError for a strict=False polarity class without a positive
+    index.  check=False waits for nothing and returns (images, status): status a (B,) uint32 device tensor of _lib.SORT_EMPTY,
+    SORT_DECREASING and SORT_NO_INDEX << class bits; the image of a flagged window is not the reference's."""
+    from . import n_imagenet_acc as ni
+    classes, qs = ni._sort_options(neglect_polarity, use_image, quantize_sort, denoise_image, denoise_sort)
+    err = ni.sort_status_error(np.where(aug.status & _lib.AUG_EMPTY, _lib.SORT_EMPTY, 0).astype(np.uint32), strict)
+    if err is not None:
+        raise err
+    images, status = ni._sort(aug.batch, aug.t, global_time, strict, classes, qs, use_image)
+    if not check:
+        return images, status
+    err = ni.sort_status_error(status.cpu().numpy(), strict)
+    if err is not None:
+        raise err
+    return images

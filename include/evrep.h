@@ -515,6 +515,54 @@ size_t evrep_dense_rank_scratch_bytes(int32_t S, int64_t total);
 int evrep_dense_rank_f32(const float *keys, const int64_t *seg_offsets, int32_t S, float *out, int32_t *n_distinct_out,
                          void *scratch, void *stream);
 
+/* N-ImageNet's sorted timestamp image (n_imagenet/real_cnn_model/data/imagenet.py:513-838, reshape_then_acc_sort) for B windows:
+ * the time index per event in front of evrep_polstats, and the image statements behind it.  Neither call takes a plan or a
+ * workspace, allocates, waits for the device or reads a size on the host: both may be captured into a graph.
+ *
+ * evrep_time_index: t DEVICE double [>= offsets[B]], the events' times in seconds, indexed like the batch's events; offsets DEVICE
+ *   int64 [B+1], ascending.  Per event idx = (int64)(t * 1e6): one IEEE float64 multiply and a truncation, as
+ *   (event_tensor[:, 2] * TIME_SCALE).long() does (:522,528).  out DEVICE double [>= offsets[B]] receives
+ *     EVREP_TIME_INDEX_RAW   (double)idx;
+ *     EVREP_TIME_INDEX_RANK  the consecutive dense rank of idx inside its window, torch.unique_consecutive +
+ *                            repeat_interleave(arange) (:523-524): the number of positions j <= i of the window, its first
+ *                            excepted, with idx[j] != idx[j-1].  The count restarts at every window.
+ *   status_out DEVICE uint32 [B] is overwritten with EVREP_SORT_EMPTY (the window has no event) and EVREP_SORT_DECREASING (idx
+ *   falls somewhere inside the window: the consecutive rank is a dense rank only where it never does).  Three launches (count,
+ *   one scan workgroup, write) with several workgroups per window; scratch DEVICE of evrep_time_index_scratch_bytes(B, total)
+ *   bytes, total >= offsets[B] - offsets[0], 16-byte aligned, no initialisation needed.  The batch holds fewer than 2^32 events;
+ *   B <= EVREP_SORT_MAX_B.
+ * evrep_sort_image: prim DEVICE float [B,H,W,2K], what evrep_polstats writes for K = 1: pol {ANY, ANY} or K = 2: pol {POS, POS,
+ *   NEG, NEG}, stat {FLAG, TMAX} per class, with the output of evrep_time_index as its per-event value.  out DEVICE float
+ *   [B,C,H,W] in the reference's channel order: per class [FLAG if EVREP_SORT_USE_IMAGE] + the sort channel, nq > 0: once per
+ *   quantize[c] (HOST int32 [nq], every value > 0, nq <= EVREP_SORT_MAX_Q); C = K * (use_image + max(nq, 1)).  One workgroup per
+ *   (window, class).
+ *     without EVREP_SORT_STRICT  sort = TMAX as it is, in every quantised copy too (the reference's float64 round(v * q) / q of
+ *                 an integer v returns v).  A class without a pixel whose TMAX is > 0 ORs EVREP_SORT_NO_INDEX << class into
+ *                 status[window]: the reference's hot_event_sort.max() raises there (:597-599).
+ *     with EVREP_SORT_STRICT     hot = pixels with FLAG; U = distinct TMAX among them; rank = distinct TMAX below the pixel's own;
+ *                 sort = (float)rank / (float)(U - 1), one correctly rounded division, at hot pixels, 0 elsewhere and everywhere
+ *                 when U == 1 (:571-592); per q: round_half_even(sort * (float)q) / (float)q as separate float32 operations.  A
+ *                 class without events is the reference's one event at pixel (0, 0) (:650-655): FLAG set there, sort zero, no
+ *                 status bit.  TMAX must be exact in float32: pass the RANK form of evrep_time_index, windows below 2^24 events.
+ *   status DEVICE uint32 [B] is OR-ed into (zero it, or pass what evrep_time_index wrote).  scratch DEVICE of
+ *   evrep_sort_image_scratch_bytes(B, H, W, K) bytes, 16-byte aligned, no initialisation needed.
+ * The *_scratch_bytes functions return 0 for arguments the calls refuse. */
+#define EVREP_TIME_INDEX_RAW 0
+#define EVREP_TIME_INDEX_RANK 1
+#define EVREP_SORT_EMPTY 1u
+#define EVREP_SORT_DECREASING 2u
+#define EVREP_SORT_NO_INDEX 4u /* << class: 4 the first (ANY or POS), 8 the second (NEG) */
+#define EVREP_SORT_STRICT 1u
+#define EVREP_SORT_USE_IMAGE 2u
+#define EVREP_SORT_MAX_B (1 << 20)
+#define EVREP_SORT_MAX_Q 16
+size_t evrep_time_index_scratch_bytes(int32_t B, int64_t total);
+int evrep_time_index(const double *t, const int64_t *offsets, int32_t B, int32_t mode, double *out, uint32_t *status_out,
+                     void *scratch, void *stream);
+size_t evrep_sort_image_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t K);
+int evrep_sort_image(const float *prim, int32_t B, int32_t H, int32_t W, int32_t K, uint32_t flags, const int32_t *quantize,
+                     int32_t nq, float *out, uint32_t *status, void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
