@@ -44,6 +44,16 @@ def _leaky(z, slope=NEG_SLOPE):
     return np.where(z > 0, z, slope * z)
 
 
+def bucket_table(ends, lo, hi, nbucket):
+    """The hint table of k_est: [lo, hi) in ``nbucket`` equal buckets, entry g = the first piece whose end
+    (``ends[k]``, ascending; piece k covers u < ends[k]) lies beyond the bucket's left edge, at most the last piece.
+    The kernel starts its forward walk there, so an entry may be too small but never too large."""
+    ends = np.asarray(ends, dtype=np.float64)
+    left = lo + (hi - lo) * np.arange(int(nbucket)) / int(nbucket)
+    bucket = np.searchsorted(ends, left, side="right")          # first piece whose end > left edge
+    return np.minimum(bucket, len(ends) - 1).astype(np.int32)
+
+
 class PiecewiseLinearKernel:
     """f(u) = w3 . leaky(W2 leaky(w1 u + b1) + b2) + b3 on [lo, hi] as sorted breakpoints + per-piece (a, c)."""
 
@@ -76,9 +86,7 @@ class PiecewiseLinearKernel:
         self.a = (a2 * A2) @ w3
         self.c = (a2 * B2) @ w3 + b3
         self.nbucket = int(nbucket)
-        left = lo + (hi - lo) * np.arange(self.nbucket) / self.nbucket
-        self.bucket = (np.searchsorted(self.edges[1:], left, side="right")).astype(np.int32)  # first piece whose end > left edge
-        self.bucket = np.minimum(self.bucket, len(self.a) - 1).astype(np.int32)
+        self.bucket = bucket_table(self.edges[1:], lo, hi, self.nbucket)
         self._dev = {}
 
     def __len__(self):

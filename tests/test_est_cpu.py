@@ -1,14 +1,24 @@
 """CPU: the EST value MLP as an exact piecewise-linear table, and the oracle's restatement of
-QuantizationLayer.forward, against outputs of the reference's own layer (tests/golden/make_golden_est.py)."""
+QuantizationLayer.forward, against outputs of the reference's own layer (tests/golden/make_golden_est.py).
+
+Also the float64 RESTATEMENT of the EST builder (est_restated), the summation bound derived from the kernel's number formats
+(assert_within_summation_bound) and every input the GPU tests of k_est use (tests/test_gpu_est.py imports them from here):
+the restatement is checked against the oracle and the reference's stored output, and every input is checked to make the bound
+selective, all without a GPU."""
 import os
+from collections import namedtuple
 
 import numpy as np
 import pytest
 
+from event_representation_study_amd.synthetic import GENERATORS
+
+GOLDEN_EST = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "est.npz")
+
 
 @pytest.fixture(scope="module")
 def est_golden():
-    return np.load(os.path.join(os.path.dirname(__file__), "golden", "est.npz"))
+    return np.load(GOLDEN_EST)
 
 
 def _weights(g):
@@ -45,3 +55,525 @@ def test_oracle_est_voxel_vs_reference(oracle, est_golden):
     # float32 matmuls in a different order than torch's: compare at the scale of the grid
     assert np.abs(got - want).max() <= 1e-5 * np.abs(want).max()
     assert np.array_equal(got == 0, want == 0) or np.abs(got[(got == 0) != (want == 0)]).max() < 1e-6
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The restatement.  Everything the kernel rounds to float32 BEFORE the value function is rounded the same way here (the
+# normalised time is a float32 input, u = t_n - i/(C-1) is ONE float32 subtraction, learned_repr.py:167); everything after is
+# float64.  The piece is found by the kernel's stated contract (the first piece with u < its end, else the last); the bucket
+# table is a hint of the kernel's and takes no part.
+# ---------------------------------------------------------------------------------------------------------------------
+U32 = 2.0 ** -24        # unit roundoff of float32
+U64X2 = 2.0 ** -52      # two float64 roundings of a * u + c, contracted or not
+Restated = namedtuple("Restated", "sum64 abs64 count mag cell v f")
+
+
+def est_terms(rows, offsets, tn, C, seg, H, W, f=None):
+    """Restated(sum64, abs64, count, mag, cell, v): the three (B, H, W, 2C) images of est_restated, mag = per cell
+    max_i |t_n| (|a u| + |c|) (the float64 multiply-add's error scale), and per record and bin the flat cell index, the
+    float64 value and f(u), each (N, C).  `f`: a float64 callable in place of the table (then mag holds max |t_n f|)."""
+    rows = np.asarray(rows)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    tn = np.asarray(tn)
+    assert tn.dtype == np.float32 and tn.shape == (rows.shape[0],) and offsets[-1] == rows.shape[0]
+    seg = np.asarray(seg, dtype=np.float64).reshape(-1, 3)
+    B, N = len(offsets) - 1, rows.shape[0]
+    b = np.repeat(np.arange(B, dtype=np.int64), np.diff(offsets))
+    x, y, p = rows[:, 0].astype(np.int64), rows[:, 1].astype(np.int64), (rows[:, 3] > 0).astype(np.int64)
+    assert N == 0 or (x.min() >= 0 and x.max() < W and y.min() >= 0 and y.max() < H)
+    shift = np.array([np.float32(i / (C - 1)) for i in range(C)], dtype=np.float32)
+    u = (tn[:, None] - shift[None, :]).astype(np.float32)          # float32 - float32: one rounding
+    assert u.dtype == np.float32
+    u64, t64 = u.astype(np.float64), tn.astype(np.float64)[:, None]
+    with np.errstate(invalid="ignore"):
+        if f is None:
+            k = np.minimum(np.searchsorted(seg[:, 0], u64, side="right"), len(seg) - 1)   # first k with u < seg[k, 0]
+            fv = seg[k, 1] * u64 + seg[k, 2]
+            mag = np.abs(t64) * (np.abs(seg[k, 1] * u64) + np.abs(seg[k, 2]))
+        else:
+            fv = np.asarray(f(u64.reshape(-1)), dtype=np.float64).reshape(N, C)
+            mag = np.abs(t64 * fv)
+        v = t64 * fv
+    cell = (((b * H + y) * W + x) * 2 * C + p * C)[:, None] + np.arange(C, dtype=np.int64)[None, :]
+    size = B * H * W * 2 * C
+    flat = cell.reshape(-1)
+    shape = (B, H, W, 2 * C)
+    sum64 = np.bincount(flat, weights=v.reshape(-1), minlength=size).reshape(shape)
+    abs64 = np.bincount(flat, weights=np.abs(v).reshape(-1), minlength=size).reshape(shape)
+    count = np.bincount(flat, minlength=size).reshape(shape)
+    mx = np.zeros(size, dtype=np.float64)
+    np.maximum.at(mx, flat, np.nan_to_num(mag.reshape(-1), nan=0.0))
+    return Restated(sum64, abs64, count, mx.reshape(shape), cell, v, fv)
+
+
+def est_restated(rows, offsets, tn, C, seg, H, W, f=None):
+    """rows (N, 4) [x, y, t, p], offsets (B + 1,), tn (N,) float32, seg (nseg, 3) float64 {end, a, c} ->
+    sum64 (B, H, W, 2C) float64 = sum of t_n * (a_k u + c_k) per cell (b, y, x, p * C + i), abs64 = the same sum of
+    magnitudes, count = records per cell."""
+    r = est_terms(rows, offsets, tn, C, seg, H, W, f)
+    return r.sum64, r.abs64, r.count
+
+
+def gamma32(k):
+    k = np.asarray(k, dtype=np.float64)
+    return k * U32 / (1.0 - k * U32)
+
+
+def summation_bound(abs64, count, mag):
+    """The kernel forms v_i = fl32(t_n * fl32(f)) and adds a cell's n values one after the other in float32: n + 1 roundings
+    on the longest chain, |got - sum| <= gamma(n + 1) * sum |v_i|.  f itself is a float64 multiply-add, contracted or not:
+    at most 2^-52 (|a u| + |c|) each.  Nothing here is measured on the kernel."""
+    n = count.astype(np.float64)
+    return gamma32(n + 1.0) * abs64 + n * U64X2 * mag
+
+
+def assert_within_summation_bound(got, r, what=""):
+    """got (B, H, W, 2C) float32 against Restated r: exactly 0 where no record fell, NaN exactly where the restatement is NaN,
+    within the derived bound elsewhere.  Returns the largest |got - sum64| / bound (a record, never a threshold)."""
+    got = np.asarray(got)
+    assert got.dtype == np.float32 and got.shape == r.sum64.shape, (what, got.dtype, got.shape, r.sum64.shape)
+    empty = r.count == 0
+    assert np.array_equal(got[empty].view(np.uint32), np.zeros(int(empty.sum()), dtype=np.uint32)), \
+        "%s: %d cells without a record are not +0.0" % (what, int((got[empty].view(np.uint32) != 0).sum()))
+    nan = np.isnan(r.sum64)
+    assert np.array_equal(np.isnan(got), nan), "%s: NaN at %d cells, the restatement has %d" % (what, int(np.isnan(got).sum()), int(nan.sum()))
+    live = ~empty & ~nan
+    err = np.abs(got.astype(np.float64) - r.sum64)[live]
+    bound = summation_bound(r.abs64, r.count, r.mag)[live]
+    bad = err > bound
+    if bad.any():
+        i = int(np.argmax(err - bound))
+        raise AssertionError("%s: %d of %d cells beyond the summation bound, worst err %.3e > bound %.3e (n = %d)"
+                             % (what, int(bad.sum()), bad.size, err[i], bound[i], int(r.count[live][i])))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ratio = np.where(bound > 0, err / bound, 0.0)
+    return float(ratio.max()) if ratio.size else 0.0
+
+
+def selective_share(r):
+    """Share of the (record, bin) values whose magnitude exceeds the bound of their own cell: dropping or doubling such a record
+    moves the cell out of the bound.  Values of NaN cells are left out (there the NaN pattern is the check)."""
+    bound = summation_bound(r.abs64, r.count, r.mag).reshape(-1)
+    cell, v = r.cell.reshape(-1), np.abs(r.v.reshape(-1))
+    ok = ~np.isnan(bound[cell])
+    if not ok.any():
+        return 1.0
+    return float((v[ok] > bound[cell][ok]).mean())
+
+
+def sequential_sum32(cell, v32, size):
+    """float32 sum per cell in ARRAY order, np.cumsum(dtype=float32) per cell: what put_(accumulate=True) does on the CPU."""
+    out = np.zeros(size, dtype=np.float32)
+    cell, v32 = np.asarray(cell).reshape(-1), np.asarray(v32, dtype=np.float32).reshape(-1)
+    order = np.argsort(cell, kind="stable")
+    cs, vs = cell[order], v32[order]
+    starts = np.flatnonzero(np.r_[True, cs[1:] != cs[:-1]]) if cs.size else np.zeros(0, dtype=np.int64)
+    ends = np.r_[starts[1:], cs.size]
+    for s, e in zip(starts, ends):
+        out[cs[s]] = vs[s] if e - s == 1 else np.cumsum(vs[s:e], dtype=np.float32)[-1]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Tables
+# ---------------------------------------------------------------------------------------------------------------------
+Table = namedtuple("Table", "seg bucket lo hi")
+
+
+def table_from_ends(ends, a, c, lo, hi, nbucket):
+    """{end, a, c} rows + the bucket hints, built the way PiecewiseLinearKernel builds them."""
+    from event_representation_study_amd.est import bucket_table
+    seg = np.ascontiguousarray(np.stack([np.asarray(ends, dtype=np.float64), np.asarray(a, dtype=np.float64),
+                                         np.asarray(c, dtype=np.float64)], axis=1))
+    return Table(seg, bucket_table(seg[:, 0], lo, hi, nbucket), float(lo), float(hi))
+
+
+def trained_table():
+    """The value MLP of tests/golden/est.npz through PiecewiseLinearKernel: what est.QuantizationLayer hands the kernel."""
+    from event_representation_study_amd.est import PiecewiseLinearKernel
+    k = PiecewiseLinearKernel(_weights(np.load(GOLDEN_EST)))
+    seg = np.ascontiguousarray(np.stack([k.edges[1:], k.a, k.c], axis=1))
+    return Table(seg, k.bucket, k.lo, k.hi)
+
+
+def handmade_table(pieces=40, lo=-1.1, hi=1.3, nbucket=37, seed=7):
+    """A continuous f with `pieces` unequal pieces on a non-dyadic [lo, hi] and 37 buckets (no bucket edge is a binary fraction):
+    1.6 + sin(3x) + noise at the knots, >= 0.3 everywhere, so no value is small against its neighbours for f's sake."""
+    rng = np.random.default_rng(seed)
+    knots = np.concatenate([[lo], np.sort(rng.uniform(lo, hi, pieces - 1)), [hi]])
+    yk = 1.6 + np.sin(3.0 * knots) + rng.uniform(-0.3, 0.3, pieces + 1)
+    a = np.diff(yk) / np.diff(knots)
+    return table_from_ends(knots[1:], a, yk[:-1] - a * knots[:-1], lo, hi, nbucket)
+
+
+def unit_table():
+    """f = 1: one piece, one bucket.  Then v = t_n exactly."""
+    return table_from_ends([1.0], [0.0], [1.0], -1.0, 1.0, 1)
+
+
+TABLES = {"trained": trained_table, "handmade": handmade_table}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Inputs of the bound tests (section "shapes"): name -> (rows, offsets, tn, C, H, W, table name)
+# ---------------------------------------------------------------------------------------------------------------------
+Case = namedtuple("Case", "rows offsets tn C H W table")
+
+
+def _tn_of(wins):
+    """float32 t / t.max() per window, as the layer normalises (learned_repr.py:159-160); a window whose times are all 0 (one
+    event) gets t_n = 1, the value the layer gives a single event with a positive time."""
+    out = []
+    for w in wins:
+        t = w[:, 2].astype(np.float32)
+        out.append(t / t.max() if t.size and t.max() > 0 else np.ones_like(t))
+    return np.concatenate(out) if out else np.zeros(0, dtype=np.float32)
+
+
+def _pack(wins, C, H, W, table):
+    offs = np.zeros(len(wins) + 1, dtype=np.int64)
+    np.cumsum([w.shape[0] for w in wins], out=offs[1:])
+    return Case(np.ascontiguousarray(np.concatenate(wins)), offs, _tn_of(wins), C, H, W, table)
+
+
+def hot_window(N, W, H, seed, polarity):
+    """In the style of test_hot_units_under_every_pass_at_gen1: a quarter of the window on ~90 pixels of one row (far beyond
+    every record stage), plus one flickering pixel.  The flicker holds N / 150 records, more than a record stage on one pixel:
+    with 200 values in a cell the bound is gamma(201) * 200 = 0.0024 of the cell's mean magnitude, and the trained f spans
+    more than that between its bins, so a longer flicker would leave its own records below the bound of their cell."""
+    ev = GENERATORS["edges"](N, W, H, seed=seed, polarity=polarity)
+    rng = np.random.default_rng(seed + 20)
+    k = rng.integers(0, N, size=N // 4)
+    ev[k, 0] = rng.integers(100, 190, size=len(k)); ev[k, 1] = 77
+    k = rng.integers(0, N, size=N // 150)
+    ev[k, 0], ev[k, 1] = 17, 200
+    return ev
+
+
+def _uniform(sizes, W, H, seed):
+    return [GENERATORS["uniform"](n, W, H, seed=seed + i, polarity=("pm1", "01")[i % 2]) if n else np.zeros((0, 4), dtype=np.int32)
+            for i, n in enumerate(sizes)]
+
+
+BOUND_CASES = {
+    # frame, windows (ragged chunk edges: 130 = 128 + 2, 65; 304 = 2 * 128 + 48), bins, polarity encodings, table
+    "uniform_1x1_C2": lambda: _pack(_uniform((150,), 1, 1, 1), 2, 1, 1, "handmade"),
+    "uniform_3x130_empty_middle_C3": lambda: _pack(_uniform((5000, 0, 700), 130, 3, 2), 3, 3, 130, "trained"),
+    "uniform_17x65_one_event_C8": lambda: _pack(_uniform((3000, 1, 900), 65, 17, 3), 8, 17, 65, "handmade"),
+    "uniform_17x65_C4": lambda: _pack(_uniform((4097,), 65, 17, 4)[:1], 4, 17, 65, "trained"),
+    "uniform_gen1_B3_C8": lambda: _pack(_uniform((20000, 19999, 20001), 304, 240, 5), 8, 240, 304, "trained"),
+    "uniform_gen1_C2": lambda: _pack([GENERATORS["uniform"](50000, 304, 240, seed=6, polarity="01")], 2, 240, 304, "handmade"),
+    "circle_gen1_C3": lambda: _pack([GENERATORS["circle"](50000, 304, 240, seed=7, polarity="pm1")], 3, 240, 304, "trained"),
+    "circle_gen1_B3_C4": lambda: _pack([GENERATORS["circle"](20000, 304, 240, seed=8 + i, polarity=("01", "pm1")[i % 2])
+                                        for i in range(3)], 4, 240, 304, "handmade"),
+    "edges_gen1_B3_C4": lambda: _pack([GENERATORS["edges"](20000, 304, 240, seed=11 + i, polarity=("pm1", "01")[i % 2])
+                                       for i in range(3)], 4, 240, 304, "trained"),
+    "edges_gen1_C8": lambda: _pack([GENERATORS["edges"](50000, 304, 240, seed=14, polarity="01")], 8, 240, 304, "handmade"),
+    "hot_gen1_C8": lambda: _pack([hot_window(60000, 304, 240, 15, "pm1")], 8, 240, 304, "handmade"),
+    "hot_gen1_B2_C3": lambda: _pack([hot_window(30000, 304, 240, 16 + i, ("01", "pm1")[i]) for i in range(2)], 3, 240, 304, "trained"),
+}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Exact cases: the order of the additions
+# ---------------------------------------------------------------------------------------------------------------------
+def order_case(long_pixel, polarity, seed=0):
+    """f = 1, so v = t_n exactly and the image is the float32 sum of the times in ARRAY order.  Neighbouring pixels hold
+    1.0 followed by many 2^-25 (every addition is absorbed: the sum stays 1.0) and the same times reversed (the small ones
+    add up exactly first); two more hold random magnitudes from 2^-20 to 1 and their reverse, where any other order of the
+    additions rounds differently somewhere.  A few thousand filler events lie between them in the array.  `long_pixel`: records
+    on the first of those pixels (5000: beyond every record stage).  All times t are 0, as est.QuantizationLayer hands them over:
+    nothing but the position in the array orders a pixel's records."""
+    H, W = 17, 65
+    rng = np.random.default_rng(seed)
+    tiny = np.float32(2.0 ** -25)
+    fwd = np.r_[np.float32(1.0), np.full(long_pixel - 1, tiny, dtype=np.float32)]
+    short = np.r_[np.float32(1.0), np.full(95, tiny, dtype=np.float32)]
+    mixed = (rng.random(160) * 2.0 ** -rng.integers(0, 21, size=160)).astype(np.float32)
+    seqs = [((30, 8), fwd), ((31, 8), fwd[::-1]), ((63, 3), short), ((64, 3), short[::-1]),   # 63 | 64: a chunk's last pixel
+            ((0, 16), mixed), ((1, 16), mixed[::-1])]
+    nfill = 4000
+    pix = [np.full(len(s), y * W + x, dtype=np.int64) for (x, y), s in seqs] + [rng.integers(0, H * W, size=nfill)]
+    tns = [s for _, s in seqs] + [rng.random(nfill).astype(np.float32)]
+    owner = np.concatenate([np.full(len(s), i) for i, s in enumerate(tns)])
+    owner = owner[rng.permutation(len(owner))]                 # random interleave that keeps every sequence's own order
+    pos = {i: np.flatnonzero(owner == i) for i in range(len(tns))}
+    n = len(owner)
+    flat, tn = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.float32)
+    for i in range(len(tns)):
+        flat[pos[i]], tn[pos[i]] = pix[i], tns[i]
+    rows = np.zeros((n, 4), dtype=np.int32)
+    rows[:, 0], rows[:, 1] = flat % W, flat // W
+    pol = rng.integers(0, 2, size=n).astype(np.int32)
+    rows[:, 3] = 2 * pol - 1 if polarity == "pm1" else pol
+    return Case(rows, np.array([0, n], dtype=np.int64), tn, 2, H, W, "unit")
+
+
+def order_expected(case):
+    """(1, H, W, 2C) float32: the sequential float32 sum of v = t_n in array order per cell."""
+    r = est_terms(case.rows, case.offsets, case.tn, case.C, unit_table().seg, case.H, case.W)
+    v32 = np.repeat(case.tn[:, None], case.C, axis=1)
+    assert np.array_equal(v32.astype(np.float64), r.v)           # f = 1: the value IS the float32 time
+    return sequential_sum32(r.cell, v32, r.sum64.size).reshape(r.sum64.shape)
+
+
+ORDER_CASES = {"short_pm1": (96, "pm1"), "long_01": (5000, "01")}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Exact cases: piece selection.  Step tables (a = 0, c = k + 1) and times whose products and sums are exact in float32.
+# ---------------------------------------------------------------------------------------------------------------------
+STEP_TIMES = np.array([0.0, 0.5, 1.0] + [m * 2.0 ** -10 for m in (1, 2, 3, 5, 7, 11, 13, 16, 1023, 513, 511)], dtype=np.float32)
+STEP_NBUCKET = (1, 3, 1000, 4096)
+STEP_NSEG = (1, 2, 300)
+STEP_RANGES = ((-1.0, 1.0), (-1.1, 1.3))
+
+
+def step_case(C, seed=0):
+    """17x65, two windows (pm1 and 01), ~2 records per cell: every time of STEP_TIMES in every bin."""
+    H, W, rng = 17, 65, np.random.default_rng(100 + seed)
+    wins = _uniform((2400, 1800), W, H, 50 + seed)
+    c = _pack(wins, C, H, W, "step")
+    tn = STEP_TIMES[rng.integers(0, len(STEP_TIMES), size=c.rows.shape[0])]
+    tn[:len(STEP_TIMES)] = STEP_TIMES                        # every time occurs, t_n = 0 (u = lo in the last bin) and 1 (u = hi in bin 0) included
+    return c._replace(tn=tn)
+
+
+def step_u_values(C):
+    """the float32 u = t_n - i/(C-1) that occur, ascending, as float64"""
+    shift = np.array([np.float32(i / (C - 1)) for i in range(C)], dtype=np.float32)
+    return np.unique((STEP_TIMES[:, None] - shift[None, :]).astype(np.float32)).astype(np.float64)
+
+
+def step_table(C, nseg, nbucket, lo, hi, kind="mixed", seed=0):
+    """nseg pieces with f = k + 1 on piece k.  Breakpoints (kind): 'at' = float32 u values that occur (u == breakpoint belongs to
+    the NEXT piece), 'above' / 'below' = one float32 ulp beside them, 'edge' = bucket edges as bucket_table forms them, 'mixed'
+    = all four, filled up with random ones."""
+    rng = np.random.default_rng(seed)
+    u = step_u_values(C)
+    u32 = u.astype(np.float32)
+    cand = {"at": u, "above": np.nextafter(u32, np.float32(np.inf)).astype(np.float64),
+            "below": np.nextafter(u32, np.float32(-np.inf)).astype(np.float64),
+            "edge": lo + (hi - lo) * np.arange(1, nbucket) / nbucket}
+    need = nseg - 1
+    inside = {k: np.unique(v[(v > lo) & (v < hi)]) for k, v in cand.items()}
+    if kind == "mixed":      # a quarter of the breakpoints from each kind, as far as it has any
+        pool = np.unique(np.concatenate([rng.choice(v, size=min(len(v), need // 4), replace=False) for v in inside.values()]))
+    else:
+        pool = inside[kind]
+    if len(pool) > need:
+        pool = np.sort(rng.choice(pool, size=need, replace=False))
+    while len(pool) < need:
+        pool = np.unique(np.concatenate([pool, rng.uniform(lo, hi, size=need - len(pool))]))
+    ends = np.concatenate([pool, [hi]])
+    return table_from_ends(ends, np.zeros(nseg), np.arange(nseg) + 1.0, lo, hi, nbucket)
+
+
+def step_tables(C, lo, hi):
+    """every (nseg, nbucket) of the issue for one range: name -> Table.  Two pieces: one breakpoint of each kind."""
+    out = {}
+    for nb in STEP_NBUCKET:
+        out["nseg1 nbucket%d" % nb] = step_table(C, 1, nb, lo, hi)
+        for kind in ("at", "above", "below") + (("edge",) if nb > 1 else ()):
+            for s in range(3):
+                out["nseg2 %s#%d nbucket%d" % (kind, s, nb)] = step_table(C, 2, nb, lo, hi, kind, seed=s)
+        for s in range(2):
+            out["nseg300 mixed#%d nbucket%d" % (s, nb)] = step_table(C, 300, nb, lo, hi, "mixed", seed=s)
+    return out
+
+
+def step_expected(case, table):
+    """exact: every product t_n * c and every partial sum is an integer multiple of 2^-10 below 2^14"""
+    r = est_terms(case.rows, case.offsets, case.tn, case.C, table.seg, case.H, case.W)
+    assert np.all(r.v * 1024 == np.rint(r.v * 1024)) and r.abs64.max() * 1024 < 2 ** 24
+    return r.sum64.astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The host wrapper's inputs: (N, 5) float32 [x, y, t, p, b] rows
+# ---------------------------------------------------------------------------------------------------------------------
+def wrapper_events(kind, H=17, W=65, seed=0):
+    rng = np.random.default_rng(200 + seed)
+
+    def item(n, b, tmax=40000.0):
+        e = np.zeros((n, 5), dtype=np.float32)
+        e[:, 0], e[:, 1] = rng.integers(0, W, size=n), rng.integers(0, H, size=n)
+        e[:, 2] = np.sort(rng.integers(1, int(tmax), size=n)).astype(np.float32) if tmax > 0 else 0.0
+        e[:, 3], e[:, 4] = rng.integers(0, 2, size=n), b
+        return e
+    if kind == "skipped_index":          # batch index 1 never occurs: an empty item in the middle
+        return np.concatenate([item(3000, 0), item(2000, 2)])
+    if kind == "single_event":           # t_n = t / t = 1
+        return np.concatenate([item(2500, 0), item(1, 1), item(1500, 2)])
+    if kind == "zero_times":             # 0 / 0: the reference's values of that item are NaN
+        return np.concatenate([item(2000, 0), item(300, 1, tmax=0.0), item(1200, 2)])
+    raise ValueError(kind)
+
+
+WRAPPER_KINDS = ("skipped_index", "single_event", "zero_times")
+
+
+def wrapper_restated_inputs(ev, H, W):
+    """what est.QuantizationLayer.voxel hands the builder, restated: integer rows, offsets per batch index, float32 t / t.max()"""
+    b = ev[:, 4].astype(np.int64)
+    nb = int(1 + ev[-1, 4])
+    offs = np.zeros(nb + 1, dtype=np.int64)
+    np.cumsum(np.bincount(b, minlength=nb), out=offs[1:])
+    rows = np.zeros((len(ev), 4), dtype=np.int32)
+    rows[:, 0], rows[:, 1], rows[:, 3] = ev[:, 0], ev[:, 1], ev[:, 3]
+    tn = ev[:, 2].astype(np.float32).copy()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for i in range(nb):
+            s, e = offs[i], offs[i + 1]
+            if e > s:
+                tn[s:e] = tn[s:e] / tn[s:e].max()
+    return rows, offs, tn
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# CPU checks
+# ---------------------------------------------------------------------------------------------------------------------
+def test_bucket_table_is_the_kernels_own_statement(est_golden):
+    """bucket_table (factored out of PiecewiseLinearKernel.__init__) returns what the constructor stored before, and the
+    device table is {edges[1:], a, c} + those hints."""
+    from event_representation_study_amd.est import PiecewiseLinearKernel, bucket_table
+    for lo, hi, nb in ((-1.0, 1.0, 4096), (-1.0, 1.0, 1), (-1.0, 1.0, 1000)):
+        k = PiecewiseLinearKernel(_weights(est_golden), lo=lo, hi=hi, nbucket=nb)
+        left = lo + (hi - lo) * np.arange(nb) / nb
+        want = np.minimum(np.searchsorted(k.edges[1:], left, side="right"), len(k.a) - 1).astype(np.int32)
+        assert k.bucket.dtype == np.int32 and np.array_equal(k.bucket, want)
+        assert np.array_equal(bucket_table(k.edges[1:], lo, hi, nb), want)
+        seg, bucket = k.device_table("cpu")
+        assert np.array_equal(seg.numpy(), np.stack([k.edges[1:], k.a, k.c], axis=1)) and np.array_equal(bucket.numpy(), want)
+
+
+def test_restated_vs_oracle_and_reference(oracle, est_golden):
+    """est_restated on the fixture's events with the trained table: against the reference's stored voxel grid and the oracle's
+    float32 restatement, at the fixture's own 1e-5 * scale (the slack of the reference's float32 MLP, not the kernel's)."""
+    g = est_golden
+    C, H, W = (int(v) for v in g["dim"])
+    ev = g["events"]
+    rows, offs, tn = wrapper_restated_inputs(ev, H, W)
+    tab = trained_table()
+    r = est_terms(rows, offs, tn, C, tab.seg, H, W)
+    sum64, abs64, count = est_restated(rows, offs, tn, C, tab.seg, H, W)
+    assert sum64.dtype == np.float64 and sum64.shape == (len(offs) - 1, H, W, 2 * C) == abs64.shape == count.shape
+    assert np.array_equal(sum64, r.sum64) and count.sum() == C * len(ev)
+    mine = np.moveaxis(sum64, -1, 1)                                   # (B, 2C, H, W)
+    want = g["voxel"].astype(np.float64)
+    scale = np.abs(want).max()
+    assert np.abs(mine - want).max() <= 1e-5 * scale
+    assert np.abs(mine - oracle.est_voxel(ev, (C, H, W), _weights(g)).astype(np.float64)).max() <= 1e-5 * scale
+    assert not np.any((want != 0) & (np.moveaxis(count, -1, 1) == 0))  # nothing outside the touched cells
+    # the MLP itself in float64 in place of the table
+    from event_representation_study_amd.est import PiecewiseLinearKernel
+    k = PiecewiseLinearKernel(_weights(g))
+    m = est_terms(rows, offs, tn, C, tab.seg, H, W, f=k.mlp)
+    assert np.abs(m.sum64 - sum64).max() <= 1e-12 * np.abs(sum64).max()
+    assert np.abs(m.v - r.v).max() <= 1e-12 * np.abs(r.v).max()
+
+
+def test_restated_piece_contract():
+    """the first piece with u < its end, the last piece beyond every end; one float32 subtraction forms u"""
+    seg = np.array([[-0.5, 0.0, 1.0], [0.0, 0.0, 2.0], [0.5, 0.0, 3.0]])
+    rows = np.zeros((5, 4), dtype=np.int32); rows[:, 3] = [1, 1, 0, 1, 1]
+    tn = np.array([0.0, 0.5, 0.5, 1.0, 0.25], dtype=np.float32)
+    s, a, n = est_restated(rows, [0, 5], tn, 2, seg, 1, 1)
+    # f per record, bin 0 (u = tn): 3 (u == 0.0 is the end of piece 1: the NEXT piece), 3 (0.5: beyond every end, the last), 3, 3, 3;
+    # bin 1 (u = tn - 1): 1, 2 (-0.5 is the end of piece 0), 2, 3 (0.0 again), 1
+    assert np.array_equal(s[0, 0, 0], [0.5 * 3, 0.5 * 2, 0 * 3 + 0.5 * 3 + 1.0 * 3 + 0.25 * 3, 0 * 1 + 0.5 * 2 + 1.0 * 3 + 0.25 * 1])
+    assert np.array_equal(n[0, 0, 0], [1, 1, 4, 4]) and np.array_equal(a, np.abs(s))
+    third = np.float32(np.float32(0.7) - np.float32(1 / 3))           # C = 4, bin 1
+    r = est_terms(rows[:1], [0, 1], np.array([0.7], dtype=np.float32), 4, np.array([[9.0, 1.0, 0.0]]), 1, 1)
+    assert r.v[0, 1] == np.float64(np.float32(0.7)) * np.float64(third)
+
+
+def test_bound_helper_is_tight_and_rejects_one_record():
+    """The helper passes the float32 sequential sum of its own case, fails when one selective record is dropped or doubled, and
+    fails on a non-zero empty cell."""
+    c = BOUND_CASES["uniform_17x65_C4"]()
+    tab = TABLES[c.table]()
+    r = est_terms(c.rows, c.offsets, c.tn, c.C, tab.seg, c.H, c.W)
+    v32 = c.tn[:, None] * r.f.astype(np.float32)                      # fl32(t_n * fl32(f))
+    assert v32.dtype == np.float32
+    good = sequential_sum32(r.cell, v32, r.sum64.size).reshape(r.sum64.shape)
+    assert 0.0 <= assert_within_summation_bound(good, r, "sequential float32") <= 1.0
+    bound = summation_bound(r.abs64, r.count, r.mag).reshape(-1)
+    sel = np.flatnonzero(np.abs(r.v).reshape(-1) > bound[r.cell.reshape(-1)])
+    for j in sel[[0, len(sel) // 2, -1]]:
+        for sign in (-1.0, 1.0):                                       # dropped, doubled
+            bad = good.copy().reshape(-1)
+            bad[r.cell.reshape(-1)[j]] += np.float32(sign * r.v.reshape(-1)[j])
+            with pytest.raises(AssertionError):
+                assert_within_summation_bound(bad.reshape(good.shape), r, "one record")
+    bad = good.copy()
+    bad[r.count == 0] = 1e-30
+    with pytest.raises(AssertionError):
+        assert_within_summation_bound(bad, r, "empty cells")
+
+
+@pytest.mark.parametrize("name", list(BOUND_CASES))
+def test_bound_is_selective_on_every_gpu_input(name):
+    """>= 99 % of the (record, bin) values exceed the bound of their own cell, by the restatement alone."""
+    c = BOUND_CASES[name]()
+    tab = TABLES[c.table]()
+    r = est_terms(c.rows, c.offsets, c.tn, c.C, tab.seg, c.H, c.W)
+    share = selective_share(r)
+    print("%s: N = %d, largest cell %d records, selective share %.5f" % (name, len(c.rows), int(r.count.max()), share))
+    assert r.count.sum() == c.C * len(c.rows) and share >= 0.99, share
+    u = c.tn[:, None].astype(np.float64) - np.arange(c.C) / (c.C - 1)
+    assert u.min() >= tab.lo - 1e-6 and u.max() <= tab.hi + 1e-6      # the whole of [-1, 1] is inside the table's range
+
+
+@pytest.mark.parametrize("kind", WRAPPER_KINDS)
+def test_wrapper_inputs_are_selective_and_match_the_oracle(oracle, kind):
+    """the host wrapper's inputs: est_restated agrees with oracle.est_voxel at the fixture's 1e-5 * scale, NaN at the oracle's NaN
+    cells and nowhere else, and the bound is selective"""
+    H, W, C = 17, 65, 5
+    ev = wrapper_events(kind, H, W)
+    rows, offs, tn = wrapper_restated_inputs(ev, H, W)
+    assert len(offs) == 4 and (kind != "skipped_index" or offs[1] == offs[2])
+    tab = trained_table()
+    r = est_terms(rows, offs, tn, C, tab.seg, H, W)
+    with np.errstate(all="ignore"):
+        want = np.moveaxis(oracle.est_voxel(ev, (C, H, W), _weights(np.load(GOLDEN_EST))), 1, -1).astype(np.float64)
+    nan = np.isnan(want)
+    assert np.array_equal(nan, np.isnan(r.sum64)) and nan.any() == (kind == "zero_times")
+    scale = np.abs(want[~nan]).max()
+    assert np.abs(r.sum64 - want)[~nan].max() <= 1e-5 * scale
+    assert selective_share(r) >= 0.99
+
+
+@pytest.mark.parametrize("name", list(ORDER_CASES))
+def test_order_cases_depend_on_the_order(name):
+    """the expected image differs from the float64 sum rounded once and from the reversed order at the planted pixels: a kernel
+    that adds in another order cannot be bit-equal"""
+    c = order_case(*ORDER_CASES[name])
+    want = order_expected(c)
+    r = est_terms(c.rows, c.offsets, c.tn, c.C, unit_table().seg, c.H, c.W)
+    assert (want != r.sum64.astype(np.float32)).sum() >= 4
+    rev = sequential_sum32(r.cell[::-1], np.repeat(c.tn[:, None], c.C, axis=1)[::-1], want.size).reshape(want.shape)
+    assert (want != rev).sum() >= 8
+    assert r.count.max() >= (ORDER_CASES[name][0] // 2 - 200)        # the long pixel's two polarity cells
+
+
+@pytest.mark.parametrize("C", [3, 8])
+@pytest.mark.parametrize("lohi", STEP_RANGES)
+def test_step_cases_are_exact_and_hit_their_breakpoints(C, lohi):
+    lo, hi = lohi
+    c = step_case(C)
+    u = step_u_values(C)
+    assert u.min() == -1.0 and u.max() == 1.0                         # u = lo and u = hi of the (-1, 1) range occur
+    tabs = step_tables(C, lo, hi)
+    assert {t.seg.shape[0] for t in tabs.values()} == set(STEP_NSEG) and {len(t.bucket) for t in tabs.values()} == set(STEP_NBUCKET)
+    hit = 0
+    for name, t in tabs.items():
+        step_expected(c, t)                                           # asserts exactness
+        assert np.all(np.diff(t.seg[:, 0]) > 0) and t.seg[-1, 0] == hi
+        hit += int(np.isin(t.seg[:-1, 0], u).sum())
+        if "nseg2 at" in name:
+            assert t.seg[0, 0] in u
+        if "nseg2 edge" in name:
+            nb = len(t.bucket)
+            assert t.seg[0, 0] in lo + (hi - lo) * np.arange(1, nb) / nb
+    assert hit >= 20

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import assert_bit_equal
+from test_est_cpu import assert_within_summation_bound, est_terms, selective_share
 
 from event_representation_study_amd import _lib
 from event_representation_study_amd.synthetic import GENERATORS
@@ -72,8 +73,8 @@ def test_clustered_1mpx_every_builder_every_pass(oracle, dist, shape):
             "acc_all": oracle.nimagenet_acc("acc_all", _ni_rows(ev), H, W),
             "acc_time_pol": oracle.nimagenet_acc("acc_time_pol", _ni_rows(ev), H, W),
         })
-    # the EST layer has no oracle entry point on raw windows: the passes are checked against each other (the classic pass
-    # walks an ordered stream; tests/test_gpu_reference_api.py pins the kernel to the reference's layer)
+    # the EST layer: the first pass against the float64 restatement under the derived summation bound (tests/test_est_cpu.py),
+    # the other passes bit for bit against the first
     seg = torch.tensor([[-0.25, 0.5, 0.1], [0.3, -1.5, 0.6], [1e9, 0.25, -0.2]], dtype=torch.float64, device="cuda:0")
     bucket = torch.zeros(16, dtype=torch.int32, device="cuda:0")
     est_ref = None
@@ -90,6 +91,9 @@ def test_clustered_1mpx_every_builder_every_pass(oracle, dist, shape):
         est = eb.est_voxel(tn.to(torch.float32), 3, seg, bucket, -1.0, 1.0).cpu().numpy()
         if est_ref is None:
             est_ref = est
+            r = est_terms(np.concatenate(wins), eb.offsets_host, tn.to(torch.float32).cpu().numpy(), 3, seg.cpu().numpy(), H, W)
+            assert selective_share(r) >= 0.99
+            assert_within_summation_bound(est, r, "est " + tag)
         else:
             assert_bit_equal(est, est_ref, "est " + tag)
         eb_ni = _batch(eng, ni_wins, H, W, flags)

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from event_representation_study_amd.synthetic import make_events
+from test_est_cpu import assert_within_summation_bound, est_terms, selective_share
 
 pytestmark = pytest.mark.gpu
 
@@ -34,7 +35,7 @@ def _batches(eng, wins, H, W, monkeypatch, force=True):
     return ks, cl
 
 
-def _builders(eb, rng_seed=0):
+def _builders(eb, rng_seed=0, wins=None):
     g = torch.Generator(device="cpu").manual_seed(rng_seed)
     tn = torch.rand(eb.total, dtype=torch.float64, generator=g).to("cuda:0")
     out = {
@@ -68,8 +69,13 @@ def _builders(eb, rng_seed=0):
     seg = torch.tensor([[-0.25, 0.5, 0.1], [0.3, -1.5, 0.6], [1e9, 0.25, -0.2]], dtype=torch.float64, device="cuda:0")
     bucket = torch.zeros(16, dtype=torch.int32, device="cuda:0")
     out["est"] = eb.est_voxel(tn.to(torch.float32), 3, seg, bucket, -1.0, 1.0)
+    est_inputs = (tn.to(torch.float32).cpu().numpy(), seg.cpu().numpy())
     out = {k: v.cpu().numpy() for k, v in out.items()}
     out["tore_bbox"] = [t.cpu().numpy() for t in eb.tore(6, frame_mode=0)]
+    if wins is not None:     # the EST layer against the float64 restatement under the derived summation bound (tests/test_est_cpu.py)
+        r = est_terms(np.concatenate(wins), eb.offsets_host, est_inputs[0], 3, est_inputs[1], eb.H, eb.W)
+        assert selective_share(r) >= 0.99
+        assert_within_summation_bound(out["est"], r, "est vs restatement")
     return out
 
 
@@ -102,7 +108,7 @@ def test_every_builder_matches_the_classic_pass(geom, monkeypatch):
     wins = [make_events(n, W, H, seed=11 * i + n % 97, polarity="pm1" if i % 2 == 0 else "01", dup_last=(3 if n > 10 else 0))
             for i, n in enumerate(sizes)]
     ks, cl = _batches(eng, wins, H, W, monkeypatch)
-    _same(_builders(ks), _builders(cl), "%dx%d" % (W, H))
+    _same(_builders(ks, wins=wins), _builders(cl), "%dx%d" % (W, H))
     np.testing.assert_array_equal(ks.status(), cl.status())
     np.testing.assert_array_equal(ks.bbox(), cl.bbox())
 
