@@ -27,6 +27,7 @@
 // sequential region of the output instead of interleaving 12 KiB tiles with the other seven
 // (6.9 vs 6.2 TB/s of raw HBM writes for 12 KiB one-wave tiles, tools/microbench/store_patterns5.hip).
 #include "evrep_common.h"
+#include "evrep_est_table.h"
 
 namespace evrep {
 
@@ -5094,23 +5095,14 @@ __global__ __launch_bounds__(kWave, 6) void k_polstats_stream(BinView bv, const 
 // --------------------------------------------------------------------------------------------
 // F4: EST quantisation layer, forward (ev-YOLOv6/yolov6/models/learned_repr.py:143-179)
 // --------------------------------------------------------------------------------------------
-constexpr int kEstMaxBins = EVREP_MAX_CHANNELS / 2;
-
-struct EstParams {
-    int32_t C, nseg, nbucket, pad;
-    double lo, inv_width;          // bucket = (u - lo) * inv_width
-    float shift[kEstMaxBins];      // float32(i / (C - 1)), as `t - i_bin / (C - 1)` rounds it (:167)
-};
+// EstParams and the piece search (est_piece) live in evrep_est_table.h: the backward (evrep_est_bwd.hip) walks the same way.
 
 // f(u) of the value MLP through its exact piecewise-linear form: segment k covers u < seg[3k] (ascending),
 // f = seg[3k+1] * u + seg[3k+2].
 __device__ inline float est_value(float u, const double *__restrict__ seg, const uint32_t *__restrict__ bucket,
                                   const EstParams &P) {
     const double ud = (double)u;
-    int g = (int)((ud - P.lo) * P.inv_width);
-    g = g < 0 ? 0 : (g >= P.nbucket ? P.nbucket - 1 : g);
-    int k = (int)bucket[g];
-    while (k + 1 < P.nseg && ud >= seg[3 * k]) ++k;
+    const int k = est_piece(ud, seg, bucket, P);
     return (float)(seg[3 * k + 1] * ud + seg[3 * k + 2]);
 }
 

@@ -367,6 +367,36 @@ class EventBatch:
                                            self._sp()), "evrep_est_voxel")
         return out
 
+    def est_voxel_backward(self, tnorm, C, segments, buckets, lo, hi, grad_out):
+        """The gradient of a loss with respect to the (a, c) columns of the table ``est_voxel`` was called with, from
+        ``grad_out`` = dL/d est_voxel (B, H, W, 2C) float32 contiguous -> (nseg, 2) float64 {dL/da, dL/dc}.  A keyed
+        float64 reduction over the events in array order (no binning pass); bit-reproducible between calls."""
+        if tnorm.dtype != torch.float32 or tnorm.device != self.device or tnorm.numel() != self.total \
+                or not tnorm.is_contiguous():
+            raise ValueError("tnorm must be a contiguous float32 tensor with one entry per event on %s" % self.device)
+        if segments.dtype != torch.float64 or segments.dim() != 2 or segments.shape[1] != 3 or buckets.dtype != torch.int32 \
+                or not segments.is_contiguous() or not buckets.is_contiguous():
+            raise ValueError("segments must be contiguous float64 (nseg, 3), buckets contiguous int32")
+        nseg = int(segments.shape[0])
+        if not 1 <= nseg <= _lib.EST_BWD_MAX_SEG:
+            raise ValueError("the table has %d pieces; the backward holds at most EVREP_EST_BWD_MAX_SEG = %d"
+                             % (nseg, _lib.EST_BWD_MAX_SEG))
+        shape = (self.B, self.H, self.W, 2 * int(C))
+        if tuple(grad_out.shape) != shape or grad_out.dtype != torch.float32 or grad_out.device != self.device \
+                or not grad_out.is_contiguous():
+            raise ValueError("grad_out must be a contiguous float32 tensor of shape %r on %s" % (shape, self.device))
+        grad = torch.empty((nseg, 2), dtype=torch.float64, device=self.device)
+        if self.total == 0:
+            return grad.zero_()
+        scratch = torch.empty(int(self.lib.evrep_est_backward_scratch_bytes(self.total, nseg)), dtype=torch.uint8,
+                              device=self.device)
+        with self._dev():
+            check(self.lib.evrep_est_voxel_backward(_ptr(self.events), _ptr(self.offsets), self.B, self.H, self.W, _ptr(tnorm),
+                                                    int(C), _ptr(segments), nseg, _ptr(buckets), int(buckets.numel()),
+                                                    float(lo), float(hi), _ptr(grad_out), _ptr(grad), _ptr(scratch),
+                                                    self._sp()), "evrep_est_voxel_backward")
+        return grad
+
     # ------------------------------------------------------------------ event filters (ev-licious tools/filters.py)
     # Each filter returns (keep, state): keep = (total,) uint8 device tensor, one byte per event in array order; state = the
     # reference's per-pixel state array as a (B, H, W) device tensor, updated IN PLACE when it was handed in -- hand it to

@@ -252,7 +252,7 @@ int evrep_polstats(const evrep_plan *plan, const int32_t *events, const int64_t 
                    const double *tnorm, int32_t C, const int32_t *pol, const int32_t *stat, double tau, float *out,
                    void *stream);
 
-/* EST quantisation layer, forward only (ev-YOLOv6/yolov6/models/learned_repr.py:143-179): channel p*C + i of a
+/* EST quantisation layer, forward (ev-YOLOv6/yolov6/models/learned_repr.py:143-179): channel p*C + i of a
  * pixel = sum over its events of t_n * f(t_n - i/(C-1)), float32, events of a pixel added in time order (what
  * vox.put_(idx, values, accumulate=True) does on the CPU, :173).  f = the layer's value MLP (:9-43), a scalar
  * function of a scalar with LeakyReLU activations, i.e. EXACTLY piecewise linear: the caller passes it as
@@ -264,6 +264,27 @@ int evrep_polstats(const evrep_plan *plan, const int32_t *events, const int64_t 
 int evrep_est_voxel(const evrep_plan *plan, const int32_t *events, const int64_t *offsets, void *workspace,
                     const float *tnorm, int32_t C, const double *segments, int32_t nseg, const uint32_t *buckets,
                     int32_t nbucket, double lo, double hi, float *out, void *stream);
+
+/* The EST layer's backward with respect to its value MLP.  f(u) = a_k u + c_k on piece k, so for an upstream gradient
+ * grad_out = dL/d out of evrep_est_voxel (DEVICE float (B,H,W,2C), contiguous)
+ *   dL/da_k = sum over (event n, bin i) with piece(u_ni) = k of grad_out[b_n, y_n, x_n, p_n*C + i] * tn_n * u_ni
+ *   dL/dc_k = the same sum of                                    grad_out[b_n, y_n, x_n, p_n*C + i] * tn_n
+ * with u_ni = float32(tn_n - float32(i/(C-1))) and the piece chosen by the same walk as the forward.  Each term is formed
+ * in float64 (G * tn exactly, then one rounding for * u) and summed in float64 in an order fixed by the library's source:
+ * two calls on the same inputs give the same bits, and no floating-point atomic is used.  grad_seg DEVICE double [nseg][2]
+ * {d/da, d/dc}, overwritten (pieces no event falls into hold 0).  The events are read in array order (x, y, p of the int32
+ * rows; tnorm as for evrep_est_voxel; the stream is offsets[0] .. offsets[B]): no plan, no binning pass, no workspace.
+ * Events outside the frame or with p not in {0, 1} contribute nothing; the events themselves get no gradient (t is data).
+ * nseg <= EVREP_EST_BWD_MAX_SEG (the per-workgroup table of 2 * nseg doubles lives in LDS), 2 <= C <= 8.
+ * scratch DEVICE, 16-byte aligned, evrep_est_backward_scratch_bytes(total_events, nseg) bytes with total_events >=
+ * offsets[B] - offsets[0] (0 for arguments out of range); its contents need not be kept or cleared between calls.
+ * Does not allocate, does not wait for the device, reads no size on the host. */
+#define EVREP_EST_BWD_MAX_SEG 8192
+size_t evrep_est_backward_scratch_bytes(int64_t total_events, int32_t nseg);
+int evrep_est_voxel_backward(const int32_t *events, const int64_t *offsets, int32_t B, int32_t H, int32_t W,
+                             const float *tnorm, int32_t C, const double *segments, int32_t nseg,
+                             const uint32_t *buckets, int32_t nbucket, double lo, double hi,
+                             const float *grad_out, double *grad_seg, void *scratch, void *stream);
 
 /* Synchronous read-backs (they synchronise `stream`). status: HOST uint32 [B];
  * bbox: HOST int32 [B,4] = xmin, ymin, xmax, ymax of each window's in-frame events. */
