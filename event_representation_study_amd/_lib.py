@@ -68,6 +68,8 @@ SYMBOLS = {
     "evrep_est_voxel": (ctypes.c_int, [_PP, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _f64, _f64, _vp, _vp]),
     "evrep_est_backward_scratch_bytes": (ctypes.c_size_t, [_i64, _i32]),
     "evrep_est_voxel_backward": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp]),
+    "evrep_est_prepare_scratch_bytes": (ctypes.c_size_t, [_i64, _i32]),
+    "evrep_est_prepare": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "evrep_read_status": (ctypes.c_int, [_PP, _vp, _vp, _vp]),
     "evrep_read_bbox": (ctypes.c_int, [_PP, _vp, _vp, _vp]),
     "evrep_copy_window_meta_async": (ctypes.c_int, [_PP, _vp, _vp, _vp]),
@@ -107,6 +109,9 @@ SORT_STRICT, SORT_USE_IMAGE = 1, 2
 SORT_MAX_B, SORT_MAX_Q = 1 << 20, 16
 # evrep_est_voxel_backward: the largest piecewise-linear table (its 2 * nseg float64 sums live in LDS)
 EST_BWD_MAX_SEG = 8192
+# evrep_est_prepare: status bits, the largest B
+EST_PREP_DESCENDING, EST_PREP_BAD_INDEX, EST_PREP_BAD_POLARITY, EST_PREP_OUT_OF_FRAME = 1, 2, 4, 8
+EST_PREP_MAX_B = 65535
 # evrep_dist / evrep_dense_rank_f32: limits
 DIST_MAX_B, RANK_MAX_SEGMENTS = 1 << 20, 1 << 24
 # evrep_nimg_prepare: mode flags, per-window parameter flags, per-window status bits

@@ -512,6 +512,32 @@ class EventBatch:
         return out
 
 
+def est_prepare(events5, B, H, W):
+    """evrep_est_prepare: the EST layer's ``(n, 5)`` float32 CUDA rows [x, y, t, p, b] (contiguous, n > 0, grouped by b) ->
+    ``(rows, offsets, tnorm, status, packed)`` on the same device: rows (n, 4) int32 {x, y, 0, p}, offsets (B + 1,) int64, tnorm
+    (n,) float32 = t / t.max() per item, status (1,) int32 holding the EVREP_EST_PREP_* bits.  offsets and status are views of
+    ``packed``, (B + 2,) int64 (status is the low half of its last word), so one small copy brings both to the host.
+    Asynchronous on the current stream: nothing is read back here."""
+    _require_gpu()
+    lib = _lib.load()
+    if not isinstance(events5, torch.Tensor) or not events5.is_cuda or events5.dtype != torch.float32 or events5.dim() != 2 \
+            or events5.shape[1] != 5 or events5.shape[0] == 0 or not events5.is_contiguous():
+        raise ValueError("events5 must be a non-empty contiguous (n, 5) float32 CUDA tensor")
+    n, B, dev = int(events5.shape[0]), int(B), events5.device
+    nbytes = int(lib.evrep_est_prepare_scratch_bytes(n, B))
+    if nbytes == 0:
+        raise ValueError("1 <= B <= %d batch items, got %d" % (_lib.EST_PREP_MAX_B, B))
+    rows = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    tnorm = torch.empty(n, dtype=torch.float32, device=dev)
+    packed = torch.empty(B + 2, dtype=torch.int64, device=dev)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    offsets, status = packed[:B + 1], packed[B + 1:].view(torch.int32)[:1]
+    with torch.cuda.device(dev):
+        check(lib.evrep_est_prepare(_ptr(events5), n, B, int(H), int(W), _ptr(rows), _ptr(offsets), _ptr(tnorm), _ptr(status),
+                                    _ptr(scratch), _stream_ptr()), "evrep_est_prepare")
+    return rows, offsets, tnorm, status, packed
+
+
 class BinBuildPipeline:
     """Throughput path for a STREAM of batches: the binning pass of batch k+1 runs on a side HIP stream
     while the builder of batch k runs on the caller's stream (the binning kernels are latency-bound and

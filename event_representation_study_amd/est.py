@@ -24,6 +24,12 @@ Differences, all on the safe side: pixel/voxel indices are exact integers (the r
 float32, :163, which loses bits beyond 2**24 voxels, i.e. for more than ~19 batch items of 6x240x304); p must
 be in {0, 1} (a p of -1 makes the reference clamp negative indices onto voxel 0, :170); the caller's events
 tensor is not modified (the reference normalises ``t`` in place through a view, :156-160).
+
+A CUDA ``(N, 5)`` tensor on the layer's device is prepared on the device (``prepare_events_device``, evrep_est_prepare): the
+int32 rows, the offsets and ``t / t.max()`` are formed there and only (B + 2) words come back, bit-equal to the host route
+that every other input takes.  Two corners of the device route differ, both declared: non-finite coordinates raise
+IndexError (the host route casts them with numpy, which is undefined for NaN), and an item whose maximum is a zero while it
+also holds negative times is unspecified (torch does not define which zero ``max`` returns; the device takes +0).
 """
 import numpy as np
 import torch
@@ -139,20 +145,85 @@ def letterbox_image_batch(image_batch, size, color=114):
     return canvas
 
 
+def _on_device(events, device):
+    """True for a CUDA tensor that lives on ``device`` ("cuda" without an index is the current device)."""
+    if not isinstance(events, torch.Tensor) or not events.is_cuda:
+        return False
+    device = torch.device(device)
+    if device.type != "cuda":
+        return False
+    return events.device.index == (device.index if device.index is not None else torch.cuda.current_device())
+
+
 def prepare_events(events, H, W, device):
     """(N, 5) [x, y, t, p, b] rows -> (EventBatch of the int32 rows, float32 t / t.max() per batch item on the device).
-    The caller's tensor is not modified."""
+    The caller's tensor is not modified.  A CUDA tensor on ``device`` is prepared there (``prepare_events_device``: no
+    event leaves the device); host tensors, numpy arrays and CUDA tensors of another device take the host route
+    (``_prepare_events_host``).  Both give the same bits."""
+    if _on_device(events, device):
+        return prepare_events_device(events, H, W, device)
+    return _prepare_events_host(events, H, W, device)
+
+
+_EMPTY_OR_SHAPE = "events must be a non-empty (N, 5) tensor of [x, y, t, p, b] rows"
+_NOT_GROUPED = "events must be grouped by batch index (ascending), as the collate function delivers them"
+_BAD_POLARITY = "p must be in {0, 1} (learned_repr.py:163 indexes the polarity half with it)"
+
+
+def prepare_events_device(events, H, W, device, batch_size=None):
+    """``prepare_events`` for a CUDA tensor on ``device``, on the device (evrep_est_prepare: offsets from the boundaries of b,
+    the per-item maximum of t by integer atomicMax, one float32 division, the int32 rows).  ``batch_size``: the number of
+    items B; default 1 + events[-1, -1] (learned_repr.py:145, a 4-byte read).  A larger one gives trailing empty items.
+    One read-back of (B + 2) words brings the offsets (``EventBatch`` sizes its plan from them) and the status word; the
+    host route's exceptions are raised from it before any builder runs: NotImplementedError (b descending), ValueError
+    (p not 0 or 1; b negative, non-integral, non-finite or >= B; empty or wrong shape), IndexError (out of the frame).
+
+    Two corners differ from the host route.  Non-finite coordinates are an IndexError here (numpy's float-to-int cast of
+    NaN, which the host route goes through, is undefined).  An item whose maximum is a zero while it also holds negative
+    times divides by +0 here if both zeros occur; torch does not define which zero its max returns, so the sign of that
+    item's infinities is unspecified on either route."""
+    from .engine import est_prepare
+    if not _on_device(events, device):
+        raise ValueError("prepare_events_device takes a CUDA tensor on %s" % (device,))
+    if events.dim() != 2 or events.shape[1] != 5 or events.shape[0] == 0:
+        raise ValueError(_EMPTY_OR_SHAPE)
+    ev = events.detach().to(torch.float32).contiguous()                 # a copy only where needed, never in place
+    if batch_size is None:
+        last = float(ev[-1, 4].item())                                   # B = 1 + events[-1, -1]  (:145)
+        if not (last == last and -1.0 < last < _lib.EST_PREP_MAX_B):
+            raise ValueError("the last batch index must be in 0 .. %d, got %r" % (_lib.EST_PREP_MAX_B - 1, last))
+        nb = int(1 + last)
+    else:
+        nb = int(batch_size)
+    if not 1 <= nb <= _lib.EST_PREP_MAX_B:
+        raise ValueError("1 <= batch_size <= %d, got %d" % (_lib.EST_PREP_MAX_B, nb))
+    rows, _, tn, _, packed = est_prepare(ev, nb, H, W)
+    host = packed.cpu()                                                  # the one read-back: offsets and status
+    status = int(host[nb + 1].item()) & 0xFFFFFFFF
+    if status & _lib.EST_PREP_DESCENDING:
+        raise NotImplementedError(_NOT_GROUPED)
+    if status & _lib.EST_PREP_BAD_POLARITY:
+        raise ValueError(_BAD_POLARITY)
+    if status & _lib.EST_PREP_OUT_OF_FRAME:
+        raise IndexError("event coordinates outside the %dx%d frame" % (W, H))
+    if status & _lib.EST_PREP_BAD_INDEX:
+        raise ValueError("batch indices must be integers in 0 .. %d" % (nb - 1))
+    return EventBatch(rows, host[:nb + 1].clone(), H, W), tn
+
+
+def _prepare_events_host(events, H, W, device):
+    """The host route of ``prepare_events``: the rows are brought to the CPU, prepared with torch and numpy, and uploaded."""
     ev = events.detach().to("cpu", torch.float32) if isinstance(events, torch.Tensor) else \
         torch.as_tensor(np.asarray(events, dtype=np.float32))
     if ev.dim() != 2 or ev.shape[1] != 5 or ev.shape[0] == 0:
-        raise ValueError("events must be a non-empty (N, 5) tensor of [x, y, t, p, b] rows")
+        raise ValueError(_EMPTY_OR_SHAPE)
     b = ev[:, 4].to(torch.int64)
     nb = int(1 + ev[-1, 4].item())                                   # B = 1 + events[-1, -1]  (:145)
     if bool((b[1:] < b[:-1]).any()):
-        raise NotImplementedError("events must be grouped by batch index (ascending), as the collate function delivers them")
+        raise NotImplementedError(_NOT_GROUPED)
     p = ev[:, 3]
     if bool(((p != 0) & (p != 1)).any()):
-        raise ValueError("p must be in {0, 1} (learned_repr.py:163 indexes the polarity half with it)")
+        raise ValueError(_BAD_POLARITY)
     counts = torch.bincount(b, minlength=nb)[:nb]
     offs = np.zeros(nb + 1, dtype=np.int64)
     np.cumsum(counts.numpy(), out=offs[1:])

@@ -286,6 +286,33 @@ int evrep_est_voxel_backward(const int32_t *events, const int64_t *offsets, int3
                              const uint32_t *buckets, int32_t nbucket, double lo, double hi,
                              const float *grad_out, double *grad_seg, void *scratch, void *stream);
 
+/* The EST layer's event preparation (learned_repr.py:145,159-160,164,170) for a stream that is already on the device.
+ * events5 DEVICE float [n][5] rows [x, y, t, p, b], contiguous, 4-byte aligned, grouped by ascending batch index b.  Writes
+ *   rows    DEVICE int32 [n][4] {trunc(x), trunc(y), 0, trunc(p)} (truncated toward zero as .long() does), 16-byte aligned:
+ *           the `events` of evrep_est_voxel / evrep_est_voxel_backward;
+ *   offsets DEVICE int64 [B+1], fully overwritten: offsets[k] = the number of events with b < k, so a batch index that never
+ *           occurs and every index beyond the last event's come out as empty items;
+ *   tnorm   DEVICE float [n]: t / (the maximum of t over the event's item), one correctly rounded float32 division.  A NaN
+ *           time makes the whole item NaN (torch.max propagates it), an all-zero item is 0/0 = NaN as in the reference.  An
+ *           item whose maximum is a zero while it also holds negative times takes +0 if both zeros occur;
+ *   status  DEVICE uint32 [1], overwritten: an OR of the EVREP_EST_PREP_* bits over all events.  An event that sets a bit
+ *           still gets its row and its tnorm, and nothing is written outside offsets[0..B] whatever b holds; with a bit set
+ *           the other outputs are not meaningful.  The cost of the offsets is the sum of the upward jumps of b: B for a
+ *           grouped stream.
+ * The maxima are integer atomicMax operations on an order-preserving image of the float32 times: two calls on the same
+ * input give the same bits, and no floating-point atomic is used.  n > 0, 1 <= B <= 65535 (what evrep_plan_init accepts),
+ * H, W in 1..EVREP_MAX_DIM; anything else, a NULL pointer or a misaligned one is EVREP_EINVAL before any launch.  scratch
+ * DEVICE, 4-byte aligned, evrep_est_prepare_scratch_bytes(n, B) bytes (0 for arguments out of range); it is cleared by the
+ * call itself and need not be kept.  No plan, no workspace.  Does not allocate, does not wait for the device, reads no size
+ * on the host. */
+#define EVREP_EST_PREP_DESCENDING 1u    /* some b[i] < b[i-1]: the stream is not grouped by batch index */
+#define EVREP_EST_PREP_BAD_INDEX 2u     /* some b negative, non-integral, non-finite or >= B */
+#define EVREP_EST_PREP_BAD_POLARITY 4u  /* some p not exactly 0 or 1 */
+#define EVREP_EST_PREP_OUT_OF_FRAME 8u  /* some trunc(x) outside [0, W) or trunc(y) outside [0, H), or x / y not finite */
+size_t evrep_est_prepare_scratch_bytes(int64_t n, int32_t B);
+int evrep_est_prepare(const float *events5, int64_t n, int32_t B, int32_t H, int32_t W, int32_t *rows, int64_t *offsets,
+                      float *tnorm, uint32_t *status, void *scratch, void *stream);
+
 /* Synchronous read-backs (they synchronise `stream`). status: HOST uint32 [B];
  * bbox: HOST int32 [B,4] = xmin, ymin, xmax, ymax of each window's in-frame events. */
 int evrep_read_status(const evrep_plan *plan, const void *workspace, uint32_t *status, void *stream);

@@ -11,6 +11,9 @@ HIP events, median of 50 after warm-up, one JSON line per C:
   (c) backward_kernel_ms         EventBatch.est_voxel_backward alone
   (d) forward_kernel_ms          EventBatch.est_voxel alone (binned stream; the binning pass is bin_ms)
   (e) table_rebuild_ms           PiecewiseLinearKernel + piece_coefficients on the host (wall clock)
+  (b') layer_cuda_fwd_bwd_ms     (b) with the events handed as a CUDA tensor: prepared on the device (est.prepare_events_device)
+  (f) prepare_kernel_ms          evrep_est_prepare alone (engine.est_prepare: two launches and a memset, allocations included)
+  (g) copy_40B_per_event_ms      a device-to-device copy of the same (N, 5) float32 rows: 20 B read + 20 B written per event
 The value MLP is the trained one of tests/golden/est.npz (97 pieces).
 """
 import json
@@ -25,6 +28,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from event_representation_study_amd import est  # noqa: E402
+from event_representation_study_amd.engine import est_prepare  # noqa: E402
 from event_representation_study_amd.synthetic import make_events  # noqa: E402
 
 
@@ -62,6 +66,10 @@ def main():
     ev = np.concatenate([np.concatenate([w.astype(np.float32), np.full((N, 1), i, np.float32)], axis=1) for i, w in enumerate(wins)])
     ev[:, 2] += 1.0                                    # t.max() > 0 in every item
     events = torch.from_numpy(ev)
+    events_dev = events.to("cuda:0")
+    copy_dst = torch.empty_like(events_dev)
+    t_prep = median_ms(lambda: est_prepare(events_dev, B, H, W))
+    t_copy = median_ms(lambda: copy_dst.copy_(events_dev))
     lines = []
     for C in (6, 8):
         layer = est.TrainableQuantizationLayer((C, H, W), est.ValueLayer(state), image_size=None)
@@ -89,6 +97,11 @@ def main():
             (wt_l * layer(events)).sum().backward()
         t_layer = median_ms(layer_step)
 
+        def layer_step_cuda():
+            layer.zero_grad(set_to_none=True)
+            (wt_l * layer(events_dev)).sum().backward()
+        t_layer_cuda = median_ms(layer_step_cuda)
+
         vl = est.ValueLayer(state).to(layer.device)
         rows = batch.events
         x, y, p = (rows[:, j].to(torch.int64) for j in (0, 1, 3))
@@ -101,6 +114,8 @@ def main():
         t_ref = median_ms(ref_step, warm=2)
         lines.append(json.dumps({"dim": [C, H, W], "batch": B, "events_per_item": N, "pieces": len(kern),
                                  "ref_statements_fwd_bwd_ms": round(t_ref, 3), "layer_fwd_bwd_ms": round(t_layer, 3),
+                                 "layer_cuda_fwd_bwd_ms": round(t_layer_cuda, 3), "prepare_kernel_ms": round(t_prep, 4),
+                                 "copy_40B_per_event_ms": round(t_copy, 4),
                                  "backward_kernel_ms": round(t_bwd, 4), "forward_kernel_ms": round(t_fwd, 4),
                                  "bin_ms": round(t_bin, 4), "table_rebuild_ms": round(t_table, 3)}))
         print(lines[-1], flush=True)
