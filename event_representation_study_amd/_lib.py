@@ -128,10 +128,53 @@ FILTER_MAX_RADIUS = 4
 
 # evrep_plan_init_ex flags.  The C library reads no environment variable; the A/B switches of the tests and tools
 # are translated here, when a plan is made.
-PLAN_NO_KEY_PASS, PLAN_THREE_KERNEL, PLAN_FORCE_KEY_SORTED, PLAN_BIG_BLOCKS, PLAN_NO_FUSED_SCATTER = 1, 2, 4, 8, 16
-_ENV_FLAGS = (("EVREP_BIN_CLASSIC", PLAN_NO_KEY_PASS), ("EVREP_BIN_THREE_KERNEL", PLAN_THREE_KERNEL),
-              ("EVREP_BIN_KEY_SORTED", PLAN_FORCE_KEY_SORTED), ("EVREP_KS_BIG_BLOCKS", PLAN_BIG_BLOCKS),
-              ("EVREP_NO_FUSED_SCATTER", PLAN_NO_FUSED_SCATTER), ("EVREP_X_SPAN2", 64), ("EVREP_X_STAGE128", 128), ("EVREP_X_TAIL_MERGE", 256), ("EVREP_X_STAGE64", 512), ("EVREP_X_HANDOVER2", 1024), ("EVREP_X_HANDOVER_DENSE", 2048), ("EVREP_X_NO_SWEEP_MAIN", 4096), ("EVREP_X_NO_MONSTER_HANDOVER", 8192), ("EVREP_X_VOXEL_ORDERED", 16384), ("EVREP_X_TORE_ORDERED", 32768), ("EVREP_X_POLSTATS_ORDERED", 65536), ("EVREP_X_ESTACK_ORDERED", 131072), ("EVREP_X_MDES_ORDERED", 262144), ("EVREP_X_MDES_STREAM", 524288), ("EVREP_X_TS_STREAM", 1048576), ("EVREP_X_TS_ORDERED", 2097152), ("EVREP_X_MDES_NO_COOP", 4194304))
+# (tests/test_capi_cpu.py holds this table to the EVREP_PLAN_* defines of include/evrep.h, name for name)
+PLAN_NO_KEY_PASS = 1
+PLAN_THREE_KERNEL = 2
+PLAN_FORCE_KEY_SORTED = 4
+PLAN_BIG_BLOCKS = 8
+PLAN_NO_FUSED_SCATTER = 16
+PLAN_X_SPAN2 = 64
+PLAN_X_STAGE128 = 128
+PLAN_X_TAIL_MERGE = 256
+PLAN_X_STAGE64 = 512
+PLAN_X_HANDOVER2 = 1024
+PLAN_X_HANDOVER_DENSE = 2048
+PLAN_X_NO_SWEEP_MAIN = 4096
+PLAN_X_NO_MONSTER_HANDOVER = 8192
+PLAN_X_VOXEL_ORDERED = 16384
+PLAN_X_TORE_ORDERED = 32768
+PLAN_X_POLSTATS_ORDERED = 65536
+PLAN_X_ESTACK_ORDERED = 131072
+PLAN_X_MDES_ORDERED = 262144
+PLAN_X_MDES_STREAM = 524288
+PLAN_X_TS_STREAM = 1048576
+PLAN_X_TS_ORDERED = 2097152
+PLAN_X_MDES_NO_COOP = 4194304
+_ENV_FLAGS = (
+    ("EVREP_BIN_CLASSIC", PLAN_NO_KEY_PASS),
+    ("EVREP_BIN_THREE_KERNEL", PLAN_THREE_KERNEL),
+    ("EVREP_BIN_KEY_SORTED", PLAN_FORCE_KEY_SORTED),
+    ("EVREP_KS_BIG_BLOCKS", PLAN_BIG_BLOCKS),
+    ("EVREP_NO_FUSED_SCATTER", PLAN_NO_FUSED_SCATTER),
+    ("EVREP_X_SPAN2", PLAN_X_SPAN2),
+    ("EVREP_X_STAGE128", PLAN_X_STAGE128),
+    ("EVREP_X_TAIL_MERGE", PLAN_X_TAIL_MERGE),
+    ("EVREP_X_STAGE64", PLAN_X_STAGE64),
+    ("EVREP_X_HANDOVER2", PLAN_X_HANDOVER2),
+    ("EVREP_X_HANDOVER_DENSE", PLAN_X_HANDOVER_DENSE),
+    ("EVREP_X_NO_SWEEP_MAIN", PLAN_X_NO_SWEEP_MAIN),
+    ("EVREP_X_NO_MONSTER_HANDOVER", PLAN_X_NO_MONSTER_HANDOVER),
+    ("EVREP_X_VOXEL_ORDERED", PLAN_X_VOXEL_ORDERED),
+    ("EVREP_X_TORE_ORDERED", PLAN_X_TORE_ORDERED),
+    ("EVREP_X_POLSTATS_ORDERED", PLAN_X_POLSTATS_ORDERED),
+    ("EVREP_X_ESTACK_ORDERED", PLAN_X_ESTACK_ORDERED),
+    ("EVREP_X_MDES_ORDERED", PLAN_X_MDES_ORDERED),
+    ("EVREP_X_MDES_STREAM", PLAN_X_MDES_STREAM),
+    ("EVREP_X_TS_STREAM", PLAN_X_TS_STREAM),
+    ("EVREP_X_TS_ORDERED", PLAN_X_TS_ORDERED),
+    ("EVREP_X_MDES_NO_COOP", PLAN_X_MDES_NO_COOP),
+)
 
 
 # (the per-sample wrappers translate the switches on every call -- a test may flip one between two samples: read CPython's own

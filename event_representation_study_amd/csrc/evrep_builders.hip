@@ -64,7 +64,7 @@ __host__ __device__ inline size_t align16(size_t v) { return (v + 15) & ~(size_t
 constexpr int kParts = EVREP_PARTS;
 constexpr int kPartPx = kChunkPx / kParts;  // pixels per part tile
 constexpr int kEvStage = 64;                // records staged in LDS; denser chunks read the rest from HBM/L2
-// The stage size is chosen per launch (unit_cfg() in evrep_capi.hip): 64 records for one-chunk units, 128 for wider ones
+// The stage size is chosen per launch (unit_cfg() in evrep_capi_builders.h): 64 records for one-chunk units, 128 for wider ones
 // (two-chunk float32 units and TORE's shifted frame hold ~65 records on the sparse windows they are chosen for: the
 // key-sorted front end orders them inside LDS).
 struct UnitCfg {
@@ -78,17 +78,21 @@ struct UnitCfg {
     // units per row and two multiply-shift reciprocals over (fastdiv_make; exact for ids < 2^31, which evrep_plan_init ensures)
     int nunit;
     uint32_t nunit_m, nunit_sh, h_m, h_sh;
-    int xflags;  // bit 2 (value 4): two-chunk units of sparse windows: only units of >= kHotSubMin records are handed over (r05b: a monster unit's
-                 // ordering is the main launch's tail -- 200 us on the 1 Mpx circle -- while the mid-size hot units of a 640x480 window are
-                 // better off ordered beside the store-bound waves);
-                 // bit 1: builders with a hot-launch split sweep (float32 ERGO-12) hand units beyond the record stage over whole -- set by
-                 // the host for one-chunk units of windows whose AVERAGE unit fits the stage (hot units are the exception: on dense
-                 // windows every unit would go, and the hot launch is the slower place: 8 x 500 000 events 82 -> 134 us, measured);
-                 // EVREP_PLAN_X_HANDOVER2 (experiment) also sets it for two-chunk units
+    int xflags;  // kXf* bits (below): which units beyond the record stage a main launch hands to the launches behind it
     int merge;   // 1: the row's last unit also takes the short tail chunk of a sensor whose width is not a multiple of 128 (r04:
                  // Gen1's 304-pixel rows are 128 + 128 + 48 -- a third of the units were 48-pixel tails with a full unit's
                  // fixed cost; now a row is two units, 128 and 176 pixels)
 };
+// UnitCfg::xflags, set by the host (unit_cfg and the entry points), read by the builder waves.
+// kXfHandOverWhole: builders with a hot-launch split sweep (float32 ERGO-12) hand units beyond the record stage over whole -- set by
+// the host for one-chunk units of windows whose AVERAGE unit fits the stage (hot units are the exception: on dense windows every
+// unit would go, and the hot launch is the slower place: 8 x 500 000 events 82 -> 134 us, measured); EVREP_PLAN_X_HANDOVER2
+// (experiment) also sets it for two-chunk units.
+// kXfHandOverMonsters: two-chunk units of sparse windows: only units of >= kHotSubMin records are handed over (r05b: a monster
+// unit's ordering is the main launch's tail -- 200 us on the 1 Mpx circle -- while the mid-size hot units of a 640x480 window are
+// better off ordered beside the store-bound waves).
+// kXfCoopErgo12: the float32 ERGO-12 hands units of >= kErgoCoopMin records to the cooperative launch (k_mdes_coop, r06).
+constexpr int kXfHandOverWhole = 2, kXfHandOverMonsters = 4, kXfCoopErgo12 = 8;
 // floor(n / d) for 0 <= n < 2^31 as mulhi(n, m) >> sh (Granlund-Montgomery: l = ceil(log2 d), m = floor(2^(31 + l) / d) + 1,
 // sh = l - 1; m == 0 stands for d == 1)
 __host__ inline void fastdiv_make(uint32_t d, uint32_t &m, uint32_t &sh) {
@@ -106,7 +110,7 @@ __host__ __device__ inline int units_per_row(int nchunk, int span, int merge) {
 }
 // float32 builders on sparse windows take two consecutive 128-pixel chunks per wave (the same 12 KB per
 // wave as a float64 builder: 108 -> 90 us for EventStack at 640x480x32); chosen on the host from the
-// average record count per chunk, see unit_cfg() in evrep_capi.hip.
+// average record count per chunk, see unit_cfg() in evrep_capi_builders.h.
 
 // LDS carve of one builder wave.  HOT_: the wave belongs to a HOT launch (run_units): it may run the paths of units that
 // do not fit the stage (the spill sort of unit_records, emit_rounds); a main launch defers such units instead.
@@ -2300,9 +2304,10 @@ __device__ inline void mdes_unit(const BinView &bv, const int64_t *__restrict__ 
         auto never = []() -> bool { return false; };
         auto nof = [](uint32_t, const Rec8 &, uint2 &, const uint2 &) -> bool { return false; };
         // lane k: the status word of the window's block k (meta_prefetch: q2.x), merged by unit_records only when a unit is hot
-        auto sp = unit_split<true>(never, nof, never, kErgoSplitWords, (uint32_t)mraw.q2.x | ((uc.xflags & 14) ? 0u : kStEscaped),
-                                   (uc.xflags & 2) ? 0u : kHotSubMin);
-        sp.coop_min = (uc.xflags & 8) ? kErgoCoopMin : 0u;   // r06: a cooperative launch of sixteen waves per unit takes the big ones (k_mdes_coop)
+        auto sp = unit_split<true>(never, nof, never, kErgoSplitWords,
+                                   (uint32_t)mraw.q2.x | ((uc.xflags & (kXfHandOverWhole | kXfHandOverMonsters | kXfCoopErgo12)) ? 0u : kStEscaped),
+                                   (uc.xflags & kXfHandOverWhole) ? 0u : kHotSubMin);
+        sp.coop_min = (uc.xflags & kXfCoopErgo12) ? kErgoCoopMin : 0u;   // r06: a cooperative launch of sixteen waves per unit takes the big ones (k_mdes_coop)
         u = unit_front<OutT, HOT, false, NoVisit>(bv, off, H, W, nchunk, uc, w, g, uid, part, NoVisit(), sp);
         // (two-chunk units -- sparse windows, 640x480 / 1280x720 at 50 000 - 200 000 events -- keep the ordered ways: measured, r05b,
         //  their hot units are few and huge -- 4 000 to 20 000 records, one wave's instruction stream each, 30 to 100 us of sweep --
@@ -3717,10 +3722,10 @@ __global__ __launch_bounds__(kWave, HOT ? 4 : (CM <= 12 ? EVREP_TORE_WAVES : 1))
                 } else {
                     auto never = []() -> bool { return false; };
                     auto nof = [](uint32_t, const Rec8 &, uint2 &, const uint2 &) -> bool { return false; };
-                    const bool hand = (uc.xflags & 6) && tf == nullptr && !(m.status & EVREP_ST_UNSORTED);   // wave-uniform
+                    const bool hand = (uc.xflags & (kXfHandOverWhole | kXfHandOverMonsters)) && tf == nullptr && !(m.status & EVREP_ST_UNSORTED);   // wave-uniform
                     ur = unit_records<float, HOT, false, NoVisit>(bv, off, b, H * nchunk, row * nchunk + ch_lo, row * nchunk + ch_hi + 1,
                                       row * W + ch_lo * kChunkPx, (ch_hi - ch_lo + 1) * kChunkPx, w, row * W + sc_lo, ch_lo * kChunkPx, uid, npix, part,
-                                      NoVisit(), unit_split_whole<true>(never, nof, never, 2 * K, hand ? 0u : kStEscaped, (uc.xflags & 2) ? 0u : kHotSubMin));
+                                      NoVisit(), unit_split_whole<true>(never, nof, never, 2 * K, hand ? 0u : kStEscaped, (uc.xflags & kXfHandOverWhole) ? 0u : kHotSubMin));
                 }
             } else {
                 const uint32_t *co = bv.chunk_off + ((size_t)b * H + row) * (nchunk + 1);
@@ -4838,7 +4843,7 @@ __global__ __launch_bounds__(kWave, (HOT || SM) ? 4 : EVREP_PS_WAVES) void k_pol
             auto never = []() -> bool { return false; };
             auto nof = [](uint32_t, const Rec8 &, uint2 &, const uint2 &) -> bool { return false; };
             u = unit_front<float, HOT, false, NoVisit>(bv, off, H, W, nchunk, uc, w, g, uid, part, NoVisit(),
-                                                       unit_split<true>(never, nof, never, kPsWords, (uc.xflags & 2) ? 0u : kStEscaped));
+                                                       unit_split<true>(never, nof, never, kPsWords, (uc.xflags & kXfHandOverWhole) ? 0u : kStEscaped));
         }
         if (u.deferred) return;
         float *dst = out + (((size_t)g.b * H + g.row) * (size_t)W + g.c0) * C;

@@ -85,7 +85,13 @@ typedef struct evrep_plan {
 #define EVREP_PLAN_BIG_BLOCKS 8u        /* key-sorted pass: 8192-event blocks also for short windows */
 #define EVREP_PLAN_NO_FUSED_SCATTER 16u /* three-kernel pass: separate scan and scatter kernels */
 #define EVREP_PLAN_X_SPAN2 64u          /* experiment: float64 MDES units of two 128-pixel chunks (NOTES.md 8) */
+#define EVREP_PLAN_X_STAGE128 128u      /* experiment: a 128-record stage also for one-chunk units of sparse windows */
 #define EVREP_PLAN_X_TAIL_MERGE 256u    /* experiment: a row's last unit also takes a short tail chunk (NOTES.md r04: slower) */
+#define EVREP_PLAN_X_STAGE64 512u       /* experiment: key-sorted one-chunk units stage 64 records: units of > 64 records leave the two-batch path */
+#define EVREP_PLAN_X_HANDOVER2 1024u    /* experiment: two-chunk units beyond the record stage also go to the hot launch whole */
+#define EVREP_PLAN_X_HANDOVER_DENSE 2048u /* experiment: one-chunk units are handed over whole on dense windows as well */
+#define EVREP_PLAN_X_NO_SWEEP_MAIN 4096u  /* experiment: TORE and the accumulators keep the ordered main launch on dense windows */
+#define EVREP_PLAN_X_NO_MONSTER_HANDOVER 8192u /* experiment: two-chunk units hand nothing over, not even their monster units */
 #define EVREP_PLAN_X_POLSTATS_ORDERED 65536u /* A/B: the n_imagenet accumulators by k_polstats also where r06 streams them (k_polstats_stream) */
 #define EVREP_PLAN_X_ESTACK_ORDERED 131072u /* A/B: EventStack by k_event_stack also where r06 streams it (k_event_stack_stream) */
 #define EVREP_PLAN_X_MDES_NO_COOP 4194304u /* A/B: the ordered float32 ERGO-12's big hot units by time slices of one-wave workgroups (r05) instead of k_mdes_coop */

@@ -32,6 +32,24 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
     assert lib.evrep_abi_version() == _lib.ABI_VERSION
 
 
+def _declared_plan_flags():
+    text = open(os.path.join(ROOT, "include", "evrep.h")).read()
+    return {name: int(value) for name, value in re.findall(r"^#define\s+EVREP_(PLAN_[A-Z0-9_]+)\s+(\d+)u\b", text, flags=re.M)}
+
+
+def test_plan_flags_match_header():
+    """A bit renumbered on one side would send a "force the stream / force the ordered path" switch to the wrong path, whose
+    results are bit-equal: only this comparison of the two tables notices."""
+    from event_representation_study_amd import _lib
+    header = _declared_plan_flags()
+    python = {name: value for name, value in vars(_lib).items() if name.startswith("PLAN_")}
+    assert len(header) >= 22
+    assert header == python, (set(header.items()) ^ set(python.items()))
+    assert all(v > 0 and v & (v - 1) == 0 for v in header.values())
+    assert len(set(header.values())) == len(header)
+    assert {bit for _, bit in _lib._ENV_FLAGS} <= set(header.values())
+
+
 def test_plan_struct_layout_matches_header(lib):
     from event_representation_study_amd._lib import Plan
     p = Plan()
