@@ -156,7 +156,8 @@ int evrep_optimized(const evrep_plan *plan, const int32_t *events, const int64_t
  * window: level k = polarity of the last event at each pixel among events[off_k:].
  * out DEVICE (B,H,W,S) float32; premap 1 applies p -> (p+1)//2 first (gen1_transforms.py:34) and the value is
  * int8(2p - 1) (event_stack.py:18); premap 0: p is {0,1}; premap 2: the p column already holds the int8 value
- * (EventStack.pre_stack builds both halves on the host side: past as is, future reversed and negated, :21-41). */
+ * (EventStack.pre_stack builds both halves on the host side: past as is, future reversed and negated, :21-41).
+ * `scale`: the int8 value as float32 times `scale`, one float32 multiply; pixels without an event stay +0. */
 int evrep_event_stack(const evrep_plan *plan, const int32_t *events, const int64_t *offsets, void *workspace,
                       int32_t stack_size, int32_t premap, float scale, float *out, void *stream);
 
@@ -173,7 +174,9 @@ int evrep_event_stack(const evrep_plan *plan, const int32_t *events, const int64
  * overflows.  Two forms compute it: exp((t - tref) / tau) * exp((tref - t_cut) / tau) around the last cut tref (one
  * exponential per event), and exp((t - t_cut) / tau) per slice.  The factorised form is taken only while every factor is a
  * normal float64: no live cut more than 600 tau from tref and no event of the window (binning statistics: t.min(), t.max())
- * more than 700 tau before or after it.  float32: the float64 value rounded once. */
+ * more than 700 tau before or after it.  float32: the float64 value rounded once.
+ * `scale`: every surface value, untouched pixels included, is exp(.) * scale in float64 before that rounding (the factorised form
+ * carries scale in its per-slice factor); slices the scan never reaches stay exactly 0. */
 int evrep_time_surface(const evrep_plan *plan, const int32_t *events, const int64_t *offsets, void *workspace,
                        int32_t slices, const int32_t *indices, double tau, int32_t premap, double scale,
                        int32_t out_dtype, void *out, void *stream);
@@ -193,6 +196,8 @@ int evrep_time_surface_ftime(const evrep_plan *plan, const int32_t *events, cons
  * frame_mode 2: full (H,W) frame, no shift (x, y used as 0-based pixel coordinates).
  * Timestamps that are not ascending (EVREP_ST_UNSORTED): array order, each event replacing the (pixel, polarity) k-vector v by the
  * sorted [dt] + v[:k-1] -- what np.partition yields there on numpy >= 2.0 / AVX2+ hosts (tore.py:22-25).
+ * `scale`: the finished float32 value max(log(v + 1) - log(151), 0) times `scale`, one float32 multiply, empty FIFOs included; a
+ * negative scale is taken (the values then descend along a FIFO).
  * out DEVICE float32. */
 int evrep_tore(const evrep_plan *plan, const int32_t *events, const int64_t *offsets, void *workspace,
                int32_t k, int32_t frame_mode, const int32_t *sample_times, float scale, float *out, void *stream);
@@ -209,7 +214,9 @@ int evrep_tore_ftime(const evrep_plan *plan, const int32_t *events, const int64_
  * mode 0.  mode 1 = tonic.transforms.ToVoxelGrid as gen1_transforms.py:22-25 consumes it
  * (restated from tonic's published algorithm; parity unpinned).  mode 2 = ev-licious
  * events_to_voxel_grid, integer-pixel path (ev-licious/src/evlicious/tools/utils.py:52-108), before
- * its optional normalisation.  out DEVICE (B,H,W,bins) float64. */
+ * its optional normalisation.  out DEVICE (B,H,W,bins) float64.
+ * `scale` (here and in evrep_voxel_range / evrep_voxel_tnorm): the finished float64 sum of a (pixel, bin) cell times `scale`,
+ * once, at the pixels that hold an event; a pixel without events stays +0 whatever the sign of scale. */
 int evrep_voxel(const evrep_plan *plan, const int32_t *events, const int64_t *offsets, void *workspace,
                 int32_t bins, int32_t mode, double scale, double *out, void *stream);
 /* The same with an explicit time range per window (mode 2 only): t_range DEVICE int64 [B,2] = the t0_us, t1_us

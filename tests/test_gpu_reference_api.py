@@ -236,17 +236,9 @@ def test_tonic_standins_vs_numpy_restatement():
     ev = make_events(N, W, H, seed=77, polarity="01")
     grid = ToVoxelGrid((W, H, 2), n_time_bins=T)(to_structured(ev))
     assert grid.shape == (T, 1, H, W)
-    ref = np.zeros(T * H * W)
-    ts = T * (ev[:, 2].astype(float) - ev[0, 2]) / (ev[-1, 2] - ev[0, 2])
-    pol = np.where(ev[:, 3] == 0, -1, ev[:, 3]).astype(float)
-    tis = ts.astype(int)
-    dts = ts - tis
-    base = ev[:, 0] + ev[:, 1] * W
-    ok = tis < T
-    np.add.at(ref, base[ok] + tis[ok] * W * H, (pol * (1.0 - dts))[ok])
-    ok = (tis + 1) < T
-    np.add.at(ref, base[ok] + (tis[ok] + 1) * W * H, (pol * dts)[ok])
-    assert_bit_equal(np.ascontiguousarray(grid[:, 0]), ref.reshape(T, H, W))
+    from oracle import options_oracle
+    ref = options_oracle.tonic_voxel(ev, H, W, T)                       # (H, W, T)
+    assert_bit_equal(np.ascontiguousarray(grid[:, 0]), np.ascontiguousarray(np.moveaxis(ref, -1, 0)))
     img = ToImage((W, H, 2))(to_structured(ev))
     want = np.zeros((2, H, W), np.int16)
     np.add.at(want, (ev[:, 3], ev[:, 1], ev[:, 0]), 1)
