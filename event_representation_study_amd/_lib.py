@@ -101,6 +101,8 @@ SYMBOLS = {
     "evrep_time_index": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "evrep_sort_image_scratch_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32]),
     "evrep_sort_image": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _I32P, _i32, _vp, _vp, _vp, _vp]),
+    "evrep_detector_input": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
+                                            _vp, _vp, _vp, _f32, _vp, _vp]),
 }
 # evrep_time_index / evrep_sort_image: modes, per-window status bits (NO_INDEX << polarity class), flags, limits
 TIME_INDEX_RAW, TIME_INDEX_RANK = 0, 1
@@ -112,6 +114,8 @@ EST_BWD_MAX_SEG = 8192
 # evrep_est_prepare: status bits, the largest B
 EST_PREP_DESCENDING, EST_PREP_BAD_INDEX, EST_PREP_BAD_POLARITY, EST_PREP_OUT_OF_FRAME = 1, 2, 4, 8
 EST_PREP_MAX_B = 65535
+# evrep_detector_input: per-sample flags
+DETIN_WARP, DETIN_FLIPUD, DETIN_FLIPLR = 1, 2, 4
 # evrep_dist / evrep_dense_rank_f32: limits
 DIST_MAX_B, RANK_MAX_SEGMENTS = 1 << 20, 1 << 24
 # evrep_nimg_prepare: mode flags, per-window parameter flags, per-window status bits

@@ -624,6 +624,38 @@ size_t evrep_sort_image_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t K
 int evrep_sort_image(const float *prim, int32_t B, int32_t H, int32_t W, int32_t K, uint32_t flags, const int32_t *quantize,
                      int32_t nq, float *out, uint32_t *status, void *scratch, void *stream);
 
+/* The detector's input batch in ONE launch: what Gen1H5.__getitem__ does after get_item_transform, plus collate_fn and
+ * Trainer.prepro_data (ev-YOLOv6/yolov6/data/gen1_2yolo.py:230-265,320-398,427-447; data_augment.py:31-85,110-184;
+ * yolov6/core/engine.py:629-635).  A channel-last representation becomes the channel-first float32 tensor of the detector; per
+ * output element, with T the dtype of rep and no multiply fused with an add:
+ *     R  R(b, y, x, c) = what evrep_resize_taps writes with scale 1 and out_dtype T through the given tap tables (x taps, then y
+ *        taps, both sums in float64 in tap order, one cast to T); one tap of weight 1 per row and column copies the source.
+ *     L  I(b, y, x, c) = R(b, y - top, x - left, c) inside the nh x nw rectangle of the S x S square, pad[c] elsewhere.
+ *     W  where flags[b] has EVREP_DETIN_WARP: cv2.warpAffine(I, M[:2], dsize=(S, S), borderValue=pad) with its defaults
+ *        (INTER_LINEAR, BORDER_CONSTANT), restated from OpenCV's published algorithm -- parity unpinned (cv2 absent).  The inverse
+ *        map comes as integer tables in 10-bit fixed point, warp[b] = { adelta[S], bdelta[S], X0[S], Y0[S] } (X0, Y0 per output
+ *        row, rounding offset 16 included):  X = (X0[y] + adelta[x]) >> 5, Y = (Y0[y] + bdelta[x]) >> 5 (arithmetic shifts);
+ *        sx = clamp(X >> 5, -32768, 32767), sy likewise; ax = (X & 31) / 32, ay = (Y & 31) / 32;  the value, in T, is
+ *        ((v00 w00 + v01 w01) + v10 w10) + v11 w11, w00 = (1-ay)(1-ax), w01 = (1-ay) ax, w10 = ay (1-ax), w11 = ay ax, v00 at
+ *        (sy, sx), v01 at (sy, sx+1), v10 at (sy+1, sx), v11 at (sy+1, sx+1), a tap outside [0, S) being pad[c].  The sums
+ *        X0 + adelta and Y0 + bdelta are the caller's to keep inside int32 (event_representation_study_amd/detector_input.py
+ *        refuses a matrix whose tables leave it); the kernel adds them in 64 bits.
+ *     F  F(b, y, x, c) = W(b, S-1-y if EVREP_DETIN_FLIPUD, S-1-x if EVREP_DETIN_FLIPLR, c)
+ *        out[b, c, y, x] = (float)F(b, y, x, C-1-c) * scale        (scale = (float)(1.0 / 255): torch's `.float() / 255`; 1: as is)
+ * rep DEVICE float64/float32 (rep_dtype) [B,H,W,C]; tap tables DEVICE as for evrep_resize_taps, for nh rows and nw columns of
+ * T weights each; pad DEVICE double [C]; flags DEVICE uint32 [B] with warp DEVICE int32 [B,4,S] (entries of samples without
+ * EVREP_DETIN_WARP are not read), or both NULL: no sample warps or flips; out DEVICE float [B,C,S,S], every element written
+ * exactly once.  1 <= B <= 65535, 1 <= C <= EVREP_MAX_CHANNELS, H, W, S, T in 1..EVREP_MAX_DIM, the rectangle inside the
+ * square; anything else, a NULL or misaligned pointer or a NaN scale is EVREP_EINVAL before any launch.  Every index is
+ * brought into range before a load, whatever the tables hold.  Does not allocate, does not wait for the device. */
+#define EVREP_DETIN_WARP 1u
+#define EVREP_DETIN_FLIPUD 2u
+#define EVREP_DETIN_FLIPLR 4u
+int evrep_detector_input(const void *rep, int32_t rep_dtype, int32_t B, int32_t H, int32_t W, int32_t C, int32_t nh, int32_t nw,
+                         int32_t T, const int32_t *ystart, const int32_t *ycount, const double *ywt, const int32_t *xstart,
+                         const int32_t *xcount, const double *xwt, int32_t S, int32_t top, int32_t left, const double *pad,
+                         const uint32_t *flags, const int32_t *warp, float scale, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
