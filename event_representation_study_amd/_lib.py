@@ -103,6 +103,9 @@ SYMBOLS = {
     "evrep_sort_image": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _I32P, _i32, _vp, _vp, _vp, _vp]),
     "evrep_detector_input": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
                                             _vp, _vp, _vp, _f32, _vp, _vp]),
+    "evrep_resize_tap_tables": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp]),
+    "evrep_detector_input_frames_scratch_bytes": (ctypes.c_size_t, [_i32]),
+    "evrep_detector_input_frames": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp]),
 }
 # evrep_time_index / evrep_sort_image: modes, per-window status bits (NO_INDEX << polarity class), flags, limits
 TIME_INDEX_RAW, TIME_INDEX_RANK = 0, 1
@@ -116,6 +119,21 @@ EST_PREP_DESCENDING, EST_PREP_BAD_INDEX, EST_PREP_BAD_POLARITY, EST_PREP_OUT_OF_
 EST_PREP_MAX_B = 65535
 # evrep_detector_input: per-sample flags
 DETIN_WARP, DETIN_FLIPUD, DETIN_FLIPLR = 1, 2, 4
+# evrep_resize_tap_tables: interpolation codes; the columns of an axis descriptor
+TAPS_LINEAR, TAPS_AREA, TAPS_IDENTITY = 0, 1, 2
+TAPS_AXIS_FIELDS = 6
+
+
+class DetinFrame(ctypes.Structure):
+    """evrep_detin_frame: one sample of evrep_detector_input_frames."""
+    _fields_ = [("src", ctypes.c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("rh", ctypes.c_int32), ("rw", ctypes.c_int32), ("T1", ctypes.c_int32),
+                ("row1", ctypes.c_int32), ("col1", ctypes.c_int32), ("wrow1", ctypes.c_int32), ("wcol1", ctypes.c_int32),
+                ("nh", ctypes.c_int32), ("nw", ctypes.c_int32), ("T2", ctypes.c_int32),
+                ("row2", ctypes.c_int32), ("col2", ctypes.c_int32), ("wrow2", ctypes.c_int32), ("wcol2", ctypes.c_int32),
+                ("top", ctypes.c_int32), ("left", ctypes.c_int32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_int32)]
+
+
 # evrep_dist / evrep_dense_rank_f32: limits
 DIST_MAX_B, RANK_MAX_SEGMENTS = 1 << 20, 1 << 24
 # evrep_nimg_prepare: mode flags, per-window parameter flags, per-window status bits

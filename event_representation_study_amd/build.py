@@ -23,7 +23,7 @@ UNIT_DEPS = {"evrep_capi.hip": _BIN, "evrep_capi_mdes.hip": _BLD, "evrep_capi_bu
              "evrep_capi_sort.hip": ["evrep_sort.hip", "evrep_ranksort.h", "evrep_common.h", "evrep_capi_shared.h"],
              "evrep_est_bwd.hip": ["evrep_est_table.h", "evrep_common.h", "evrep_capi_shared.h"],
              "evrep_est_prep.hip": ["evrep_common.h", "evrep_capi_shared.h"],
-             "evrep_capi_detin.hip": ["evrep_detin.hip", "evrep_common.h", "evrep_capi_shared.h"]}
+             "evrep_capi_detin.hip": ["evrep_detin.hip", "evrep_detin_frames.hip", "evrep_common.h", "evrep_capi_shared.h"]}
 OBJDIR = os.path.join(PKG, "_obj")
 
 # -ffp-contract=off: the parity contract is bit-exactness with the reference's separate

@@ -1,7 +1,10 @@
-// evrep_capi_detin.hip -- the extern "C" surface, part 10: the detector's input batch (evrep_detin.hip): argument checks and
-// the one launch.  No plan, no workspace, no allocation, no wait for the device.
+// evrep_capi_detin.hip -- the extern "C" surface, part 10: the detector's input batch (evrep_detin.hip) and its form for frames
+// of different sizes with the tap tables made on the device (evrep_detin_frames.hip): argument checks and one launch per entry
+// point.  No plan, no workspace, no allocation, no wait for the device.
+#include <limits.h>
+
 #include "evrep_capi_shared.h"
-#include "evrep_detin.hip"
+#include "evrep_detin_frames.hip"
 
 using namespace evrep;
 using evrep_host::hip_check;
@@ -47,6 +50,82 @@ int evrep_detector_input(const void *rep, int32_t rep_dtype, int32_t B, int32_t 
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (rep_dtype == EVREP_F64) return detin_launch<double>(d, rep, B, stream);
     return detin_launch<float>(d, rep, B, stream);
+}
+
+int evrep_resize_tap_tables(const int32_t *axes, int32_t n_axes, int32_t max_dst, int32_t *start, int32_t *count, double *weights,
+                            int64_t n_rows, int64_t n_wt, void *stream_) {
+    if (n_axes < 1 || max_dst < 1 || max_dst > EVREP_MAX_DIM) return EVREP_EINVAL;
+    if (n_rows < 1 || n_wt < 1 || n_rows > INT32_MAX || n_wt > INT32_MAX) return EVREP_EINVAL;
+    if (bad_ptr(axes, 4) || bad_ptr(start, 4) || bad_ptr(count, 4) || bad_ptr(weights, 8)) return EVREP_EINVAL;
+    TapTableArgs a;
+    a.axes = axes; a.start = start; a.count = count; a.wt = weights; a.n_rows = n_rows; a.n_wt = n_wt; a.n_axes = n_axes;
+    const dim3 grid((unsigned)n_axes, (unsigned)((max_dst + kThreads - 1) / kThreads));
+    k_resize_tap_tables<<<grid, kThreads, 0, static_cast<hipStream_t>(stream_)>>>(a);
+    LAUNCH_CHECK("k_resize_tap_tables");
+    return EVREP_OK;
+}
+
+size_t evrep_detector_input_frames_scratch_bytes(int32_t B) {
+    return (B < 1 || B > 65535) ? 0 : (size_t)B * sizeof(evrep_detin_frame);
+}
+
+// offset >= 0 and [offset, offset + n * per) inside [0, limit)
+static inline bool run_inside(int32_t off, int32_t n, int32_t per, int64_t limit) {
+    return off >= 0 && (int64_t)off + (int64_t)n * per <= limit;
+}
+
+int evrep_detector_input_frames(const evrep_detin_frame *frames, int32_t B, int32_t rep_dtype, int32_t C, int32_t S,
+                                const int32_t *start, const int32_t *count, const double *weights, int64_t n_rows, int64_t n_wt,
+                                const double *pad, const int32_t *warp, float scale, void *frames_dev, float *out, void *stream_) {
+    if (rep_dtype != EVREP_F64 && rep_dtype != EVREP_F32) return EVREP_EINVAL;
+    if (B <= 0 || B > 65535 || C < 1 || C > EVREP_MAX_CHANNELS || S < 1 || S > EVREP_MAX_DIM) return EVREP_EINVAL;
+    if (n_rows < 1 || n_wt < 1 || n_rows > INT32_MAX || n_wt > INT32_MAX) return EVREP_EINVAL;
+    if (!(scale == scale)) return EVREP_EINVAL;   // NaN
+    if (bad_ptr(frames, 8) || bad_ptr(frames_dev, 8) || bad_ptr(out, 4) || bad_ptr(pad, 8)) return EVREP_EINVAL;
+    if (bad_ptr(start, 4) || bad_ptr(count, 4) || bad_ptr(weights, 8)) return EVREP_EINVAL;
+    const uintptr_t elem = rep_dtype == EVREP_F64 ? 8 : 4;
+    const auto dim = [](int32_t v) { return v >= 1 && v <= EVREP_MAX_DIM; };
+    bool warps = false;
+    for (int32_t b = 0; b < B; ++b) {
+        const evrep_detin_frame &f = frames[b];
+        if (bad_ptr(f.src, elem)) return EVREP_EINVAL;
+        if (!dim(f.H) || !dim(f.W) || !dim(f.rh) || !dim(f.rw) || !dim(f.nh) || !dim(f.nw) || !dim(f.T1)) return EVREP_EINVAL;
+        if (f.T2 < 0 || f.T2 > EVREP_MAX_DIM) return EVREP_EINVAL;
+        if (f.top < 0 || f.left < 0 || f.nh > S - f.top || f.nw > S - f.left) return EVREP_EINVAL;
+        if (!run_inside(f.row1, f.rh, 1, n_rows) || !run_inside(f.col1, f.rw, 1, n_rows)) return EVREP_EINVAL;
+        if (!run_inside(f.wrow1, f.rh, f.T1, n_wt) || !run_inside(f.wcol1, f.rw, f.T1, n_wt)) return EVREP_EINVAL;
+        if (f.T2 == 0) {
+            if (f.nh != f.rh || f.nw != f.rw) return EVREP_EINVAL;
+        } else {
+            if (!run_inside(f.row2, f.nh, 1, n_rows) || !run_inside(f.col2, f.nw, 1, n_rows)) return EVREP_EINVAL;
+            if (!run_inside(f.wrow2, f.nh, f.T2, n_wt) || !run_inside(f.wcol2, f.nw, f.T2, n_wt)) return EVREP_EINVAL;
+        }
+        if (f.flags & ~(EVREP_DETIN_WARP | EVREP_DETIN_FLIPUD | EVREP_DETIN_FLIPLR)) return EVREP_EINVAL;
+        warps = warps || (f.flags & EVREP_DETIN_WARP) != 0u;
+    }
+    if (warps ? bad_ptr(warp, 4) : warp != nullptr) return EVREP_EINVAL;   // the flag and the tables come together
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int rc = hip_check(hipMemcpyAsync(frames_dev, frames, (size_t)B * sizeof(evrep_detin_frame), hipMemcpyHostToDevice, stream),
+                       "hipMemcpyAsync(frames)");
+    if (rc != EVREP_OK) return rc;
+    const int P = kThreads / ((C + kDetinGroup - 1) / kDetinGroup);   // pixels of a workgroup (evrep_detin.hip)
+    const dim3 grid((unsigned)(((size_t)S * S + P - 1) / P), (unsigned)B);
+    const auto fill = [&](auto &a) {
+        a.frames = static_cast<const evrep_detin_frame *>(frames_dev);
+        a.tstart = start; a.tcount = count; a.twt = weights; a.pad = pad; a.warp = warp; a.out = out;
+        a.n_rows = n_rows; a.n_wt = n_wt; a.C = C; a.S = S; a.scale = scale;
+    };
+    if (rep_dtype == EVREP_F64) {
+        DetinFramesArgs<double> a;
+        fill(a);
+        k_detector_input_frames<double><<<grid, kThreads, 0, stream>>>(a);
+    } else {
+        DetinFramesArgs<float> a;
+        fill(a);
+        k_detector_input_frames<float><<<grid, kThreads, 0, stream>>>(a);
+    }
+    LAUNCH_CHECK("k_detector_input_frames");
+    return EVREP_OK;
 }
 
 }  // extern "C"

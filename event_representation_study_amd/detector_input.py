@@ -14,8 +14,13 @@ is OpenCV's fixed-point walk of the inverse map (10 fractional bits, coordinates
 stored as int16), see ``warp_tables``; ``borderValue`` is a per-channel table because what cv2's four-entry Scalar does for a
 fifth channel is not known here.
 
-Out of scope (NotImplementedError): ``rect`` / ``batch_shapes``, and TORE's per-window bounding-box frames as one batch (call
-``prepare`` per window).
+Frames of DIFFERENT sizes -- TORE's per-window bounding boxes, ``EventBatch.tore(frame_mode=0)`` -- go through
+``DetectorFrontEnd.prepare_frames``: every sample through its own geometry, the resize tap tables made on the device
+(``evrep_resize_tap_tables``), then ONE launch of ``evrep_detector_input_frames`` (csrc/evrep_detin_frames.hip); a sample whose
+letterbox needs a resize of its own takes both resizes inside that launch.  ``targets_frames`` is its host side (targets and
+shapes from the B frame sizes), usable without a device.  ``prepare`` itself keeps refusing a list.
+
+Out of scope (NotImplementedError): ``rect`` / ``batch_shapes``.
 """
 import collections
 import ctypes
@@ -369,37 +374,217 @@ class DetectorFrontEnd:
 
     def targets(self, labels, params, g, lb_pad):
         """The box statements of __getitem__:348-394, random_affine's label branch and the flips, per sample, then collate_fn."""
-        S, rows = self.img_size, []
-        for b, lab in enumerate(labels or []):
-            lab = np.array(lab, copy=True)
-            lab = lab.reshape(-1, 5) if lab.size else np.zeros((0, 5), dtype=lab.dtype if lab.dtype.kind == "f" else np.float32)
-            p = params[b]
-            if lab.size:
-                w, h = g.rw * g.ratio, g.rh * g.ratio
-                boxes = np.copy(lab[:, 1:])
-                boxes[:, 0] = w * (lab[:, 1] - lab[:, 3] / 2) + lb_pad[0]
-                boxes[:, 1] = h * (lab[:, 2] - lab[:, 4] / 2) + lb_pad[1]
-                boxes[:, 2] = w * (lab[:, 1] + lab[:, 3] / 2) + lb_pad[0]
-                boxes[:, 3] = h * (lab[:, 2] + lab[:, 4] / 2) + lb_pad[1]
-                lab[:, 1:] = boxes
-            if self.augment:
-                lab = _affine_labels(lab, np.asarray(p.M, dtype=np.float64), p.s, S, S)
-            if len(lab):
-                lab[:, [1, 3]] = lab[:, [1, 3]].clip(0, S - 1e-3)
-                lab[:, [2, 4]] = lab[:, [2, 4]].clip(0, S - 1e-3)
-                boxes = np.copy(lab[:, 1:])
-                boxes[:, 0] = ((lab[:, 1] + lab[:, 3]) / 2) / S
-                boxes[:, 1] = ((lab[:, 2] + lab[:, 4]) / 2) / S
-                boxes[:, 2] = (lab[:, 3] - lab[:, 1]) / S
-                boxes[:, 3] = (lab[:, 4] - lab[:, 2]) / S
-                lab[:, 1:] = boxes
-                if p.flipud:
-                    lab[:, 2] = 1 - lab[:, 2]
-                if p.fliplr:
-                    lab[:, 1] = 1 - lab[:, 1]
-            t = torch.zeros((len(lab), 6))
-            if len(lab):
-                t[:, 1:] = torch.from_numpy(np.ascontiguousarray(lab))
-            t[:, 0] = b
-            rows.append(t)
+        rows = [self._sample_targets(b, lab, params[b], g, lb_pad) for b, lab in enumerate(labels or [])]
         return torch.cat(rows, 0) if rows else torch.zeros((0, 6))
+
+    def _sample_targets(self, b, lab, p, g, lb_pad):
+        """Sample b's rows of ``targets``: its boxes through its own geometry ``g`` and letterbox pad."""
+        S = self.img_size
+        lab = np.array(lab, copy=True)
+        lab = lab.reshape(-1, 5) if lab.size else np.zeros((0, 5), dtype=lab.dtype if lab.dtype.kind == "f" else np.float32)
+        if lab.size:
+            w, h = g.rw * g.ratio, g.rh * g.ratio
+            boxes = np.copy(lab[:, 1:])
+            boxes[:, 0] = w * (lab[:, 1] - lab[:, 3] / 2) + lb_pad[0]
+            boxes[:, 1] = h * (lab[:, 2] - lab[:, 4] / 2) + lb_pad[1]
+            boxes[:, 2] = w * (lab[:, 1] + lab[:, 3] / 2) + lb_pad[0]
+            boxes[:, 3] = h * (lab[:, 2] + lab[:, 4] / 2) + lb_pad[1]
+            lab[:, 1:] = boxes
+        if self.augment:
+            lab = _affine_labels(lab, np.asarray(p.M, dtype=np.float64), p.s, S, S)
+        if len(lab):
+            lab[:, [1, 3]] = lab[:, [1, 3]].clip(0, S - 1e-3)
+            lab[:, [2, 4]] = lab[:, [2, 4]].clip(0, S - 1e-3)
+            boxes = np.copy(lab[:, 1:])
+            boxes[:, 0] = ((lab[:, 1] + lab[:, 3]) / 2) / S
+            boxes[:, 1] = ((lab[:, 2] + lab[:, 4]) / 2) / S
+            boxes[:, 2] = (lab[:, 3] - lab[:, 1]) / S
+            boxes[:, 3] = (lab[:, 4] - lab[:, 2]) / S
+            lab[:, 1:] = boxes
+            if p.flipud:
+                lab[:, 2] = 1 - lab[:, 2]
+            if p.fliplr:
+                lab[:, 1] = 1 - lab[:, 1]
+        t = torch.zeros((len(lab), 6))
+        if len(lab):
+            t[:, 1:] = torch.from_numpy(np.ascontiguousarray(lab))
+        t[:, 0] = b
+        return t
+
+    # -------------------------------------------------------------------------------------------- frames of different sizes
+    def frame_geometries(self, sizes):
+        """``geometry`` of every (h0, w0) of a ragged batch; an empty frame (an empty window has no bounding box) and a frame so
+        thin that the keep-ratio resize leaves no row or column are ValueErrors naming the sample (the reference fails inside
+        cv2.resize or divides by zero there)."""
+        geos = []
+        for b, (h0, w0) in enumerate(sizes):
+            h0, w0 = int(h0), int(w0)
+            if h0 < 1 or w0 < 1:
+                raise ValueError("prepare_frames: sample %d is an empty %d x %d frame (an empty window)" % (b, h0, w0))
+            r = self.img_size / max(h0, w0)
+            if r != 1 and (int(h0 * r) < 1 or int(w0 * r) < 1):
+                raise ValueError("prepare_frames: sample %d (%d x %d) resizes to %d x %d" % (b, h0, w0, int(h0 * r), int(w0 * r)))
+            geos.append(self.geometry(h0, w0))
+        return geos
+
+    def _lb_pad(self, g):
+        return (g.left, g.top) if bool(self.hyp and self.hyp.get("letterbox_return_int")) else (g.dw, g.dh)
+
+    def targets_frames(self, sizes, labels=None, params=None):
+        """The host side of ``prepare_frames``, no device needed: ``sizes`` are the B (h0, w0) pairs.  Returns (targets, shapes)
+        as ``prepare`` does, sample b through its OWN geometry: the reference scales the sensor-normalised boxes by the resized
+        bounding-box frame (gen1_2yolo.py:348-363 after gen1_transforms.py:61-66), and so does this."""
+        geos = self.frame_geometries(sizes)
+        B = len(geos)
+        if labels is not None and len(labels) != B:
+            raise ValueError("prepare_frames: %d label arrays for %d frames" % (len(labels), B))
+        if params is None:
+            params = self.draw(B)
+        if len(params) != B:
+            raise ValueError("prepare_frames: %d parameter sets for %d frames" % (len(params), B))
+        rows = [self._sample_targets(b, lab, params[b], geos[b], self._lb_pad(geos[b])) for b, lab in enumerate(labels or [])]
+        shapes = [((int(h0), int(w0)), ((g.rh * g.ratio / int(h0), g.rw * g.ratio / int(w0)), self._lb_pad(g)))
+                  for (h0, w0), g in zip(sizes, geos)]
+        return (torch.cat(rows, 0) if rows else torch.zeros((0, 6))), shapes
+
+    def frame_tables(self, sizes, geos, params):
+        """The host side of one ragged launch: (table, host, n_axes, max_dst, n_rows, n_wt).  ``table``: the B evrep_detin_frame
+        descriptors (``src`` left 0); ``host``: the int32 buffer that is uploaded, the axis descriptors of
+        evrep_resize_tap_tables -- one axis per distinct (src, dst, interpolation, T) of the batch -- followed, when a sample
+        warps, by the (B, 4, S) warp tables.  T is known in closed form: 2 for INTER_LINEAR, ``area_taps_bound`` for INTER_AREA, 1
+        for a copy; no (dst, src) matrix is made."""
+        B, S = len(sizes), self.img_size
+        axes, rows_total, wt_total = {}, 0, 0
+
+        def axis(src, dst, code, T):
+            nonlocal rows_total, wt_total
+            key = (src, dst, code, T)
+            if key not in axes:
+                axes[key] = (rows_total, wt_total)
+                rows_total, wt_total = rows_total + dst, wt_total + dst * T
+            return axes[key]
+
+        table = np.zeros(B, dtype=_FRAME_DTYPE)
+        warp = None
+        for b, (g, p) in enumerate(zip(geos, params)):
+            h0, w0 = sizes[b]
+            d = table[b]
+            if g.r == 1:
+                code, T1 = _lib.TAPS_IDENTITY, 1
+            elif g.interp == "area":
+                code, T1 = _lib.TAPS_AREA, max(area_taps_bound(h0, g.rh), area_taps_bound(w0, g.rw))
+            else:
+                code, T1 = _lib.TAPS_LINEAR, 2
+            (d["row1"], d["wrow1"]), (d["col1"], d["wcol1"]) = axis(h0, g.rh, code, T1), axis(w0, g.rw, code, T1)
+            d["H"], d["W"], d["rh"], d["rw"], d["T1"] = h0, w0, g.rh, g.rw, T1
+            d["nh"], d["nw"], d["top"], d["left"] = g.nh, g.nw, g.top, g.left
+            if not g.fused:
+                d["T2"] = 2
+                (d["row2"], d["wrow2"]), (d["col2"], d["wcol2"]) = axis(g.rh, g.nh, _lib.TAPS_LINEAR, 2), axis(g.rw, g.nw, _lib.TAPS_LINEAR, 2)
+            flag = (_lib.DETIN_FLIPUD if p.flipud else 0) | (_lib.DETIN_FLIPLR if p.fliplr else 0)
+            if (np.asarray(p.M) != np.eye(3)).any():
+                flag |= _lib.DETIN_WARP
+                if warp is None:
+                    warp = np.zeros((B, 4, S), dtype=np.int32)
+                warp[b] = np.stack(warp_tables(p.M, S))
+            d["flags"] = flag
+        n_axes = len(axes)
+        host = np.empty(n_axes * _lib.TAPS_AXIS_FIELDS + (warp.size if warp is not None else 0), dtype=np.int32)
+        host[:n_axes * _lib.TAPS_AXIS_FIELDS] = np.array([k + v for k, v in axes.items()], dtype=np.int32).reshape(-1)
+        if warp is not None:
+            host[n_axes * _lib.TAPS_AXIS_FIELDS:] = warp.reshape(-1)
+        return table, host, n_axes, max(k[1] for k in axes), rows_total, wt_total
+
+    def prepare_frames(self, frames, labels=None, params=None, pad=114.0, scale=1.0 / 255, out=None):
+        """``prepare`` for B frames of DIFFERENT sizes -- ``EventBatch.tore(frame_mode=0)``'s per-window bounding boxes -- in one
+        launch.  frames: a list / tuple of (H_b, W_b, C) CUDA tensors of one dtype (float64 / float32), C and device; views into
+        one allocation are read where they lie, a non-contiguous frame is made contiguous.  Returns (images, targets, shapes)
+        as ``prepare`` does, every sample through its own ``geometry``.  From the host go one upload (axis descriptors and the
+        warp tables, one buffer) and the descriptor table that evrep_detector_input_frames checks and copies itself; then one
+        launch makes the tap tables (evrep_resize_tap_tables) and one the images.  A sample whose letterbox needs a resize of
+        its own takes both resizes inside that launch; no intermediate image is made.  Everything is checked, and every table
+        is made, before anything is launched.  ``out``: a contiguous (B, C, S, S) float32 tensor to write into."""
+        if not isinstance(frames, (list, tuple)) or not len(frames):
+            raise ValueError("prepare_frames: a non-empty list of (H, W, C) frames")
+        B, S = len(frames), self.img_size
+        if (params is not None and len(params) != B) or (labels is not None and len(labels) != B):
+            raise ValueError("prepare_frames: one parameter set and one label array per frame (%d frames)" % B)
+        for b, f in enumerate(frames):
+            if not torch.is_tensor(f) or f.dim() != 3:
+                raise ValueError("prepare_frames: sample %d is not an (H, W, C) tensor" % b)
+            if f.dtype not in (torch.float64, torch.float32):
+                raise TypeError("prepare_frames: float64 or float32 frames, sample %d is %s" % (b, f.dtype))
+            if f.dtype != frames[0].dtype or int(f.shape[2]) != int(frames[0].shape[2]):
+                raise TypeError("prepare_frames: sample %d is %s with %d channels, sample 0 %s with %d"
+                                % (b, f.dtype, int(f.shape[2]), frames[0].dtype, int(frames[0].shape[2])))
+        C = int(frames[0].shape[2])
+        if C < 1 or C > _lib.MAX_CHANNELS:
+            raise ValueError("prepare_frames: 1..%d channels, not %d" % (_lib.MAX_CHANNELS, C))
+        sizes = [(int(f.shape[0]), int(f.shape[1])) for f in frames]
+        geos = self.frame_geometries(sizes)
+        for b, f in enumerate(frames):
+            if not f.is_cuda or f.device != frames[0].device:
+                raise _lib.EvrepError("prepare_frames needs CUDA tensors on one device (sample %d is on %s); there is no CPU fallback"
+                                      % (b, f.device))
+        dev = frames[0].device
+        if out is None:
+            out = torch.empty((B, C, S, S), dtype=torch.float32, device=dev)
+        elif tuple(out.shape) != (B, C, S, S) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+            raise ValueError("prepare_frames: out must be a contiguous float32 tensor of shape %r on %s" % ((B, C, S, S), dev))
+        if params is None:
+            params = self.draw(B)
+        table, host, n_axes, max_dst, rows_total, wt_total = self.frame_tables(sizes, geos, params)
+        targets, shapes = self.targets_frames(sizes, labels, params)
+        keep = [f if f.is_contiguous() else f.contiguous() for f in frames]
+        table["src"] = [f.data_ptr() for f in keep]
+        has_warp = host.size > n_axes * _lib.TAPS_AXIS_FIELDS
+        lib = _lib.load()
+        up = torch.from_numpy(host).to(dev)                                    # the one upload
+        axes_d = up[:n_axes * _lib.TAPS_AXIS_FIELDS]
+        warp_d = up[n_axes * _lib.TAPS_AXIS_FIELDS:] if has_warp else None
+        idx = torch.empty(2 * rows_total, dtype=torch.int32, device=dev)
+        start_d, count_d = idx[:rows_total], idx[rows_total:]
+        wt_d = torch.empty(wt_total, dtype=torch.float64, device=dev)
+        frames_d = torch.empty(int(lib.evrep_detector_input_frames_scratch_bytes(B)) // 8, dtype=torch.int64, device=dev)
+        pad_d = _pad_table(pad, C, dev)
+        images = out
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        with torch.cuda.device(dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(lib.evrep_resize_tap_tables(ptr(axes_d), n_axes, max_dst, ptr(start_d), ptr(count_d), ptr(wt_d),
+                                                   rows_total, wt_total, stream), "evrep_resize_tap_tables")
+            _lib.check(lib.evrep_detector_input_frames(ctypes.c_void_p(table.ctypes.data), B,
+                                                       _lib.F64 if frames[0].dtype == torch.float64 else _lib.F32, C, S, ptr(start_d),
+                                                       ptr(count_d), ptr(wt_d), rows_total, wt_total, ptr(pad_d), ptr(warp_d),
+                                                       1.0 if scale is None else float(scale), ptr(frames_d), ptr(images), stream),
+                       "evrep_detector_input_frames")
+        return images, targets, shapes
+
+
+_FRAME_DTYPE = np.dtype(_lib.DetinFrame)
+
+
+def area_taps_bound(src, dst):
+    """An upper bound, in closed form, on the taps of one output sample of an INTER_AREA axis: ceil(src / dst) + 1 (the cell
+    [d scale, (d + 1) scale) touches at most that many source samples)."""
+    return (int(src) + int(dst) - 1) // int(dst) + 1
+
+
+def resize_tap_tables(axes, device):
+    """One launch of evrep_resize_tap_tables for ``axes``, a list of (src, dst, interpolation, T) with interpolation "linear" /
+    "area" / "identity".  Returns per axis the (start, count, weights, T) device tables, views into three tensors."""
+    lib = _lib.load()
+    codes = {"linear": _lib.TAPS_LINEAR, "area": _lib.TAPS_AREA, "identity": _lib.TAPS_IDENTITY}
+    desc, rows, wts = [], 0, 0
+    for src, dst, interp, T in axes:
+        desc.append((int(src), int(dst), codes[interp], int(T), rows, wts))
+        rows, wts = rows + int(dst), wts + int(dst) * int(T)
+    axes_d = torch.from_numpy(np.array(desc, dtype=np.int32).reshape(-1)).to(device)
+    start = torch.empty(rows, dtype=torch.int32, device=device)
+    count = torch.empty(rows, dtype=torch.int32, device=device)
+    wt = torch.empty(wts, dtype=torch.float64, device=device)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    with torch.cuda.device(device):
+        _lib.check(lib.evrep_resize_tap_tables(ptr(axes_d), len(desc), max(d[1] for d in desc), ptr(start), ptr(count), ptr(wt), rows, wts,
+                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "evrep_resize_tap_tables")
+    return [(start[r:r + dst], count[r:r + dst], wt[w:w + dst * T].view(dst, T), T) for (_, dst, _, T, r, w) in desc]

@@ -656,6 +656,60 @@ int evrep_detector_input(const void *rep, int32_t rep_dtype, int32_t B, int32_t 
                          const int32_t *xcount, const double *xwt, int32_t S, int32_t top, int32_t left, const double *pad,
                          const uint32_t *flags, const int32_t *warp, float scale, float *out, void *stream);
 
+/* The same batch from frames of DIFFERENT sizes (TORE's per-window bounding boxes; representations/gen1_transforms.py:51-67),
+ * in one launch, with the resize tap tables made on the device.
+ * evrep_resize_tap_tables: ONE launch fills the tap tables of n_axes axes.  axes DEVICE int32 [n_axes][6] = { src, dst,
+ *   interpolation (EVREP_TAPS_*), T, row offset, weight offset }: for every output index d < dst of the axis it writes
+ *   start[row offset + d], count[row offset + d] and the T float64 weights at weights[weight offset + d * T], zeros after the
+ *   first count.  The tables equal, bit for bit, the non-zero run of every row of OpenCV's published INTER_AREA / INTER_LINEAR
+ *   weight matrix in float64 as event_representation_study_amd/gwd_pipeline.py resize_taps builds it on the host (count 0 and
+ *   start 0 for a row without an entry); EVREP_TAPS_IDENTITY (src == dst) is one tap of weight 1 at d.  T is the caller's upper
+ *   bound on count (2 for LINEAR, ceil(src / dst) + 1 for AREA, 1 for IDENTITY; a larger T only pads).  start, count DEVICE int32
+ *   [n_rows], weights DEVICE double [n_wt]; max_dst >= every dst.  An axis with src, dst or T < 1 or an unknown interpolation,
+ *   and a run that would leave [0, n_rows) or [0, n_wt), is not written.  1 <= n_axes, 1 <= max_dst <= EVREP_MAX_DIM,
+ *   1 <= n_rows, n_wt < 2^31; anything else, a NULL or misaligned pointer is EVREP_EINVAL before the launch.
+ * evrep_detector_input_frames: what evrep_detector_input computes, sample b reading its own frame through its own tables.  frames
+ *   HOST [B]; per sample, with T the dtype of the frames:
+ *     R1 R1(y, x, c) = what evrep_resize_taps writes for the H x W frame at src with scale 1 and out_dtype T through the stage-1
+ *        tables (rows: rh entries from row1 with T1 weights each from wrow1; columns: rw entries from col1 / wcol1).
+ *     R  T2 == 0: R = R1 and nh x nw == rh x rw.  T2 > 0 (letterbox needs a resize of its own): R(y, x, c) = (T) sum over the y
+ *        taps of (sum over the x taps of (double)R1 * xw2) * yw2 through the stage-2 tables (nh entries from row2 / wrow2,
+ *        nw from col2 / wcol2, T2 weights each), tap rows and columns clamped to the rh x rw rectangle: what two passes of
+ *        evrep_resize_taps compute through an rh x rw image in memory; here no intermediate image exists.
+ *     L, W, F and the conversion as for evrep_detector_input with this sample's nh, nw, top, left and flags (EVREP_DETIN_*).
+ *   The entry point checks the whole table on the host -- rep_dtype; 1 <= B <= 65535; 1 <= C <= EVREP_MAX_CHANNELS; S, every H,
+ *   W, rh, rw, nh, nw, T1 in 1..EVREP_MAX_DIM, T2 in 0..EVREP_MAX_DIM; the nh x nw rectangle at top, left inside the square; every
+ *   offset >= 0 and offset + length inside n_rows / n_wt; src non-NULL and aligned to the element; no unknown flag bit; warp
+ *   DEVICE int32 [B,4,S] given exactly when some sample has EVREP_DETIN_WARP; a non-NaN scale; every other pointer non-NULL and
+ *   aligned -- and returns EVREP_EINVAL before any launch otherwise.  It then copies the table with one asynchronous copy on
+ *   `stream` into frames_dev (DEVICE, evrep_detector_input_frames_scratch_bytes(B) bytes, 8-byte aligned; the kernel reads that
+ *   copy, so `frames` may be reused when the call returns) and launches once.  start, count, weights DEVICE as
+ *   evrep_resize_tap_tables wrote them (ordered before this call on `stream`); pad DEVICE double [C]; out DEVICE float
+ *   [B,C,S,S], every element written exactly once.  Every index taken from a device table is brought into range before a
+ *   load.  Neither call allocates; neither waits for the device beyond what the runtime's copy from pageable host memory does
+ *   (pinned `frames` avoid that). */
+#define EVREP_TAPS_LINEAR 0
+#define EVREP_TAPS_AREA 1
+#define EVREP_TAPS_IDENTITY 2
+typedef struct evrep_detin_frame {
+    const void *src;              /* DEVICE [H,W,C], channel last */
+    int32_t H, W;
+    int32_t rh, rw, T1;           /* stage 1: H x W -> rh x rw */
+    int32_t row1, col1;           /* table rows of its rh row entries / rw column entries */
+    int32_t wrow1, wcol1;         /* where their weights start */
+    int32_t nh, nw, T2;           /* stage 2: rh x rw -> nh x nw, bilinear; T2 == 0: none */
+    int32_t row2, col2, wrow2, wcol2;
+    int32_t top, left;            /* the nh x nw rectangle in the S x S square */
+    uint32_t flags;               /* EVREP_DETIN_* */
+    int32_t reserved;             /* 0 */
+} evrep_detin_frame;              /* 88 bytes */
+int evrep_resize_tap_tables(const int32_t *axes, int32_t n_axes, int32_t max_dst, int32_t *start, int32_t *count, double *weights,
+                            int64_t n_rows, int64_t n_wt, void *stream);
+size_t evrep_detector_input_frames_scratch_bytes(int32_t B);
+int evrep_detector_input_frames(const evrep_detin_frame *frames, int32_t B, int32_t rep_dtype, int32_t C, int32_t S,
+                                const int32_t *start, const int32_t *count, const double *weights, int64_t n_rows, int64_t n_wt,
+                                const double *pad, const int32_t *warp, float scale, void *frames_dev, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
