@@ -106,7 +106,11 @@ SYMBOLS = {
     "evrep_resize_tap_tables": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp]),
     "evrep_detector_input_frames_scratch_bytes": (ctypes.c_size_t, [_i32]),
     "evrep_detector_input_frames": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp]),
+    "evrep_voxel_normalize_scratch_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32]),
+    "evrep_voxel_normalize": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
 }
+# evrep_voxel_normalize: flags
+VOXNORM_NORMALIZE = 1
 # evrep_time_index / evrep_sort_image: modes, per-window status bits (NO_INDEX << polarity class), flags, limits
 TIME_INDEX_RAW, TIME_INDEX_RANK = 0, 1
 SORT_EMPTY, SORT_DECREASING, SORT_NO_INDEX = 1, 2, 4

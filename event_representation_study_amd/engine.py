@@ -333,6 +333,25 @@ class EventBatch:
                   "evrep_voxel_subpixel")
         return out
 
+    def evl_voxel_grid(self, num_bins, normalize=True, t_range=None, xy=None, out=None, return_stats=False):
+        """ev-licious events_to_voxel_grid for every window -> (B, num_bins, H, W) float32, channel first, standardised over each
+        window's non-zero entries when `normalize` (utils.py:51-85; evrep_voxel_normalize).  xy=None: the integer-pixel grid
+        (voxel mode 2); xy = (total, 2) float64 device tensor of the original coordinates: the sub-pixel grid (voxel_subpixel).
+        return_stats: also the (B, 4) float64 device tensor {n, mean, std, applied} per window (needs normalize).  Nothing is
+        read back: the call stays on the batch's stream."""
+        _require_gpu()
+        bins = int(num_bins)
+        shape = (self.B, bins, self.H, self.W)
+        _check_evl_out(out, shape, self.device)           # before anything is launched
+        if return_stats and not normalize:
+            raise ValueError("the statistics come with the normalisation: return_stats needs normalize=True")
+        if xy is None:
+            grid = self.voxel(bins=bins, mode=2, t_range=t_range)
+        else:
+            grid = self.voxel_subpixel(xy, bins=bins, t_range=t_range)
+        with self._dev():
+            return voxel_normalize(grid, normalize=normalize, out=out, return_stats=return_stats, stream=self._sp())
+
     def polstats(self, tnorm, pol, stat, tau=0.3, out=None):
         """n_imagenet's per-polarity accumulators (imagenet.py:169-511): channel c = stat[c] over the events of
         polarity class pol[c] at each pixel.  tnorm: float64 device tensor, one normalised time per event."""
@@ -510,6 +529,41 @@ class EventBatch:
         out = EventBatch(ev_out[: int(off_host[-1])], off_host, self.H, self.W, plan_flags=int(self.plan.flags))
         out._pinned_stream = self._pinned_stream
         return out
+
+
+def _check_evl_out(out, shape, device):
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != torch.float32
+                            or not out.is_contiguous() or out.device != device):
+        raise ValueError("out must be a contiguous torch.float32 tensor of shape %r on %s" % (tuple(shape), device))
+
+
+def voxel_normalize(grid, normalize=True, out=None, return_stats=False, stream=None):
+    """evrep_voxel_normalize: a contiguous (B, H, W, bins) float64 / float32 device tensor of channel-last voxel grids ->
+    (B, bins, H, W) float32, each window standardised over its non-zero entries when `normalize` (ev-licious utils.py:77-83),
+    else only cast and transposed.  return_stats: also (B, 4) float64 {n, mean, std, applied}.  Three launches on the current
+    stream (`stream`: a stream pointer the caller has pinned), no read-back."""
+    _require_gpu()
+    lib = _lib.load()
+    if not isinstance(grid, torch.Tensor) or not grid.is_cuda or grid.dim() != 4 or not grid.is_contiguous():
+        raise ValueError("grid must be a contiguous (B, H, W, bins) CUDA tensor")
+    B, H, W, bins = (int(v) for v in grid.shape)
+    _check_evl_out(out, (B, bins, H, W), grid.device)
+    if return_stats and not normalize:
+        raise ValueError("the statistics come with the normalisation: return_stats needs normalize=True")
+    dt = EventBatch._dt(grid.dtype)
+    if out is None:
+        out = torch.empty((B, bins, H, W), dtype=torch.float32, device=grid.device)
+    stats = torch.empty((B, 4), dtype=torch.float64, device=grid.device) if return_stats else None
+    null = ctypes.c_void_p(None)
+    scratch = None
+    if normalize:
+        scratch = torch.empty(max(int(lib.evrep_voxel_normalize_scratch_bytes(B, H, W, bins)), 16), dtype=torch.uint8,
+                              device=grid.device)
+    with torch.cuda.device(grid.device) if stream is None else _NO_GUARD:
+        check(lib.evrep_voxel_normalize(_ptr(grid), dt, B, H, W, bins, _lib.VOXNORM_NORMALIZE if normalize else 0, _ptr(out),
+                                        _ptr(stats) if return_stats else null, _ptr(scratch) if normalize else null,
+                                        _stream_ptr() if stream is None else stream), "evrep_voxel_normalize")
+    return (out, stats) if return_stats else out
 
 
 def est_prepare(events5, B, H, W):

@@ -214,7 +214,7 @@ int evrep_tore_ftime(const evrep_plan *plan, const int32_t *events, const int64_
  * mode 0.  mode 1 = tonic.transforms.ToVoxelGrid as gen1_transforms.py:22-25 consumes it
  * (restated from tonic's published algorithm; parity unpinned).  mode 2 = ev-licious
  * events_to_voxel_grid, integer-pixel path (ev-licious/src/evlicious/tools/utils.py:52-108), before
- * its optional normalisation.  out DEVICE (B,H,W,bins) float64.
+ * its optional normalisation (evrep_voxel_normalize applies it to the whole batch).  out DEVICE (B,H,W,bins) float64.
  * `scale` (here and in evrep_voxel_range / evrep_voxel_tnorm): the finished float64 sum of a (pixel, bin) cell times `scale`,
  * once, at the pixels that hold an event; a pixel without events stays +0 whatever the sign of scale. */
 int evrep_voxel(const evrep_plan *plan, const int32_t *events, const int64_t *offsets, void *workspace,
@@ -230,7 +230,7 @@ int evrep_voxel_range(const evrep_plan *plan, const int32_t *events, const int64
  * bilinear-in-x/y draw of every event into its four surrounding pixels, float32 accumulation in the reference's
  * order.  `events` carries the TRUNCATED coordinates (x.astype("int32"), :92-93), xy DEVICE double [total,2] the
  * original (x, y) of every event (indexed like `events`); t_range as evrep_voxel_range.
- * out DEVICE float32 (B,H,W,bins), before the optional normalisation. */
+ * out DEVICE float32 (B,H,W,bins), before the optional normalisation (evrep_voxel_normalize). */
 /* compute_repr(x, y, t, p, width, height, bins) itself (representation_search/gromov_wasserstein.py:72-82): the caller hands
  * its own normalised time per event -- tnorm DEVICE double [total_events], indexed like `events`, used exactly as the
  * reference uses `t`: b = (bins - 1) * t, blim in {int(b), int(b) + 1}, grid[y, x, blim] += (1 - |blim - b|) * p, lower
@@ -240,6 +240,28 @@ int evrep_voxel_tnorm(const evrep_plan *plan, const int32_t *events, const int64
 
 int evrep_voxel_subpixel(const evrep_plan *plan, const int32_t *events, const int64_t *offsets, void *workspace,
                          const double *xy, int32_t bins, const int64_t *t_range, float *out, void *stream);
+
+/* The rest of ev-licious events_to_voxel_grid for a whole batch (utils.py:56,77-83, the numpy variant): the channel-last grids
+ * that evrep_voxel_range (mode 2, float64) or evrep_voxel_subpixel (float32) wrote become the channel-first float32 tensor
+ * the reference returns, standardised over each window's non-zero entries.
+ * grid DEVICE (B,H,W,bins) float64 / float32 (grid_dtype); out DEVICE float (B,bins,H,W), every element written exactly once.
+ * Without EVREP_VOXNORM_NORMALIZE: out[b,c,y,x] = (float)grid[b,y,x,c], bit for bit, in one launch; scratch is not used and
+ * stats_out must be NULL.  With it, per window and with v = (float)grid value, every sum, mean, std and the quotient in float64
+ * and no multiply fused with an add:
+ *     n = #{v != 0};  mean = (sum over v != 0 of v) / n;  std = sqrt((sum over v != 0 of (v - mean)^2) / n)   (two passes)
+ *     n > 0 and std > 0:  out = (float)(((double)v - mean) / (1e-5 + std)) where v != 0, +0 elsewhere;
+ *     otherwise the window is written un-normalised, as without the flag.
+ * stats_out DEVICE double [B][4] = { n, mean, std, applied (1 or 0) } or NULL; mean = std = 0 for n = 0.
+ * Reproducible bit for bit: nothing is added atomically, a window is summed in slices that depend on (H, W, bins, grid_dtype)
+ * alone and the partial sums are combined in slice order, so two calls agree, and a window gives the same bits alone and at
+ * any place of any batch.  Three launches; does not allocate, reads nothing back, does not wait for the device.
+ * 1 <= B <= 65535, H, W >= 1, 1 <= bins <= EVREP_MAX_CHANNELS, H * W * bins < 2^31; grid, out, scratch (DEVICE,
+ * evrep_voxel_normalize_scratch_bytes(B, H, W, bins) bytes; 0 for sizes the call refuses) and stats_out 16-byte aligned.
+ * Anything else, a NULL pointer, an unknown dtype or flag bit is EVREP_EINVAL before any launch. */
+#define EVREP_VOXNORM_NORMALIZE 1u
+size_t evrep_voxel_normalize_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t bins);
+int evrep_voxel_normalize(const void *grid, int32_t grid_dtype, int32_t B, int32_t H, int32_t W, int32_t bins, uint32_t flags,
+                          float *out, double *stats_out, void *scratch, void *stream);
 
 /* n_imagenet's per-polarity accumulators (n_imagenet/real_cnn_model/data/imagenet.py:169-511,841-871:
  * reshape_then_acc, _acc_time, _acc_count, _acc_count_pol, _acc_count_only, _acc_all, _flat, _flat_pol,
