@@ -108,7 +108,17 @@ SYMBOLS = {
     "evrep_detector_input_frames": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp]),
     "evrep_voxel_normalize_scratch_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32]),
     "evrep_voxel_normalize": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
+    "evrep_decode_scratch_bytes": (ctypes.c_size_t, [_i64]),
+    "evrep_decode_state_init": (ctypes.c_int, [_vp, _vp]),
+    "evrep_decode_dat": (ctypes.c_int, [_vp, _i64, _i32, _i64, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "evrep_decode_bin5": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "evrep_dat_seek_time": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp]),
 }
+# evrep_decode_dat / evrep_decode_bin5: modes, the overrun bit of the state's n_in, the fields of the state, the largest n
+DECODE_STRICT, DECODE_DROP_OOB = 0, 1
+DECODE_N_IN_OVERRUN = 1 << 62
+DECODE_STATE_FIELDS = ("n_in", "n_out", "oob_count", "oob_first", "desc_count", "desc_first", "t_first", "t_last")
+DECODE_MAX_N = 1 << 30
 # evrep_voxel_normalize: flags
 VOXNORM_NORMALIZE = 1
 # evrep_time_index / evrep_sort_image: modes, per-window status bits (NO_INDEX << polarity class), flags, limits

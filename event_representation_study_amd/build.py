@@ -8,23 +8,24 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libevrep.so")
-# thirteen translation units, compiled in parallel and linked into one .so (r05; a unity build until then: four minutes)
+# fourteen translation units, compiled in parallel and linked into one .so (r05; a unity build until then: four minutes)
 SOURCES = ["evrep_capi.hip", "evrep_capi_mdes.hip", "evrep_capi_builders.hip", "evrep_capi_gwd.hip", "evrep_capi_filters.hip",
            "evrep_capi_windows.hip", "evrep_capi_augment.hip", "evrep_capi_dist.hip", "evrep_capi_sort.hip", "evrep_est_bwd.hip",
-           "evrep_est_prep.hip", "evrep_capi_detin.hip", "evrep_capi_voxnorm.hip"]
+           "evrep_est_prep.hip", "evrep_capi_detin.hip", "evrep_capi_voxnorm.hip", "evrep_capi_decode.hip"]
 _BIN = ["evrep_bin.hip", "evrep_common.h", "evrep_capi_shared.h"]
 _BLD = _BIN + ["evrep_builders.hip", "evrep_capi_builders.h", "evrep_est_table.h"]
 UNIT_DEPS = {"evrep_capi.hip": _BIN, "evrep_capi_mdes.hip": _BLD, "evrep_capi_builders.hip": _BLD,
              "evrep_capi_gwd.hip": ["evrep_gwd.hip", "evrep_otmi.hip", "evrep_gw.hip", "evrep_common.h", "evrep_capi_shared.h"],
              "evrep_capi_filters.hip": ["evrep_filters.hip", "evrep_common.h", "evrep_capi_shared.h"],
-             "evrep_capi_windows.hip": ["evrep_windows.hip", "evrep_common.h", "evrep_capi_shared.h"],
+             "evrep_capi_windows.hip": ["evrep_windows.hip", "evrep_wave_search.h", "evrep_common.h", "evrep_capi_shared.h"],
              "evrep_capi_augment.hip": ["evrep_augment.hip", "evrep_common.h", "evrep_capi_shared.h"],
              "evrep_capi_dist.hip": ["evrep_dist.hip", "evrep_ranksort.h", "evrep_common.h", "evrep_capi_shared.h"],
              "evrep_capi_sort.hip": ["evrep_sort.hip", "evrep_ranksort.h", "evrep_common.h", "evrep_capi_shared.h"],
              "evrep_est_bwd.hip": ["evrep_est_table.h", "evrep_common.h", "evrep_capi_shared.h"],
              "evrep_est_prep.hip": ["evrep_common.h", "evrep_capi_shared.h"],
              "evrep_capi_detin.hip": ["evrep_detin.hip", "evrep_detin_frames.hip", "evrep_common.h", "evrep_capi_shared.h"],
-             "evrep_capi_voxnorm.hip": ["evrep_voxnorm.hip", "evrep_common.h", "evrep_capi_shared.h"]}
+             "evrep_capi_voxnorm.hip": ["evrep_voxnorm.hip", "evrep_common.h", "evrep_capi_shared.h"],
+             "evrep_capi_decode.hip": ["evrep_decode.hip", "evrep_wave_search.h", "evrep_common.h", "evrep_capi_shared.h"]}
 OBJDIR = os.path.join(PKG, "_obj")
 
 # -ffp-contract=off: the parity contract is bit-exactness with the reference's separate

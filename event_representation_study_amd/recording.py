@@ -17,8 +17,16 @@ Queries.  The reference searches ``np.searchsorted(t, q + 1e-3)`` in float64.  T
 first ``t >= q + 1e-3`` is the first ``t > ceil(q + 1e-3) - 1``: the host forms that integer (``query_to_int``) and the device
 compares integers.  The two agree wherever float64 still resolves 1e-3 next to the query, |q| < 2**43 us (three months);
 beyond it ``ValueError`` is raised instead of an answer that could differ.
+
+Raw files.  ``DeviceRecording.from_dat`` and ``from_bin`` upload the payload of a Prophesee ``*_td.dat`` file (8 or 28 bytes per
+record) or of an N-Caltech / N-MNIST ``.bin`` file (5 bytes per record) as it lies on disk and decode it on the device
+(``evrep_decode_dat`` / ``evrep_decode_bin5``); ``load_events_from_path`` dispatches on the suffix as
+``evlicious.io.load_events_from_path`` does.  ``DatDeviceRecording`` answers ``get_between_idx``, ``get_between_time`` and
+``seek_time`` as the reference's ``DatEventHandle`` does (``dat_seek_index`` states the seek in numpy).
 """
 import ctypes
+import os
+import pathlib
 
 import numpy as np
 import torch
@@ -96,9 +104,137 @@ def _column(values, dtype, name):
     return np.ascontiguousarray(v.astype(dtype))
 
 
+DAT_EVENT_SIZES = {0: 8, 12: 8, 40: 28}           # prophesee_utils.EV_TYPES: bytes per record of the event types the reference reads
+DAT_SEEK_TERM = 100000                             # EventBaseReader.seek_time's default term_criterion
+
+
+def parse_dat_header(path):
+    """prophesee_utils.parse_header (io/utils/prophesee_utils.py:64-121) -> (payload_offset, ev_type, ev_size, (height, width)).
+
+    The header is the leading lines that start with "% "; ``% Height h`` and ``% Width w`` give the sensor size (None where a
+    line is missing; ``ValueError`` for such a line without a value, where the reference ends in an ``IndexError``).  Behind a
+    header come one byte of event type and one of event size; a file without a header is type 0 with 8-byte records from its
+    first byte.  ``ValueError`` where the file ends inside the two bytes."""
+    size = [None, None]
+    with open(str(path), "rb") as f:
+        lines = 0
+        while True:
+            bod = f.tell()
+            line = f.readline()
+            if line[:2] != b"% ":
+                break
+            words = line.split()
+            if len(words) > 1 and words[1] in (b"Height", b"Width"):
+                if len(words) < 3:
+                    raise ValueError("%s: the header's %s line holds no value" % (path, words[1].decode()))
+                size[words[1] == b"Width"] = int(words[2])
+            lines += 1
+        if lines == 0:
+            return 0, 0, 8, (None, None)
+        f.seek(bod)
+        two = f.read(2)
+        if len(two) != 2:
+            raise ValueError("%s: the file ends inside its header" % (path,))
+        return bod + 2, int(two[0]), int(two[1]), (size[0], size[1])
+
+
+def dat_seek_index(t_host, q, term=DAT_SEEK_TERM):
+    """EventBaseReader.seek_time(q, term) (prophesee_utils.py:367-418) on an ascending host column, in numpy: the record index
+    the reader stands at afterwards.  What ``evrep_dat_seek_time`` computes; a scalar for a scalar, int64 array for an array.
+
+    q above the last timestamp gives n and q <= 0 gives 0.  Otherwise [0, n) is bisected while more than ``term`` records
+    remain, and a probe that EQUALS q ends the search at middle + 1 -- the reader has consumed the probed record, which need
+    not be the first with that timestamp.  The remaining range gives its first record with t >= q.  A query is truncated
+    towards zero, as ``int(expected_time)``."""
+    t = np.asarray(t_host)
+    n = len(t)
+    qs = np.trunc(np.asarray(q, dtype=np.float64)).astype(np.int64) if np.asarray(q).dtype.kind == "f" else np.asarray(q, dtype=np.int64)
+    out = np.empty(qs.shape, np.int64)
+    for k, v in enumerate(qs.reshape(-1)):
+        v = int(v)
+        if n == 0 or v <= 0:
+            res = 0
+        elif v > int(t[n - 1]):
+            res = n
+        else:
+            low, high, res = 0, n, -1
+            while high - low > term:
+                middle = (low + high) // 2
+                m = int(t[middle])
+                if m > v:
+                    high = middle
+                elif m < v:
+                    low = middle + 1
+                else:
+                    res = middle + 1
+                    break
+            if res < 0:
+                res = low + int(np.searchsorted(t[low:high], v, side="left"))
+        out.reshape(-1)[k] = res
+    return out if out.ndim else out[()]
+
+
+def dat_between_idx_rows(n, i0, i1):
+    """The rows [a, e) DatEventHandle.get_between_idx(i0, i1) returns of n records: seek_event clips i0 into [0, n] and
+    load_n_events reads i1 - i0 records or what is left.  i1 < i0 raises what the reference raises: ``ValueError`` (np.empty
+    of a negative length), but ``IndexError`` for i1 == i0 - 1 (the buffer of i1 - i0 + 1 == 0 records is indexed)."""
+    i0, i1 = int(i0), int(i1)
+    if i1 == i0 - 1:
+        raise IndexError("get_between_idx(%d, %d): i1 == i0 - 1" % (i0, i1))
+    if i1 < i0:
+        raise ValueError("get_between_idx(%d, %d): i1 < i0" % (i0, i1))
+    a = min(max(i0, 0), n)
+    return a, min(a + (i1 - i0), n)
+
+
+def dat_between_time_rows(n, t0_us, t1_us, seek, lower_bound):
+    """The rows [a, e) DatEventHandle.get_between_time(t0_us, t1_us) returns: ``seek(q)`` is the reader's seek_time,
+    ``lower_bound(q)`` the first index with t >= q.  The reader seeks to t0 first and load_delta_t(t1 - t0) then refuses a
+    delta below 1 us (``ValueError`` with its text).  For t0 <= 0 the reader's clock is reset to 0, NOT to t0, so the end is
+    the first t >= t1 - t0; a t0 beyond the last timestamp leaves the reader done: an empty window."""
+    t0, t1 = int(t0_us), int(t1_us)
+    delta = int(t1_us - t0_us)
+    if delta < 1:
+        raise ValueError("load_delta_t(): Delta_t must be at least 1 micro-second: {}".format(delta))
+    s = int(seek(t0))
+    if s >= n:
+        return n, n
+    if t0 <= 0:
+        return s, max(s, int(lower_bound(delta)))
+    return s, max(s, int(lower_bound(t0 + delta)))
+
+
+def load_events_from_path(path, height=None, width=None, divider=1, device="cuda:0"):
+    """evlicious.io.load_events_from_path (ev-licious/src/evlicious/io/__init__.py:18-35) for the device: ``.h5`` ->
+    ``DeviceRecording.from_h5``, ``.dat`` -> ``from_dat`` (height / width serve a header without a size), ``.bin`` ->
+    ``from_bin``.  A ``.bag`` and a directory of ``.npy`` / ``.npz`` files raise ``NotImplementedError``; anything else
+    ``ValueError``, as the reference."""
+    path = pathlib.Path(path)
+    if int(divider) != 1:
+        raise ValueError("divider %r: sub-pixel coordinates do not fit the int32 event rows" % (divider,))
+    if path.suffix == ".h5":
+        return DeviceRecording.from_h5(path, device=device)
+    if path.suffix == ".dat":
+        return DeviceRecording.from_dat(path, height=height, width=width, device=device)
+    if path.suffix == ".bag":
+        raise NotImplementedError("%s: rosbags need the ROS Python API, which this package does not depend on" % path)
+    if path.suffix == ".bin":
+        if height is None or width is None:
+            raise ValueError("%s: a .bin file names no sensor size; pass height and width" % path)
+        return DeviceRecording.from_bin(path, height, width, device=device)
+    if path.is_dir():
+        raise NotImplementedError("%s: the reference's NPY / NPZ directory handles search t0_us for BOTH ends of get_between_time "
+                                  "(npy_event_handle.py:67-68, npz_event_handle.py:82-83): there is no meaningful result to "
+                                  "reproduce" % path)
+    raise ValueError("%s: neither .h5, .dat, .bin, .bag nor a directory" % path)
+
+
 class DeviceRecording:
     """One recording in HBM: x, y uint16, t int64 (ascending), p int8 of n events on an H x W sensor.  ``divider > 1`` (sub-pixel
     coordinates, x / divider) does not fit the int32 row layout of the engine and raises ``ValueError``."""
+
+    _desc_first = -1        # a decoded file: the index of the first record whose t is smaller than its predecessor's
+    decode_state = None     # a decoded file: the fields of evrep_decode_state as a dict
 
     def __init__(self, x, y, t, p, height, width, divider=1, device="cuda:0"):
         if int(divider) != 1:
@@ -141,6 +277,112 @@ class DeviceRecording:
         rec.n, rec._limits = int(rec.t.numel()), None
         return rec
 
+    # ------------------------------------------------------------------ raw files
+    @classmethod
+    def from_dat(cls, path, height=None, width=None, device="cuda:0", out_of_bounds="raise", chunk_events=1 << 24):
+        """A Prophesee DAT file (event types 0, 12 and 40) decoded on the device -> ``DatDeviceRecording``.  The sensor size is
+        the header's; ``height`` / ``width`` serve a header without one (``ValueError`` if neither gives it, and for an event size
+        in the header that is not the size of the event type's records).  A trailing
+        partial record is ignored, as the reference's ``(end - start) // ev_size`` ignores it.  See ``_from_raw``."""
+        offset, ev_type, ev_size, (h, w) = parse_dat_header(path)
+        if ev_type not in DAT_EVENT_SIZES:
+            raise ValueError("%s: event type %d is none of %s" % (path, ev_type, sorted(DAT_EVENT_SIZES)))
+        if ev_size != DAT_EVENT_SIZES[ev_type]:      # (the reference would count records by one size and read them by the other)
+            raise ValueError("%s: event size %d in the header, but records of type %d hold %d bytes"
+                             % (path, ev_size, ev_type, DAT_EVENT_SIZES[ev_type]))
+        h, w = (height if h is None else h), (width if w is None else w)
+        if h is None or w is None:
+            raise ValueError("%s: the header names no sensor size; pass height and width" % (path,))
+        n = (os.path.getsize(str(path)) - offset) // ev_size
+        return DatDeviceRecording._from_raw("dat", path, offset, n, ev_size, h, w, device, out_of_bounds, chunk_events)
+
+    @classmethod
+    def from_bin(cls, path, height, width, device="cuda:0", out_of_bounds="raise", chunk_events=1 << 24):
+        """An N-Caltech / N-MNIST file of 5-byte records decoded on the device.  ``ValueError`` for a length that is no
+        multiple of 5 (the reference's ``np.column_stack`` fails there).  See ``_from_raw``."""
+        size = os.path.getsize(str(path))
+        if size % 5:
+            raise ValueError("%s: %d bytes are no whole number of 5-byte records" % (path, size))
+        return DeviceRecording._from_raw("bin", path, 0, size // 5, 5, height, width, device, out_of_bounds, chunk_events)
+
+    @classmethod
+    def _from_raw(cls, fmt, path, offset, n, rec_bytes, height, width, device, out_of_bounds, chunk_events):
+        """Upload n records of rec_bytes bytes behind ``offset`` in chunks of ``chunk_events`` and decode them where they land.
+
+        A chunk is read from the file into one of two pinned staging buffers and copied to the device on the current stream;
+        the decode call follows it there and accumulates into the 64-byte ``evrep_decode_state``.  The host waits only for the
+        COPY of the chunk before last, to reuse its staging buffer -- never for a decode -- and reads the state back once, at
+        the end.  out_of_bounds: "raise" -- ``ValueError`` naming the first record with x >= width or y >= height and their
+        count (ev-licious' ``Events.__init__`` assertion, once, at load time); "drop" -- those records are left out and the
+        others keep their order (the mask of ev-YOLOv6/yolov6/data/gen4/dataset.py:109-112).  A file whose timestamps descend
+        somewhere is loaded; its time queries raise (``_require_ascending``).  The columns are views of ``n_out`` entries;
+        ``decode_state`` holds the state's fields."""
+        if out_of_bounds not in ("raise", "drop"):
+            raise ValueError("out_of_bounds must be 'raise' or 'drop'")
+        chunk_events = int(chunk_events)
+        if not 1 <= chunk_events <= _lib.DECODE_MAX_N:
+            raise ValueError("chunk_events must lie in 1 .. %d" % _lib.DECODE_MAX_N)
+        height, width = int(height), int(width)
+        if height < 1 or width < 1:
+            raise ValueError("the sensor size must be positive")
+        _require_gpu()
+        rec = cls.__new__(cls)
+        rec.lib, rec.device = _lib.load(), torch.device(device)
+        rec.height, rec.width, rec.divider = height, width, 1
+        lib, dev = rec.lib, rec.device
+        flags = _lib.DECODE_DROP_OOB if out_of_bounds == "drop" else _lib.DECODE_STRICT
+        cols = [torch.empty(n, dtype=d, device=dev) for d in (torch.uint16, torch.uint16, torch.int64, torch.int8)]
+        state = torch.empty(len(_lib.DECODE_STATE_FIELDS), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.evrep_decode_state_init(_ptr(state), _stream_ptr()), "evrep_decode_state_init")
+            if n:
+                scratch = torch.empty(lib.evrep_decode_scratch_bytes(min(n, chunk_events)), dtype=torch.uint8, device=dev)
+                room = (min(n, chunk_events) * rec_bytes + 15) // 16 * 16        # whole 16-byte pieces: the kernels read those
+                pinned = [torch.empty(room, dtype=torch.uint8).pin_memory() for _ in range(2)]
+                staged = [torch.empty(room, dtype=torch.uint8, device=dev) for _ in range(2)]
+                copied = [torch.cuda.Event() for _ in range(2)]
+                with open(str(path), "rb") as f:
+                    f.seek(offset)
+                    for k, first in enumerate(range(0, n, chunk_events)):
+                        m, b = min(chunk_events, n - first), k & 1
+                        nbytes = m * rec_bytes
+                        if k >= 2:
+                            copied[b].synchronize()
+                        if f.readinto(memoryview(pinned[b].numpy())[:nbytes]) != nbytes:
+                            raise IOError("%s: short read" % (path,))
+                        padded = (nbytes + 15) // 16 * 16
+                        staged[b][:padded].copy_(pinned[b][:padded], non_blocking=True)
+                        copied[b].record()
+                        args = (first, height, width, flags, _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(cols[3]), n,
+                                _ptr(state), _ptr(scratch), _stream_ptr())
+                        if fmt == "dat":
+                            check(lib.evrep_decode_dat(_ptr(staged[b]), m, rec_bytes, *args), "evrep_decode_dat")
+                        else:
+                            check(lib.evrep_decode_bin5(_ptr(staged[b]), m, *args), "evrep_decode_bin5")
+            st = dict(zip(_lib.DECODE_STATE_FIELDS, (int(v) for v in state.cpu().numpy())))      # the one read-back
+        if st["n_in"] != n:
+            raise _lib.EvrepError("decode of %s: state %r after %d records" % (path, st, n))
+        rec.decode_state = st
+        if st["oob_count"] and out_of_bounds == "raise":
+            raise ValueError("%s: %d of %d records lie outside the %d x %d (height x width) sensor, the first at index %d"
+                             % (path, st["oob_count"], n, height, width, st["oob_first"]))
+        rec.n = st["n_out"]
+        rec.x, rec.y, rec.t, rec.p = (c[:rec.n] for c in cols)
+        rec._desc_first = st["desc_first"]
+        if rec.n == 0:
+            rec._limits = None
+        elif rec.n == n:
+            rec._limits = (np.int64(st["t_first"]), np.int64(st["t_last"]))
+        else:       # records were dropped: the state's limits are those of the RAW records, the first or last may be gone
+            ends = rec.t[[0, -1]].cpu().numpy()
+            rec._limits = (ends[0], ends[1])
+        return rec
+
+    def _require_ascending(self):
+        if self._desc_first >= 0:
+            raise ValueError("the timestamps of this recording descend at record %d (a clock that wrapped is not unwrapped): "
+                             "it answers index cuts only, no time query" % self._desc_first)
+
     # ------------------------------------------------------------------ the reference's names
     def __len__(self):
         return self.n
@@ -159,6 +401,7 @@ class DeviceRecording:
 
     def _search_device(self, k):
         """first index with t > k for an int64 host array k -> int64 DEVICE tensor: ONE evrep_time_to_index call."""
+        self._require_ascending()
         k = np.ascontiguousarray(k, dtype=np.int64).reshape(-1)
         out = torch.empty(k.size, dtype=torch.int64, device=self.device)
         if k.size:
@@ -274,3 +517,39 @@ class DeviceRecording:
         a, e = iterator_pairs(i0, i1)
         for k in range(0, len(a), int(batch_size)):
             yield self.windows(a[k:k + batch_size], e[k:k + batch_size], rebase="first")
+
+
+class DatDeviceRecording(DeviceRecording):
+    """What ``DeviceRecording.from_dat`` returns: the recording of a DAT file with ``DatEventHandle``'s semantics
+    (ev-licious/src/evlicious/io/dat_event_handle.py) under the reference's names -- ``get_between_idx`` and
+    ``get_between_time`` follow the reader (``dat_between_idx_rows``, ``dat_between_time_rows``, ``dat_seek_index``), not the
+    slices and the ``+ 1e-3`` search of the H5 handle.  ``compute_time_and_index_windows`` and ``iterator`` keep the H5 handle's
+    arithmetic of the base class: ``DatEventHandle`` itself has none (its base raises ``NotImplemented``)."""
+
+    def seek_time_index(self, t_us, term=DAT_SEEK_TERM):
+        """``EventBaseReader.seek_time`` for one query or an array of them, searched on the device in ONE evrep_dat_seek_time
+        call -> the record index the reader stands at: a numpy integer for a scalar, an int64 array for an array."""
+        self._require_ascending()
+        q = np.asarray(t_us)
+        q = np.trunc(q.astype(np.float64)).astype(np.int64) if q.dtype.kind == "f" else q.astype(np.int64)
+        flat = np.ascontiguousarray(q.reshape(-1))
+        out = torch.empty(flat.size, dtype=torch.int64, device=self.device)
+        if flat.size:
+            d_q = torch.from_numpy(flat).to(self.device)
+            with torch.cuda.device(self.device):
+                check(self.lib.evrep_dat_seek_time(_ptr(self.t), self.n, _ptr(d_q), flat.size, int(term), _ptr(out), _stream_ptr()),
+                      "evrep_dat_seek_time")
+        idx = out.cpu().numpy().reshape(q.shape)
+        return idx if q.ndim else idx[()]
+
+    def _lower_bound(self, q):
+        """The first index with t >= q: the first with t > q - 1."""
+        return int(self._search_device(np.array([int(q) - 1], np.int64)).cpu()[0])
+
+    def get_between_idx(self, i0, i1, rebase="first"):
+        a, e = dat_between_idx_rows(self.n, i0, i1)
+        return self.windows([a], [e], rebase=rebase)
+
+    def get_between_time(self, t0_us, t1_us, rebase="first"):
+        a, e = dat_between_time_rows(self.n, t0_us, t1_us, self.seek_time_index, self._lower_bound)
+        return self.windows([a], [e], rebase=rebase)

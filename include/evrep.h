@@ -515,6 +515,52 @@ int evrep_windows_gather(const uint16_t *x, const uint16_t *y, const int64_t *t,
                          const int64_t *i1, const int64_t *dst_offsets, int32_t B, int32_t rebase_mode, const int64_t *base_in,
                          int32_t *events_out, int64_t *base_out, uint32_t *status_out, void *stream);
 
+/* Raw event files decoded on the device into the columns of a recording (x, y uint16, t int64, p int8): Prophesee DAT
+ * records (ev-licious/src/evlicious/io/utils/prophesee_utils.py:8-61: a uint32 timestamp and a uint32 word holding x in bits
+ * 0-13, y in bits 14-27, p in bit 28, bits 29-31 ignored; 8 bytes for event types 0 and 12, 28 for type 40, whose further
+ * fields are skipped) and the 5-byte records of N-Caltech / N-MNIST (io/bin_event_handle.py:37-51: x = b0, y = b1, p = bit 7
+ * of b2, t = (b2 & 127) << 16 | b3 << 8 | b4).  p is +1 where the bit is set and -1 otherwise; t is zero-extended, never
+ * negative.  No call allocates or waits for the device; every result of the checks stays on the device.
+ *
+ * evrep_decode_state: eight int64 fields a FILE accumulates over the calls that decode its chunks, one behind the other on
+ *   one stream.  n_in: records seen (bit EVREP_DECODE_N_IN_OVERRUN: some call found n_out + its records > capacity; that
+ *   call and every later one write nothing and leave n_out as it is, the checks still run).  n_out: records written; a call
+ *   writes its columns at [n_out, ...).  oob_count / oob_first: records with x >= W or y >= H, and the file index of the
+ *   first (-1: none).  desc_count / desc_first: records whose t is smaller than their predecessor's in the RAW record order,
+ *   across chunk joints too, and the file index of the first (-1: none).  t_first, t_last: t of the first and of the last
+ *   RAW record (-1: no record yet).  evrep_decode_state_init starts a file (one launch).
+ * evrep_decode_dat: n records of `stride` bytes (a multiple of 4, >= 8) at raw, DEVICE, 16-byte aligned.  first_index: the
+ *   index record 0 has in the file (oob_first and desc_first are file indices).  x, y, t, p DEVICE, 16-byte aligned,
+ *   `capacity` entries each.  flags: EVREP_DECODE_STRICT -- every record is written, out-of-frame ones are counted only;
+ *   EVREP_DECODE_DROP_OOB -- out-of-frame records are left out, the others keep their order (a count launch, one scan
+ *   workgroup, a write launch; with nothing dropped the columns equal the strict ones).  scratch DEVICE, 256-byte aligned,
+ *   evrep_decode_scratch_bytes(n) bytes, needed by DROP_OOB only (NULL otherwise); it is free again when the call's
+ *   launches have run.  n <= EVREP_DECODE_MAX_N.  With stride 8 a lane decodes 16 records whose output index starts at a
+ *   multiple of 16: 16-byte loads (8-byte where n_out is odd) and 16-byte stores of every column.
+ * evrep_decode_bin5: the same for 5-byte records.  raw must be readable up to the next multiple of 16 bytes behind the last
+ *   record: the payload is read in whole aligned 16-byte pieces.
+ * evrep_dat_seek_time: EventBaseReader.seek_time(queries[k], term) (prophesee_utils.py:367-418) on the ascending t DEVICE
+ *   int64 [n] -> out_idx[k], the reader's record position: n for a query above t[n-1], 0 for a query <= 0; otherwise bisect
+ *   [0, n) while more than `term` records remain -- a probe t[middle] EQUAL to the query ends at middle + 1, which need not be
+ *   the first record with that timestamp -- and then take the first record of the remaining range with t >= query.  One
+ *   wavefront per query.  term >= 1, nq <= EVREP_WINDOWS_MAX_QUERIES. */
+typedef struct evrep_decode_state {
+    int64_t n_in, n_out, oob_count, oob_first, desc_count, desc_first, t_first, t_last;
+} evrep_decode_state;
+#define EVREP_DECODE_STRICT 0u
+#define EVREP_DECODE_DROP_OOB 1u
+#define EVREP_DECODE_N_IN_OVERRUN (1ll << 62)
+#define EVREP_DECODE_MAX_N (1ll << 30)
+size_t evrep_decode_scratch_bytes(int64_t n);
+int evrep_decode_state_init(evrep_decode_state *state, void *stream);
+int evrep_decode_dat(const void *raw, int64_t n, int32_t stride, int64_t first_index, int32_t H, int32_t W, uint32_t flags,
+                     uint16_t *x, uint16_t *y, int64_t *t, int8_t *p, int64_t capacity, evrep_decode_state *state, void *scratch,
+                     void *stream);
+int evrep_decode_bin5(const void *raw, int64_t n, int64_t first_index, int32_t H, int32_t W, uint32_t flags, uint16_t *x,
+                      uint16_t *y, int64_t *t, int8_t *p, int64_t capacity, evrep_decode_state *state, void *scratch, void *stream);
+int evrep_dat_seek_time(const int64_t *t, int64_t n, const int64_t *queries, int64_t nq, int64_t term, int64_t *out_idx,
+                        void *stream);
+
 /* N-ImageNet's event front end and base_augment on the device (n_imagenet/real_cnn_model/data/imagenet.py: load_event :30-57,
  * reshape_event_no_sample :104-108, slice_event :60-84, base_augment("train") :1140-1187), for the B windows of a batch in one
  * call: a count launch, one scan workgroup, a write launch.  The call takes no plan and no workspace, neither allocates nor
