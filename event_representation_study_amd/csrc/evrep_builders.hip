@@ -1104,7 +1104,9 @@ __device__ inline UnitRecs unit_records(const BinView &bv, const int64_t *__rest
         uint32_t splitmask = 0u;   // parts beyond a HOT wave's stage (tile + kHotStage records): deferred as quarters
         for (int o0 = 0; o0 < npix_out; o0 += kWave) {
             const int lo = o0 + dpx, hi = min(o0 + kWave, npix_out) + dpx;
-            const uint32_t b0 = lo < npixu ? cnt[lo] : nrec, b1 = hi < npixu ? cnt[hi] : nrec;
+            // (dpx < 0: TORE's frame origin lies left of sensor column 0 -- an out-of-frame event with a negative x; the output
+            //  pixels in front of unit pixel 0 hold nothing)
+            const uint32_t b0 = lo <= 0 ? 0u : (lo < npixu ? cnt[lo] : nrec), b1 = hi <= 0 ? 0u : (hi < npixu ? cnt[hi] : nrec);
             fits = fits && b1 - b0 <= (uint32_t)(EVREP_DEFER_MULT * w.bigcap);
             if (b1 - b0 > (uint32_t)(w.bigcap - w.nstage + kHotStage)) splitmask |= 1u << (o0 / kWave);
         }
@@ -1647,7 +1649,7 @@ __device__ inline void emit_warm(const UnitRecs &u, uint32_t nrec, Digest digest
         const int np = min(kWave, npix - p * kWave);
         const int px = p * kWave + u.dpx + lane;
         uint32_t st = 0, en = 0;
-        if (lane < np && px < u.npixu) { en = cnt[px]; st = px ? cnt[px - 1] : 0u; }
+        if (lane < np && px >= 0 && px < u.npixu) { en = cnt[px]; st = px ? cnt[px - 1] : 0u; }   // (px < 0: see unit_records, dpx)
         OutT vals[CMAX];
 #pragma unroll
         for (int c = 0; c < CMAX; ++c) vals[c] = (bg && c < C) ? bg[c] : (OutT)0;
@@ -1759,7 +1761,7 @@ __device__ inline void emit_chunk(const UnitRecs &u, Digest digest, DigestFly di
         for (int p = 0; p * kWave < npix; ++p) {
             const int px = p * kWave + u.dpx + lane;
             uint32_t st = 0, en = 0;
-            if (lane < min(kWave, npix - p * kWave) && px < u.npixu) { en = cnt[px]; st = px ? cnt[px - 1] : 0u; }
+            if (lane < min(kWave, npix - p * kWave) && px >= 0 && px < u.npixu) { en = cnt[px]; st = px ? cnt[px - 1] : 0u; }
             if (p == 0) w.pace();
             emit_part_main<OutT, CMAX, STAGE>(sorted + cs, st, en, p, digest, digest_fly, npix, C, dst, w, bg, reduce);
         }
@@ -3677,6 +3679,9 @@ __global__ __launch_bounds__(kWave, HOT ? 4 : (CM <= 12 ? EVREP_TORE_WAVES : 1))
         int x0 = 0, y0 = 0, Hf = H, Wf = W;
         if (!empty && (frame_mode == 0 || frame_mode == 1)) { x0 = m.xmin; y0 = m.ymin; }  // x - min(x) + 1, then [.., j - 1]
         if (frame_mode == 0) { Hf = m.ymax - m.ymin + 1; Wf = m.xmax - m.xmin + 1; }
+        // out-of-frame events (EVREP_ST_OOB) can stretch the bounding box beyond the frame: the compact array then does not fit the
+        // window's H * W * C slice (its rows of Wf pixels would run into the next window, or past the tensor): nothing is written
+        if (frame_mode == 0 && ((int64_t)m.ymax - m.ymin + 1 > H || (int64_t)m.xmax - m.xmin + 1 > W)) return;
         if (orow >= Hf || oc0 >= Wf) return;
         const int npix = min(span * kChunkPx, Wf - oc0);
         const int row = orow + y0;  // sensor row feeding this output row
@@ -3961,6 +3966,7 @@ __global__ __launch_bounds__(kWave, EVREP_TST_WAVES) void k_tore_stream(const in
     int x0 = 0, y0 = 0, Hf = H, Wf = W;
     if (!empty && (frame_mode == 0 || frame_mode == 1)) { x0 = m.xmin; y0 = m.ymin; }
     if (frame_mode == 0) { Hf = m.ymax - m.ymin + 1; Wf = m.xmax - m.xmin + 1; }
+    if (frame_mode == 0 && ((int64_t)m.ymax - m.ymin + 1 > H || (int64_t)m.xmax - m.xmin + 1 > W)) return;   // (k_tore: the box does not fit)
     if (orow >= Hf || oc0 >= Wf) return;
     const int npix = min(uc.span * kChunkPx, Wf - oc0);
     const int row = orow + y0;

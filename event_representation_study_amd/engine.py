@@ -252,7 +252,9 @@ class EventBatch:
     def tore(self, k=6, frame_mode=0, scale=1.0, out=None, sample_times=None, times_f64=None, sample_times_f64=None):
         """TORE.  frame_mode 0 (bounding box, the gen1/gen4 dispatcher's behaviour) returns a list of
         per-window (Hbb, Wbb, 2k) views (needs one host sync for the boxes); modes 1/2 return
-        (B, H, W, 2k)."""
+        (B, H, W, 2k).  Mode 0 gives a (0, 0, 2k) view for an empty window AND for a window whose out-of-frame events
+        stretch its box beyond H x W (nothing is written for either): ``status()`` tells them apart, ST_EMPTY against
+        ST_OOB -- a batched caller that must not take the second for the first reads it."""
         self.bin()
         out = self._out(out, 2 * k, torch.float32)
         keep, tptr = self._i32_dev(sample_times, 1)
@@ -282,6 +284,8 @@ class EventBatch:
             hb, wb = int(bb[b, 3]) - int(bb[b, 1]) + 1, int(bb[b, 2]) - int(bb[b, 0]) + 1
             if hb <= 0 or wb <= 0:                      # an empty window has no bounding box: an empty frame
                 hb = wb = 0
+            if hb > self.H or wb > self.W:              # out-of-frame events (ST_OOB) stretched the box beyond the frame: the
+                hb = wb = 0                             # compact array does not fit the window's slice and is not written
             flat = out[b].reshape(-1)
             views.append(flat[: hb * wb * 2 * k].view(hb, wb, 2 * k))
         return views

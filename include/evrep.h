@@ -191,7 +191,8 @@ int evrep_time_surface_ftime(const evrep_plan *plan, const int32_t *events, cons
 /* events2ToreFeature (tore.py:6-83) for one sample time per window, k <= 8.
  * sample_times == NULL: T = t[-1] (gen1_transforms.py:63); otherwise DEVICE int32 [B].
  * frame_mode 0: the events' bounding box, origin-shifted (gen1_transforms.py:61-64); the window's
- *               output is a compact (Hbb,Wbb,2k) array at out + b*H*W*2k, bbox via evrep_read_bbox;
+ *               output is a compact (Hbb,Wbb,2k) array at out + b*H*W*2k, bbox via evrep_read_bbox; a window whose
+ *               out-of-frame events (EVREP_ST_OOB) stretch the box beyond H x W has no such array: nothing is written for it;
  * frame_mode 1: full (H,W) frame, origin-shifted by (xmin,ymin) (n_imagenet .../imagenet.py:1095-1103);
  * frame_mode 2: full (H,W) frame, no shift (x, y used as 0-based pixel coordinates).
  * Timestamps that are not ascending (EVREP_ST_UNSORTED): array order, each event replacing the (pixel, polarity) k-vector v by the
