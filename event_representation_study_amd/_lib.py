@@ -101,6 +101,8 @@ SYMBOLS = {
     "evrep_time_index": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "evrep_sort_image_scratch_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32]),
     "evrep_sort_image": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _I32P, _i32, _vp, _vp, _vp, _vp]),
+    "evrep_nimg_study_rows_scratch_bytes": (ctypes.c_size_t, [_i32, _i64]),
+    "evrep_nimg_study_rows": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "evrep_detector_input": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
                                             _vp, _vp, _vp, _f32, _vp, _vp]),
     "evrep_resize_tap_tables": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp]),
@@ -126,6 +128,9 @@ TIME_INDEX_RAW, TIME_INDEX_RANK = 0, 1
 SORT_EMPTY, SORT_DECREASING, SORT_NO_INDEX = 1, 2, 4
 SORT_STRICT, SORT_USE_IMAGE = 1, 2
 SORT_MAX_B, SORT_MAX_Q = 1 << 20, 16
+# evrep_nimg_study_rows: the row sets to write, per-window status bits
+STUDY_MDES, STUDY_STACK, STUDY_TORE = 1, 2, 4
+STUDY_EMPTY, STUDY_FUTURE, STUDY_T_RANGE, STUDY_FLAT, STUDY_UNORDERED = 1, 2, 4, 8, 16
 # evrep_est_voxel_backward: the largest piecewise-linear table (its 2 * nseg float64 sums live in LDS)
 EST_BWD_MAX_SEG = 8192
 # evrep_est_prepare: status bits, the largest B

@@ -8,10 +8,10 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libevrep.so")
-# fourteen translation units, compiled in parallel and linked into one .so (r05; a unity build until then: four minutes)
+# fifteen translation units, compiled in parallel and linked into one .so (r05; a unity build until then: four minutes)
 SOURCES = ["evrep_capi.hip", "evrep_capi_mdes.hip", "evrep_capi_builders.hip", "evrep_capi_gwd.hip", "evrep_capi_filters.hip",
            "evrep_capi_windows.hip", "evrep_capi_augment.hip", "evrep_capi_dist.hip", "evrep_capi_sort.hip", "evrep_est_bwd.hip",
-           "evrep_est_prep.hip", "evrep_capi_detin.hip", "evrep_capi_voxnorm.hip", "evrep_capi_decode.hip"]
+           "evrep_est_prep.hip", "evrep_capi_detin.hip", "evrep_capi_voxnorm.hip", "evrep_capi_decode.hip", "evrep_capi_study.hip"]
 _BIN = ["evrep_bin.hip", "evrep_common.h", "evrep_capi_shared.h"]
 _BLD = _BIN + ["evrep_builders.hip", "evrep_capi_builders.h", "evrep_est_table.h"]
 UNIT_DEPS = {"evrep_capi.hip": _BIN, "evrep_capi_mdes.hip": _BLD, "evrep_capi_builders.hip": _BLD,
@@ -25,7 +25,8 @@ UNIT_DEPS = {"evrep_capi.hip": _BIN, "evrep_capi_mdes.hip": _BLD, "evrep_capi_bu
              "evrep_est_prep.hip": ["evrep_common.h", "evrep_capi_shared.h"],
              "evrep_capi_detin.hip": ["evrep_detin.hip", "evrep_detin_frames.hip", "evrep_common.h", "evrep_capi_shared.h"],
              "evrep_capi_voxnorm.hip": ["evrep_voxnorm.hip", "evrep_common.h", "evrep_capi_shared.h"],
-             "evrep_capi_decode.hip": ["evrep_decode.hip", "evrep_wave_search.h", "evrep_common.h", "evrep_capi_shared.h"]}
+             "evrep_capi_decode.hip": ["evrep_decode.hip", "evrep_wave_search.h", "evrep_common.h", "evrep_capi_shared.h"],
+             "evrep_capi_study.hip": ["evrep_study.hip", "evrep_wave_search.h", "evrep_common.h", "evrep_capi_shared.h"]}
 OBJDIR = os.path.join(PKG, "_obj")
 
 # -ffp-contract=off: the parity contract is bit-exactness with the reference's separate

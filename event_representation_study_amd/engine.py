@@ -254,7 +254,8 @@ class EventBatch:
         per-window (Hbb, Wbb, 2k) views (needs one host sync for the boxes); modes 1/2 return
         (B, H, W, 2k).  Mode 0 gives a (0, 0, 2k) view for an empty window AND for a window whose out-of-frame events
         stretch its box beyond H x W (nothing is written for either): ``status()`` tells them apart, ST_EMPTY against
-        ST_OOB -- a batched caller that must not take the second for the first reads it."""
+        ST_OOB -- a batched caller that must not take the second for the first reads it.  sample_times_f64 (with times_f64): one
+        float64 sample time per window, as a host sequence or as a (B,) float64 tensor already on the batch's device."""
         self.bin()
         out = self._out(out, 2 * k, torch.float32)
         keep, tptr = self._i32_dev(sample_times, 1)
@@ -268,7 +269,14 @@ class EventBatch:
                     or not times_f64.is_contiguous():
                 raise ValueError("times_f64 must be a contiguous float64 tensor with one entry per event on %s" % self.device)
             fptr = _ptr(times_f64)
-            if sample_times_f64 is not None:
+            if isinstance(sample_times_f64, torch.Tensor) and sample_times_f64.is_cuda:
+                # made on the device (evrep_nimg_study_rows): taken as it lies, nothing crosses to the host and back
+                keep_f = sample_times_f64
+                if keep_f.dtype != torch.float64 or keep_f.device != self.device or tuple(keep_f.shape) != (self.B,) \
+                        or not keep_f.is_contiguous():
+                    raise ValueError("a device sample_times_f64 must be a contiguous (B,) float64 tensor on %s" % self.device)
+                sfptr = _ptr(keep_f)
+            elif sample_times_f64 is not None:
                 keep_f = torch.as_tensor(np.asarray(sample_times_f64, dtype=np.float64)).reshape(-1).to(self.device)
                 if keep_f.numel() != self.B:
                     raise ValueError("sample_times_f64 must hold one time per window")

@@ -24,7 +24,9 @@ min-max of the intensity) are strided float32 tensor ops on the builder's output
 
 The three n_imagenet wrappers of the path's own builders that run in the reference -- reshape_then_optimized
 (:1025-1039), reshape_then_event_stack (:1042-1060), reshape_then_tore (:1080-1107) -- are mirrored here too
-(float64 event tensors with integral values, as load_event produces them without `reshape`).
+(float64 event tensors with integral values, as load_event produces them without `reshape`).  study_batch is their batched
+form: one upload, evrep_nimg_study_rows (csrc/evrep_study.hip: the rows each wrapper hands its builder, formed on the device), the
+batched builder, one cast-and-transpose launch; n_imagenet_front.study_device is the same on device-made rows.
 reshape_then_time_surface (:1110-1137) raises IndexError in the reference itself (a float `p` field indexes
 the surface memory, time_surface.py:67) and does so here; reshape_then_voxel_grid / _to_image go through tonic
 (absent; see representations/tonic_compat.py).
@@ -520,3 +522,134 @@ def reshape_then_time_surface(event_tensor, augment=None, **kwargs):
     # the reference stores int8 polarities back into a '<f8' field and then indexes memory[p, y, x] with it
     raise IndexError("only integers, slices (`:`), ellipsis (`...`), numpy.newaxis (`None`) and integer or boolean "
                      "arrays are valid indices")
+
+
+# ---------------------------------------------------------------------------------------------
+# the same three wrappers for a batch: the rows formed on the device (csrc/evrep_study.hip), then the batched builders
+# ---------------------------------------------------------------------------------------------
+STUDY_NAMES = ("optimized", "event_stack", "tore")
+_STUDY_EMPTY_ERRORS = {      # what reshape_then_<name> raises for an empty tensor, and where
+    "optimized": (ValueError, "zero-size array to reduction operation minimum which has no identity"),   # t.min() on no events
+    "event_stack": (IndexError, "index -1 is out of bounds for axis 0 with size 0"),                     # data[-1]["t"]
+    "tore": (ValueError, "min() arg is an empty sequence"),                                              # min(x)
+}
+
+
+def _study_name(name):
+    if name == "time_surface":
+        reshape_then_time_surface(None)           # the reference cannot run it: its IndexError
+    if name not in STUDY_NAMES:
+        raise KeyError(name)
+    from . import _lib
+    return {"optimized": _lib.STUDY_MDES, "event_stack": _lib.STUDY_STACK, "tore": _lib.STUDY_TORE}[name]
+
+
+def study_status_error(name, status):
+    """The exception the status words of evrep_nimg_study_rows stand for under reshape_then_<name> (None: no window is refused),
+    naming the first such sample: the wrapper's own exception for an empty tensor, ValueError for times that cannot be cast or
+    rebased into int32, and for EventStack ValueError for a window with rows behind its last time."""
+    from ._lib import STUDY_EMPTY, STUDY_FUTURE, STUDY_T_RANGE
+    status = np.asarray(status)
+    hit = np.flatnonzero(status & STUDY_EMPTY)
+    if hit.size:
+        cls, text = _STUDY_EMPTY_ERRORS[name]
+        return cls("%s (sample %d: empty event tensor)" % (text, int(hit[0])))
+    hit = np.flatnonzero(status & STUDY_T_RANGE)
+    if hit.size:
+        return ValueError("sample %d: a time that is NaN or not below 2^63, or whole seconds that span more than int32 holds"
+                          % int(hit[0]))
+    hit = np.flatnonzero(status & STUDY_FUTURE) if name == "event_stack" else np.zeros(0, np.int64)
+    if hit.size:
+        return ValueError("sample %d: rows later than the window's last time (descending or negative times); the batched form "
+                          "builds the past half only, reshape_then_event_stack builds such a window" % int(hit[0]))
+    return None
+
+
+def _study_rows(batch, t, xy, want):
+    """evrep_nimg_study_rows on the rows of `batch` ([x.long(), y.long(), 0, sign p]), their float64 times and untruncated
+    coordinates -> dict of device tensors: "mdes" / "stack" / "tore" ((total, 4) int32, the wanted sets only), "sample_times"
+    ((B,) float64, with "tore"), "status" ((B,) uint32).  Nothing waits for the device."""
+    import ctypes
+    from . import _lib
+    from ._lib import check
+    from .engine import _ptr, _stream_ptr
+    B, total, dev, lib = batch.B, batch.total, batch.device, batch.lib
+    if B == 0:
+        raise ValueError("no window")
+    if t.dtype != torch.float64 or t.device != dev or t.numel() != total or not t.is_contiguous():
+        raise ValueError("one contiguous float64 time per event on %s" % dev)
+    if int(batch.offsets_host[0]) != 0 or int(batch.offsets_host[-1]) != total:
+        raise ValueError("the batch's offsets must run from 0 to its %d rows: the row sets are written at the offsets" % total)
+    tore = bool(want & _lib.STUDY_TORE)
+    if tore and (xy is None or xy.dtype != torch.float64 or xy.device != dev or tuple(xy.shape) != (total, 2) or not xy.is_contiguous()):
+        raise ValueError("TORE needs the untruncated coordinates: a contiguous (total, 2) float64 tensor on %s" % dev)
+    nbytes = int(lib.evrep_nimg_study_rows_scratch_bytes(B, total))
+    if nbytes == 0:
+        raise ValueError("evrep_nimg_study_rows does not take %d windows" % B)
+    n = max(total, 1)
+    sets = [k for k, bit in (("mdes", _lib.STUDY_MDES), ("stack", _lib.STUDY_STACK), ("tore", _lib.STUDY_TORE)) if want & bit]
+    out = torch.empty((len(sets) * n, 4), dtype=torch.int32, device=dev)
+    res = {k: out[j * n:j * n + n] for j, k in enumerate(sets)}
+    meta = torch.empty(nbytes + B * 16, dtype=torch.uint8, device=dev)         # scratch, sample times, status words
+    res["sample_times"] = meta[nbytes:nbytes + B * 8].view(torch.float64)
+    res["status"] = meta[nbytes + B * 8:nbytes + B * 12].view(torch.uint32)
+    if total == 0:       # an empty tensor has no address: one row nothing reads
+        rows_in, t_in, xy_in = out.new_zeros((1, 4)), meta.new_zeros(8).view(torch.float64), meta.new_zeros(16).view(torch.float64)
+    else:
+        rows_in, t_in, xy_in = batch.events, t, xy
+    null = ctypes.c_void_p(None)
+    with torch.cuda.device(dev):
+        check(lib.evrep_nimg_study_rows(_ptr(rows_in), _ptr(t_in), _ptr(xy_in) if tore else null, _ptr(batch.offsets), B, batch.H, batch.W,
+                                        int(want), *[_ptr(res[k]) if k in res else null for k in ("mdes", "stack", "tore")],
+                                        _ptr(res["sample_times"]) if tore else null, _ptr(res["status"]), _ptr(meta), _stream_ptr()),
+              "evrep_nimg_study_rows")
+    for k in sets:
+        res[k] = res[k][:total]
+    return res
+
+
+def _study(name, batch, t, xy):
+    """The part of study_batch behind the upload (n_imagenet_front.study_device enters here with device-made rows): the rows of
+    reshape_then_<name> from evrep_nimg_study_rows, the batched builder on an EventBatch over them, the cast and the channel-first
+    transpose (evrep_voxel_normalize without its normalisation) -> ((B, 12, H, W) float32, (B,) uint32 status words, both on the
+    device).  Nothing waits for the device."""
+    from .engine import voxel_normalize
+    want = _study_name(name)
+    r = _study_rows(batch, t, xy, want)
+    rows = r[{"optimized": "mdes", "event_stack": "stack", "tore": "tore"}[name]]
+    nb = EventBatch(rows, batch.offsets_host, batch.H, batch.W, max_events_per_window=int(batch.plan.max_events_per_window),
+                    plan_flags=int(batch.plan.flags))
+    if name == "optimized":
+        rep = nb.optimized(scale=1.0, dtype=torch.float64)
+    elif name == "event_stack":
+        rep = nb.event_stack(12, premap=2, scale=1.0)            # the rows hold the final -1 / +1 (EventStack.pre_stack's 2p - 1)
+    else:
+        rep = nb.tore(k=6, frame_mode=2, scale=1.0, times_f64=t, sample_times_f64=r["sample_times"])
+    return voxel_normalize(rep, normalize=False), r["status"]
+
+
+def study_batch(name, event_tensors, height=IMAGE_H, width=IMAGE_W, device="cuda:0"):
+    """reshape_then_optimized / reshape_then_event_stack / reshape_then_tore (name "optimized", "event_stack", "tore") for a batch:
+    a list of (N_b, 4) float64 event tensors [x, y, t_seconds, p], p in {-1, 0, +1}, coordinates inside the frame -> (B, 12, H, W)
+    float32 device tensor; window b is what reshape_then_<name>(event_tensors[b], height=height, width=width) returns (ERGO-12 and
+    EventStack bit for bit).  The batched sibling of accumulate_batch, dist_batch and sort_batch: one upload of the rows, their
+    times and coordinates; evrep_nimg_study_rows; the binning pass and the builder for B windows; one cast-and-transpose launch.
+
+    Refused, naming the sample: an empty tensor (the exception reshape_then_<name> raises for one), times that are NaN, not below
+    2^63 or whose whole seconds span more than int32 holds (ValueError), for "event_stack" a window with rows later than its last
+    time (ValueError: the batched form builds the past half only), coordinates outside the frame (RuntimeError) and a polarity
+    outside {-1, 0, +1} (ValueError).  "time_surface" raises the IndexError of reshape_then_time_surface, any other name KeyError."""
+    _study_name(name)
+    wins = [_as_f64(e) for e in event_tensors]
+    for b, w in enumerate(wins):
+        if len(w) and not np.isin(w[:, 3], (-1.0, 0.0, 1.0)).all():
+            raise ValueError("sample %d: the batched form takes polarities -1, 0 and +1" % b)
+    batch = EventBatch.from_numpy([_window(w, height, width)[0] for w in wins], height, width, device=device)
+    cat = np.concatenate(wins) if wins else np.zeros((0, 4))
+    tx = torch.from_numpy(np.ascontiguousarray(cat[:, [2, 0, 1]].T)).to(batch.device)          # one upload: t, x, y
+    t, xy = tx[0].contiguous(), tx[1:].t().contiguous()
+    images, status = _study(name, batch, t, xy)
+    err = study_status_error(name, status.cpu().numpy())
+    if err is not None:
+        raise err
+    return images

@@ -25,9 +25,17 @@ builds any of the eleven ``n_imagenet_acc.SPECS`` accumulators from it, ``dist_d
 host by ``draw_slice`` / ``draw_augment`` from the global ``random`` / ``np.random`` streams in exactly the order B sequential reference
 calls consume them, so seeding the two generators reproduces the reference's batch.
 
+THE STUDY'S REPRESENTATIONS.  ``study_device(name, aug)`` builds ERGO-12, EventStack or TORE ("optimized", "event_stack", "tore")
+for the whole batch as n_imagenet's reshape_then_optimized / _event_stack / _tore wrappers (imagenet.py:1025-1107) build them per
+sample: ``evrep_nimg_study_rows`` (csrc/evrep_study.hip: a reduction per window, a write pass) turns ``aug.t`` and ``aug.xy`` into the
+rows those wrappers hand the builders -- whole seconds rebased to the window's first, the past half of the stack, coordinates
+shifted to their minimum with the float64 roundings of ``x - min(x) + 1`` --, the batched builder runs on an ``EventBatch`` over
+them, and ``voxel_normalize(normalize=False)`` casts and transposes; no event leaves the device.  ``study_rows_host`` is the numpy
+restatement of the kernel for one window.
+
 OUT OF SCOPE.  ``reshape_method`` "sample" and "unique" (``reshape_event_with_sample`` / ``reshape_event_unique`` raise
 NotImplementedError: the first draws a permutation of the whole sample, the second needs a key sort of it and is off by default
-in the reference); device-input forms of the ``_prep`` wrappers; ``accumulate_device("acc_sort", aug)`` (acc_sort is no
+in the reference); ``accumulate_device("acc_sort", aug)`` (acc_sort is no
 ``SPECS`` accumulator: ``sort_device`` is its device-input form); the ``denoise_*`` options, which the reference reads and never
 defines.  There is no CPU fallback for the device path: without a HIP device it raises ``EvrepError``.
 """
@@ -365,6 +373,90 @@ def dist_device(aug):
     if flat.size:
         raise ValueError("DiST of a window whose first and last timestamp agree (sample %d): its normalised times are NaN" % int(flat[0]))
     return ni._dist(aug.batch, aug.tnorm)
+
+
+def study_device(name, aug, check=True):
+    """ERGO-12, EventStack or TORE (name "optimized", "event_stack", "tore") from an AugmentedBatch -> (B, 12, H, W) float32 device
+    tensor, contiguous and channel first: what torch.stack([n_imagenet_acc.reshape_then_<name>(host rows of window b, height=H,
+    width=W) for b]) gives (imagenet.py:1025-1107), bit for bit.  evrep_nimg_study_rows forms the rows those wrappers hand the
+    builders from aug.batch, aug.t and aug.xy (see study_rows_host), the batched builder runs on an EventBatch over them with the
+    wrappers' arguments -- ERGO-12 in float64; twelve EventStack levels of the past half; TORE with k = 6 on the whole frame, the
+    float64 times themselves and each window's last time as its sample time --, evrep_voxel_normalize casts and transposes.  No
+    event leaves the device; aug is left as it is.
+
+    check=True reads the (B,) status words once, at the end, and raises what the per-sample wrapper raises on such rows, naming
+    the first such sample: for a window without events the wrapper's own exception for an empty tensor (ValueError, for
+    "event_stack" IndexError); ValueError for a window with a time that is NaN or not below 2^63, or whose whole seconds span more
+    than int32 holds; for "event_stack" ValueError for a window with rows later than its last time (descending or negative
+    times: the device form builds the past half only, reshape_then_event_stack builds such a window).  check=False reads
+    nothing back and returns (images, status): status a (B,) uint32 device tensor of _lib.STUDY_EMPTY, STUDY_FUTURE,
+    STUDY_T_RANGE, STUDY_FLAT and STUDY_UNORDERED; the image of a window flagged as above is not the reference's.
+
+    "time_surface" raises the IndexError reshape_then_time_surface raises (the reference cannot run it), any other name
+    KeyError.  TORE needs aug.xy (prepare(want_xy=True))."""
+    from . import n_imagenet_acc as ni
+    ni._study_name(name)
+    images, status = ni._study(name, aug.batch, aug.t, aug.xy)
+    if not check:
+        return images, status
+    err = ni.study_status_error(name, status.cpu().numpy())
+    if err is not None:
+        raise err
+    return images
+
+
+def study_rows_host(rows, t, xy):
+    """What evrep_nimg_study_rows writes for ONE window, in numpy: rows (n, 4) int32 [trunc x, trunc y, 0, sign p], t (n,) float64
+    seconds, xy (n, 2) float64 untruncated -> (rows_mdes, rows_stack, rows_tore, t_last, status), the three (n, 4) int32 row
+    sets, TORE's sample time and the window's _lib.STUDY_* word.
+
+        rows_mdes   [x, y, ti - ti.min(), p], ti = t.astype(np.int64): MixedDensityEventStack.stack's own casts
+                    (mixed_density_event_stack.py:26-33), narrowed to int32
+        rows_stack  [x, y, 0, +1 where p > 0 else -1]: 2 * ((p + 1) // 2) - 1 (imagenet.py:1051, event_stack.py:18); the window's
+                    past half ti <= t[-1] (event_stack.py:34) only where STUDY_FUTURE is clear
+        rows_tore   [int(x - min(x) + 1) - 1, int(y - min(y) + 1) - 1, k, p] on the float64 xy (imagenet.py:1098-1099,
+                    tore.py:29-33), k the row's index, counted down under STUDY_UNORDERED (events2ToreFeature's order marker)
+
+    A time that is NaN or not below 2^63 (STUDY_T_RANGE) takes no part in ti.min() and gets the time column 0; an empty window
+    is (three empty sets, 0.0, STUDY_EMPTY)."""
+    rows = np.asarray(rows, dtype=np.int32).reshape(-1, 4)
+    t = np.asarray(t, dtype=np.float64).reshape(-1)
+    xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    n = len(t)
+    if len(rows) != n or len(xy) != n:
+        raise ValueError("one time and one coordinate pair per row")
+    if n == 0:
+        return tuple(np.zeros((0, 4), np.int32) for _ in range(3)) + (0.0, np.uint32(_lib.STUDY_EMPTY))
+    st = 0
+    with np.errstate(invalid="ignore", over="ignore"):
+        ok = np.abs(t) < 2.0 ** 63                                     # (NaN compares False)
+        ti = np.zeros(n, np.int64)
+        ti[ok] = t[ok].astype(np.int64)                                # truncation toward zero
+        if not ok.all():
+            st |= _lib.STUDY_T_RANGE
+        if (ok & ~(ti.astype(np.float64) <= t[-1])).any():             # numpy compares the int64 times with the float64 last one
+            st |= _lib.STUDY_FUTURE
+        if not np.all(np.diff(t) >= 0):
+            st |= _lib.STUDY_UNORDERED
+        tc = np.zeros(n, np.int32)
+        if ok.any():
+            tmin, tmax = int(ti[ok].min()), int(ti[ok].max())
+            if tmax - tmin > np.iinfo(np.int32).max:
+                st |= _lib.STUDY_T_RANGE
+            if tmax == tmin and not st & _lib.STUDY_T_RANGE:
+                st |= _lib.STUDY_FLAT
+            tc[ok] = (ti[ok] - np.int64(tmin)).astype(np.int32)        # (both steps wrap where the result does not fit)
+
+        def shifted(c):
+            v = (c - c.min()) + 1.0                                    # two float64 roundings
+            inside = (v > -2147483649.0) & (v < 2147483648.0)
+            return (np.where(inside, np.where(inside, v, 0.0).astype(np.int64), np.iinfo(np.int32).min) - 1).astype(np.int32)
+        k = np.arange(n, dtype=np.int32)
+        mdes, stack, tore = rows.copy(), rows.copy(), rows.copy()
+        mdes[:, 2] = tc
+        stack[:, 2], stack[:, 3] = 0, np.where(rows[:, 3] > 0, 1, -1)
+        tore[:, 0], tore[:, 1], tore[:, 2] = shifted(xy[:, 0]), shifted(xy[:, 1]), -k if st & _lib.STUDY_UNORDERED else k
+    return mdes, stack, tore, float(t[-1]), np.uint32(st)
 
 
 def sort_device(aug, global_time, neglect_polarity, use_image, strict, quantize_sort=None, denoise_image=False, denoise_sort=False,

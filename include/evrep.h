@@ -693,6 +693,53 @@ size_t evrep_sort_image_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t K
 int evrep_sort_image(const float *prim, int32_t B, int32_t H, int32_t W, int32_t K, uint32_t flags, const int32_t *quantize,
                      int32_t nq, float *out, uint32_t *status, void *scratch, void *stream);
 
+/* The rows the study's own representations are built from, out of what evrep_nimg_prepare leaves: the host step of n_imagenet's
+ * reshape_then_optimized / reshape_then_event_stack / reshape_then_tore (imagenet.py:1025-1107) in front of evrep_optimized,
+ * evrep_event_stack and evrep_tore_ftime, for the B windows of a batch.  One memset and two launches (a reduction per window over
+ * several workgroups, a write pass); no plan, no workspace, no allocation, nothing waits for the device or reads a size on the
+ * host: the call may be captured into a graph.
+ *
+ * evrep_nimg_study_rows: rows DEVICE int32 [>= offsets[B],4] = (trunc x, trunc y, 0, sign p), 16-byte aligned; t DEVICE double
+ *   [>= offsets[B]], seconds; xy DEVICE double [>= offsets[B],2], the untruncated coordinates, 16-byte aligned (read for
+ *   EVREP_STUDY_TORE only, else it may be NULL); offsets DEVICE int64 [B+1], ascending.  want: which row sets are written
+ *   (EVREP_STUDY_MDES | _STACK | _TORE, not 0); the output of a set that is not wanted is not touched and may be NULL.  With
+ *   ti = (int64)trunc(t) of a row, tmin the minimum of ti over its window, t_last the t of the window's last row and k the row's
+ *   index inside its window, every set DEVICE int32 [>= offsets[B],4], 16-byte aligned, indexed like rows:
+ *     rows_mdes   (x, y, (int32)(ti - tmin), p): astype(np.int64) and t - t.min() of MixedDensityEventStack.stack
+ *                 (mixed_density_event_stack.py:26-33); the difference wraps to 32 bits where it does not fit (EVREP_STUDY_T_RANGE)
+ *     rows_stack  (x, y, 0, p > 0 ? 1 : -1): p' = (p + 1) // 2 (imagenet.py:1051), then 2 p' - 1 (event_stack.py:18), for
+ *                 evrep_event_stack's premap 2.  They are the window's past half, ti <= t_last (event_stack.py:34), only where no
+ *                 row has EVREP_STUDY_FUTURE; the future half of such a window is not formed here
+ *     rows_tore   ((int32)trunc((x - xmin) + 1.0) - 1, (int32)trunc((y - ymin) + 1.0) - 1, m, p) from the float64 xy and their
+ *                 minima over the window, every operation one IEEE float64 operation (imagenet.py:1098-1099, tore.py:29-33);
+ *                 m = k, or -k in a window with EVREP_STUDY_UNORDERED: the order marker events2ToreFeature's float-time form
+ *                 hands evrep_tore_ftime beside times_f64 = t.  sample_times DEVICE double [B] = t_last (imagenet.py:1100), 0 for
+ *                 an empty window; wanted with this set
+ *   status DEVICE uint32 [B] is overwritten with
+ *     EVREP_STUDY_EMPTY      the window has no row (no other bit is set then)
+ *     EVREP_STUDY_FUTURE     a row with (double)ti > t_last, or a t_last that is NaN: times that descend or are negative
+ *     EVREP_STUDY_T_RANGE    a t that is NaN or not below 2^63 in magnitude (tested before the cast; such a row's time column is 0
+ *                            and it takes no part in tmin), or max ti - tmin above INT32_MAX
+ *     EVREP_STUDY_FLAT       every ti of the window is equal (informational: the builders define what they do then)
+ *     EVREP_STUDY_UNORDERED  t[k + 1] - t[k] >= 0 fails somewhere in the window (informational: it chooses TORE's order marker)
+ *   xy must be finite.  scratch DEVICE of evrep_nimg_study_rows_scratch_bytes(B, total) bytes, total >= offsets[B] - offsets[0],
+ *   16-byte aligned, no initialisation needed; its size depends on B alone.  1 <= H, W <= EVREP_MAX_DIM (the frame the rows lie
+ *   on; coordinates are not checked against it), 0 <= B <= EVREP_NIMG_MAX_B, a window holds fewer than 2^31 rows; anything
+ *   else, a NULL or misaligned pointer that is needed, want == 0 or an unknown want bit is EVREP_EINVAL before anything is
+ *   launched.  evrep_nimg_study_rows_scratch_bytes returns 0 for arguments the call refuses. */
+#define EVREP_STUDY_MDES 1u
+#define EVREP_STUDY_STACK 2u
+#define EVREP_STUDY_TORE 4u
+#define EVREP_STUDY_EMPTY 1u
+#define EVREP_STUDY_FUTURE 2u
+#define EVREP_STUDY_T_RANGE 4u
+#define EVREP_STUDY_FLAT 8u
+#define EVREP_STUDY_UNORDERED 16u
+size_t evrep_nimg_study_rows_scratch_bytes(int32_t B, int64_t total);
+int evrep_nimg_study_rows(const int32_t *rows, const double *t, const double *xy, const int64_t *offsets, int32_t B, int32_t H,
+                          int32_t W, uint32_t want, int32_t *rows_mdes, int32_t *rows_stack, int32_t *rows_tore,
+                          double *sample_times, uint32_t *status, void *scratch, void *stream);
+
 /* The detector's input batch in ONE launch: what Gen1H5.__getitem__ does after get_item_transform, plus collate_fn and
  * Trainer.prepro_data (ev-YOLOv6/yolov6/data/gen1_2yolo.py:230-265,320-398,427-447; data_augment.py:31-85,110-184;
  * yolov6/core/engine.py:629-635).  A channel-last representation becomes the channel-first float32 tensor of the detector; per
