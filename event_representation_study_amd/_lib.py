@@ -5,6 +5,11 @@ a builder raises.  (The library is built in-tree by ``event_representation_study
 """
 import ctypes
 import os
+import types
+
+# torch bundles its own libamdhip64.so.7; it must be the process's HIP runtime (same SONAME as /opt/rocm's) before
+# libevrep.so is loaded, otherwise device pointers / streams from torch are foreign to our launches.
+import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EVREP_LIB_PATH") or os.path.join(_PKG, "libevrep.so")  # env override: A/B builds
@@ -38,83 +43,91 @@ class Plan(ctypes.Structure):
     ]
 
 
-# every symbol include/evrep.h declares: name -> (restype, argtypes)
+class Status(tuple):
+    """A SYMBOLS entry (c_int, argtypes) whose int is an EVREP_* status code: api() gives the function an errcheck."""
+
+
+def _st(argtypes):
+    return Status((ctypes.c_int, argtypes))
+
+
+# every symbol include/evrep.h declares: name -> (restype, argtypes); _st(argtypes) for the entry points that return a status
 _vp, _i32, _i64, _f64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_float
 _PP = ctypes.POINTER(Plan)
 _I32P = ctypes.POINTER(ctypes.c_int32)
 SYMBOLS = {
     "evrep_abi_version": (ctypes.c_int, []),
     "evrep_last_hip_error": (ctypes.c_char_p, []),
-    "evrep_plan_init": (ctypes.c_int, [_PP, _i32, _i32, _i32, _i64, _i64]),
-    "evrep_plan_init_ex": (ctypes.c_int, [_PP, _i32, _i32, _i32, _i64, _i64, ctypes.c_uint32]),
-    "evrep_plan_set_pacing": (ctypes.c_int, [_PP, _i32]),
+    "evrep_plan_init": _st([_PP, _i32, _i32, _i32, _i64, _i64]),
+    "evrep_plan_init_ex": _st([_PP, _i32, _i32, _i32, _i64, _i64, ctypes.c_uint32]),
+    "evrep_plan_set_pacing": _st([_PP, _i32]),
     "evrep_workspace_bytes": (ctypes.c_size_t, [_PP]),
-    "evrep_bin_events": (ctypes.c_int, [_PP, _vp, _vp, _vp, _vp]),
-    "evrep_probe_store": (ctypes.c_int, [_vp, ctypes.c_size_t, _vp]),
-    "evrep_mdes": (ctypes.c_int, [_PP, _vp, _vp, _vp, _i32, _I32P, _I32P, _I32P, _f64, _i32, _vp, _vp]),
-    "evrep_mdes_sbt_windows": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
-    "evrep_mdes_ex": (ctypes.c_int, [_PP, _vp, _vp, _vp, _i32, _I32P, _I32P, _I32P, _f64, _i32, _vp, _vp, _vp, _vp]),
-    "evrep_optimized": (ctypes.c_int, [_PP, _vp, _vp, _vp, _f64, _i32, _vp, _vp]),
-    "evrep_event_stack": (ctypes.c_int, [_PP, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp]),
-    "evrep_time_surface": (ctypes.c_int, [_PP, _vp, _vp, _vp, _i32, _vp, _f64, _i32, _f64, _i32, _vp, _vp]),
-    "evrep_time_surface_ftime": (ctypes.c_int, [_PP, _vp, _vp, _vp, _i32, _vp, _vp, _f64, _i32, _f64, _i32, _vp, _vp]),
-    "evrep_tore": (ctypes.c_int, [_PP, _vp, _vp, _vp, _i32, _i32, _vp, _f32, _vp, _vp]),
-    "evrep_tore_ftime": (ctypes.c_int, [_PP, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
-    "evrep_voxel": (ctypes.c_int, [_PP, _vp, _vp, _vp, _i32, _i32, _f64, _vp, _vp]),
-    "evrep_voxel_range": (ctypes.c_int, [_PP, _vp, _vp, _vp, _i32, _i32, _f64, _vp, _vp, _vp]),
-    "evrep_voxel_tnorm": (ctypes.c_int, [_PP, _vp, _vp, _vp, _vp, _i32, _f64, _vp, _vp]),
-    "evrep_voxel_subpixel": (ctypes.c_int, [_PP, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
-    "evrep_polstats": (ctypes.c_int, [_PP, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _f64, _vp, _vp]),
-    "evrep_est_voxel": (ctypes.c_int, [_PP, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _f64, _f64, _vp, _vp]),
+    "evrep_bin_events": _st([_PP, _vp, _vp, _vp, _vp]),
+    "evrep_probe_store": _st([_vp, ctypes.c_size_t, _vp]),
+    "evrep_mdes": _st([_PP, _vp, _vp, _vp, _i32, _I32P, _I32P, _I32P, _f64, _i32, _vp, _vp]),
+    "evrep_mdes_sbt_windows": _st([_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "evrep_mdes_ex": _st([_PP, _vp, _vp, _vp, _i32, _I32P, _I32P, _I32P, _f64, _i32, _vp, _vp, _vp, _vp]),
+    "evrep_optimized": _st([_PP, _vp, _vp, _vp, _f64, _i32, _vp, _vp]),
+    "evrep_event_stack": _st([_PP, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp]),
+    "evrep_time_surface": _st([_PP, _vp, _vp, _vp, _i32, _vp, _f64, _i32, _f64, _i32, _vp, _vp]),
+    "evrep_time_surface_ftime": _st([_PP, _vp, _vp, _vp, _i32, _vp, _vp, _f64, _i32, _f64, _i32, _vp, _vp]),
+    "evrep_tore": _st([_PP, _vp, _vp, _vp, _i32, _i32, _vp, _f32, _vp, _vp]),
+    "evrep_tore_ftime": _st([_PP, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
+    "evrep_voxel": _st([_PP, _vp, _vp, _vp, _i32, _i32, _f64, _vp, _vp]),
+    "evrep_voxel_range": _st([_PP, _vp, _vp, _vp, _i32, _i32, _f64, _vp, _vp, _vp]),
+    "evrep_voxel_tnorm": _st([_PP, _vp, _vp, _vp, _vp, _i32, _f64, _vp, _vp]),
+    "evrep_voxel_subpixel": _st([_PP, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "evrep_polstats": _st([_PP, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _f64, _vp, _vp]),
+    "evrep_est_voxel": _st([_PP, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _f64, _f64, _vp, _vp]),
     "evrep_est_backward_scratch_bytes": (ctypes.c_size_t, [_i64, _i32]),
-    "evrep_est_voxel_backward": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp]),
+    "evrep_est_voxel_backward": _st([_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp]),
     "evrep_est_prepare_scratch_bytes": (ctypes.c_size_t, [_i64, _i32]),
-    "evrep_est_prepare": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "evrep_read_status": (ctypes.c_int, [_PP, _vp, _vp, _vp]),
-    "evrep_read_bbox": (ctypes.c_int, [_PP, _vp, _vp, _vp]),
-    "evrep_copy_window_meta_async": (ctypes.c_int, [_PP, _vp, _vp, _vp]),
+    "evrep_est_prepare": _st([_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "evrep_read_status": _st([_PP, _vp, _vp, _vp]),
+    "evrep_read_bbox": _st([_PP, _vp, _vp, _vp]),
+    "evrep_copy_window_meta_async": _st([_PP, _vp, _vp, _vp]),
     "evrep_gwd_scratch_bytes": (ctypes.c_size_t, [_i64, _i64]),
-    "evrep_resize_taps": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _i32, _vp, _vp]),
+    "evrep_resize_taps": _st([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _i32, _vp, _vp]),
     "evrep_gw_scratch_bytes": (ctypes.c_size_t, [_i64, _i64, _i32]),
-    "evrep_entropic_gw": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _f64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
-    "evrep_gwd_padded_l1": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _f64, _vp, _vp, _vp]),
+    "evrep_entropic_gw": _st([_vp, _i64, _vp, _i64, _vp, _vp, _i32, _f64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "evrep_gwd_padded_l1": _st([_vp, _i64, _i32, _vp, _i64, _i32, _f64, _vp, _vp, _vp]),
     "evrep_gwd_batch_scratch_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i64, _i64]),
-    "evrep_gwd_padded_l1_batch": (ctypes.c_int, [_i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i64, _i64, _f64, _vp, _vp, _vp]),
+    "evrep_gwd_padded_l1_batch": _st([_i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i64, _i64, _f64, _vp, _vp, _vp]),
     "evrep_otmi_scratch_bytes": (ctypes.c_size_t, [_i32]),
-    "evrep_otmi_event_clouds": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "evrep_otmi_rep_clouds": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
-    "evrep_filter_pixel_fsm": (ctypes.c_int, [_PP, _vp, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp]),
-    "evrep_filter_background": (ctypes.c_int, [_PP, _vp, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _vp]),
-    "evrep_filter_mask_gather": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp]),
-    "evrep_filter_cell_map": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "evrep_otmi_event_clouds": _st([_vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "evrep_otmi_rep_clouds": _st([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "evrep_filter_pixel_fsm": _st([_PP, _vp, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp]),
+    "evrep_filter_background": _st([_PP, _vp, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _vp]),
+    "evrep_filter_mask_gather": _st([_vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp]),
+    "evrep_filter_cell_map": _st([_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     "evrep_filter_compact_scratch_bytes": (ctypes.c_size_t, [_i32, _i64]),
-    "evrep_filter_compact": (ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "evrep_time_to_index": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
-    "evrep_windows_gather": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "evrep_filter_compact": _st([_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "evrep_time_to_index": _st([_vp, _i64, _vp, _i64, _vp, _vp]),
+    "evrep_windows_gather": _st([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "evrep_nimg_prepare_scratch_bytes": (ctypes.c_size_t, [_i32, _i64]),
-    "evrep_nimg_prepare": (ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _f64, _f64, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "evrep_nimg_prepare": _st([_vp, _vp, _i32, _vp, _vp, _f64, _f64, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "evrep_dist_scratch_bytes": (ctypes.c_size_t, [_i32, _i32, _i32]),
-    "evrep_dist": (ctypes.c_int, [_vp, _i32, _i32, _i32, _f64, _f32, _vp, _vp, _vp]),
+    "evrep_dist": _st([_vp, _i32, _i32, _i32, _f64, _f32, _vp, _vp, _vp]),
     "evrep_dense_rank_scratch_bytes": (ctypes.c_size_t, [_i32, _i64]),
-    "evrep_dense_rank_f32": (ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "evrep_dense_rank_f32": _st([_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "evrep_time_index_scratch_bytes": (ctypes.c_size_t, [_i32, _i64]),
-    "evrep_time_index": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "evrep_time_index": _st([_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "evrep_sort_image_scratch_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32]),
-    "evrep_sort_image": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _I32P, _i32, _vp, _vp, _vp, _vp]),
+    "evrep_sort_image": _st([_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _I32P, _i32, _vp, _vp, _vp, _vp]),
     "evrep_nimg_study_rows_scratch_bytes": (ctypes.c_size_t, [_i32, _i64]),
-    "evrep_nimg_study_rows": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "evrep_detector_input": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
-                                            _vp, _vp, _vp, _f32, _vp, _vp]),
-    "evrep_resize_tap_tables": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp]),
+    "evrep_nimg_study_rows": _st([_vp, _vp, _vp, _vp, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "evrep_detector_input": _st([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
+                                 _vp, _vp, _vp, _f32, _vp, _vp]),
+    "evrep_resize_tap_tables": _st([_vp, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp]),
     "evrep_detector_input_frames_scratch_bytes": (ctypes.c_size_t, [_i32]),
-    "evrep_detector_input_frames": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp]),
+    "evrep_detector_input_frames": _st([_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp]),
     "evrep_voxel_normalize_scratch_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32]),
-    "evrep_voxel_normalize": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
+    "evrep_voxel_normalize": _st([_vp, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
     "evrep_decode_scratch_bytes": (ctypes.c_size_t, [_i64]),
-    "evrep_decode_state_init": (ctypes.c_int, [_vp, _vp]),
-    "evrep_decode_dat": (ctypes.c_int, [_vp, _i64, _i32, _i64, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "evrep_decode_bin5": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "evrep_dat_seek_time": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "evrep_decode_state_init": _st([_vp, _vp]),
+    "evrep_decode_dat": _st([_vp, _i64, _i32, _i64, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "evrep_decode_bin5": _st([_vp, _i64, _i64, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "evrep_dat_seek_time": _st([_vp, _i64, _vp, _i64, _i64, _vp, _vp]),
 }
 # evrep_decode_dat / evrep_decode_bin5: modes, the overrun bit of the state's n_in, the fields of the state, the largest n
 DECODE_STRICT, DECODE_DROP_OOB = 0, 1
@@ -250,7 +263,7 @@ def pacing_from_env():
     return int(v) if v not in (None, "") else None
 
 
-_lib = None
+_lib = _api = None
 
 
 class EvrepError(RuntimeError):
@@ -258,13 +271,11 @@ class EvrepError(RuntimeError):
 
 
 def load():
-    """Load libevrep.so; raises (loudly) if the HIP extension is missing."""
+    """The raw handle: libevrep.so as the C ABI, status codes returned as they are (the C-ABI tests, bench.py and tools call
+    it).  Raises (loudly) if the HIP extension is missing."""
     global _lib
     if _lib is not None:
         return _lib
-    # torch bundles its own libamdhip64.so.7; it must be the process's HIP runtime (same SONAME as
-    # /opt/rocm's), otherwise device pointers / streams from torch are foreign to our launches.
-    import torch  # noqa: F401
     if not os.path.exists(LIB_PATH):
         raise EvrepError(
             "libevrep.so is missing (%s). Build it with `python -m event_representation_study_amd.build`; "
@@ -283,15 +294,84 @@ def load():
     return lib
 
 
-def check(rc, what=""):
-    if rc == EVREP_OK:
-        return
-    names = {EVREP_EINVAL: "EVREP_EINVAL (bad argument)", EVREP_EWORKSPACE: "EVREP_EWORKSPACE",
-             EVREP_EHIP: "EVREP_EHIP", EVREP_ENOTBINNED: "EVREP_ENOTBINNED"}
-    msg = names.get(rc, "rc=%d" % rc)
+def api():
+    """The checked handle, for the package: a namespace of one function per SYMBOLS entry with the raw handle's argtypes and
+    restype; a status other than EVREP_OK raises EvrepError naming the function.  The functions are objects of their own
+    (CDLL.__getitem__ makes a fresh one per call), so the raw handle keeps returning codes."""
+    global _api
+    if _api is None:
+        lib, ns = load(), types.SimpleNamespace()
+        for name, entry in SYMBOLS.items():
+            fn = lib[name]
+            fn.restype, fn.argtypes = entry
+            if isinstance(entry, Status):
+                fn.errcheck = _errcheck
+            setattr(ns, name, fn)
+        _api = ns
+    return _api
+
+
+def _errcheck(rc, fn, args):
+    if rc != EVREP_OK:
+        raise EvrepError(failure(rc, fn.__name__))
+    return rc
+
+
+_STATUS_NAMES = {EVREP_EINVAL: "EVREP_EINVAL (bad argument)", EVREP_EWORKSPACE: "EVREP_EWORKSPACE",
+                 EVREP_EHIP: "EVREP_EHIP", EVREP_ENOTBINNED: "EVREP_ENOTBINNED"}
+
+
+def failure(rc, what=""):
+    """The text of the EvrepError for status `rc` of the call `what` (check and the checked handle share it)."""
+    msg = _STATUS_NAMES.get(rc, "rc=%d" % rc)
     if rc == EVREP_EHIP:
         msg += ": " + (load().evrep_last_hip_error() or b"").decode()
-    raise EvrepError("%s failed: %s" % (what or "libevrep call", msg))
+    return "%s failed: %s" % (what or "libevrep call", msg)
+
+
+def check(rc, what=""):
+    """For a status the raw handle returned."""
+    if rc != EVREP_OK:
+        raise EvrepError(failure(rc, what))
+
+
+def require_gpu():
+    if not torch.cuda.is_available():
+        raise EvrepError("no HIP device visible: the builders run on an MI355X only (no CPU fallback)")
+
+
+def stream_ptr():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def ptr(t):
+    """A tensor's address as a c_void_p argument; None stays None (ctypes passes NULL)."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def scratch(nbytes, device):
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
+def want(t, what, dtype, shape=None, numel=None, device=None):
+    """The one check that `t` is the tensor a kernel will read at data_ptr(): a contiguous torch tensor of `dtype` (one, or a
+    tuple of them), of `shape` (None entries are free) or of `numel` elements, on `device` (a torch.device, or "cuda" for any
+    HIP device).  Returns t; ValueError naming `what` and what was expected otherwise."""
+    # (on the per-sample path: a few attribute reads when the tensor is right, the text only when it is not)
+    ok = isinstance(t, torch.Tensor) and (t.dtype in dtype if isinstance(dtype, tuple) else t.dtype == dtype) and t.is_contiguous()
+    if ok and shape is not None and tuple(t.shape) != shape:
+        ok = len(t.shape) == len(shape) and all(s is None or s == v for s, v in zip(shape, t.shape))
+    if ok and numel is not None:
+        ok = t.numel() == numel
+    if ok and device is not None:
+        ok = t.is_cuda if device == "cuda" else t.device == device
+    if not ok:
+        dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+        size = "" if shape is None and numel is None else \
+            (" of %d elements" % numel if shape is None else " of shape (%s)" % ", ".join("*" if s is None else str(int(s)) for s in shape))
+        raise ValueError("%s must be a contiguous %s tensor%s%s" % (what, " / ".join(str(d) for d in dtypes), size,
+                                                                   "" if device is None else " on %s" % (device,)))
+    return t
 
 
 def int32_array(values):

@@ -1,5 +1,6 @@
 """Build libevrep.so (HIP, gfx950 only) in-tree with hipcc.  hipcc cross-compiles without a GPU."""
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -12,21 +13,7 @@ LIB = os.path.join(PKG, "libevrep.so")
 SOURCES = ["evrep_capi.hip", "evrep_capi_mdes.hip", "evrep_capi_builders.hip", "evrep_capi_gwd.hip", "evrep_capi_filters.hip",
            "evrep_capi_windows.hip", "evrep_capi_augment.hip", "evrep_capi_dist.hip", "evrep_capi_sort.hip", "evrep_est_bwd.hip",
            "evrep_est_prep.hip", "evrep_capi_detin.hip", "evrep_capi_voxnorm.hip", "evrep_capi_decode.hip", "evrep_capi_study.hip"]
-_BIN = ["evrep_bin.hip", "evrep_common.h", "evrep_capi_shared.h"]
-_BLD = _BIN + ["evrep_builders.hip", "evrep_capi_builders.h", "evrep_est_table.h"]
-UNIT_DEPS = {"evrep_capi.hip": _BIN, "evrep_capi_mdes.hip": _BLD, "evrep_capi_builders.hip": _BLD,
-             "evrep_capi_gwd.hip": ["evrep_gwd.hip", "evrep_otmi.hip", "evrep_gw.hip", "evrep_common.h", "evrep_capi_shared.h"],
-             "evrep_capi_filters.hip": ["evrep_filters.hip", "evrep_common.h", "evrep_capi_shared.h"],
-             "evrep_capi_windows.hip": ["evrep_windows.hip", "evrep_wave_search.h", "evrep_common.h", "evrep_capi_shared.h"],
-             "evrep_capi_augment.hip": ["evrep_augment.hip", "evrep_common.h", "evrep_capi_shared.h"],
-             "evrep_capi_dist.hip": ["evrep_dist.hip", "evrep_ranksort.h", "evrep_common.h", "evrep_capi_shared.h"],
-             "evrep_capi_sort.hip": ["evrep_sort.hip", "evrep_ranksort.h", "evrep_common.h", "evrep_capi_shared.h"],
-             "evrep_est_bwd.hip": ["evrep_est_table.h", "evrep_common.h", "evrep_capi_shared.h"],
-             "evrep_est_prep.hip": ["evrep_common.h", "evrep_capi_shared.h"],
-             "evrep_capi_detin.hip": ["evrep_detin.hip", "evrep_detin_frames.hip", "evrep_common.h", "evrep_capi_shared.h"],
-             "evrep_capi_voxnorm.hip": ["evrep_voxnorm.hip", "evrep_common.h", "evrep_capi_shared.h"],
-             "evrep_capi_decode.hip": ["evrep_decode.hip", "evrep_wave_search.h", "evrep_common.h", "evrep_capi_shared.h"],
-             "evrep_capi_study.hip": ["evrep_study.hip", "evrep_wave_search.h", "evrep_common.h", "evrep_capi_shared.h"]}
+INCLUDE = os.path.join(ROOT, "include")
 OBJDIR = os.path.join(PKG, "_obj")
 
 # -ffp-contract=off: the parity contract is bit-exactness with the reference's separate
@@ -42,12 +29,24 @@ def hipcc():
     return exe
 
 
-def _mtime(d):
-    return os.path.getmtime(d if os.path.isabs(d) else os.path.join(CSRC, d))
+_QUOTED_INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
 
 
-def _unit_deps(src):
-    return [src] + UNIT_DEPS[src] + [os.path.join(ROOT, "include", "evrep.h")]
+def unit_deps(src):
+    """The files the translation unit `src` is compiled from, as paths: the source and, transitively, what it names in
+    #include "..." lines, looked up in csrc/ and then in include/ as the compiler does.  System includes are not followed."""
+    deps, todo = [], [os.path.join(CSRC, src)]
+    while todo:
+        path = todo.pop()
+        if path in deps:
+            continue
+        deps.append(path)
+        with open(path) as f:
+            names = _QUOTED_INCLUDE.findall(f.read())
+        for name in names:
+            found = [p for p in (os.path.join(CSRC, name), os.path.join(INCLUDE, name)) if os.path.exists(p)]
+            todo.extend(found[:1])
+    return deps
 
 
 def _obj(src, tag=""):
@@ -74,7 +73,7 @@ def needs_build(extra_flags=(), lib=LIB):
     except OSError:
         pass        # a library that travelled without its stamp (the GPU box gets the prebuilt .so): trust the mtimes
     t = os.path.getmtime(lib)
-    return any(_mtime(d) > t for src in SOURCES for d in _unit_deps(src))
+    return any(os.path.getmtime(d) > t for src in SOURCES for d in unit_deps(src))
 
 
 class _BuildLock:
@@ -107,7 +106,7 @@ def build(force=False, verbose=True, extra_flags=(), lib=LIB):
         todo = []
         for src in SOURCES:
             o = _obj(src, tag)
-            if force or not os.path.exists(o) or any(_mtime(d) > os.path.getmtime(o) for d in _unit_deps(src)):
+            if force or not os.path.exists(o) or any(os.path.getmtime(d) > os.path.getmtime(o) for d in unit_deps(src)):
                 todo.append((o, [hipcc()] + FLAGS + extra_flags + ["-I", os.path.join(ROOT, "include"), "-I", CSRC, "-c",
                                                                    os.path.join(CSRC, src)]))
 

@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr, stream_ptr, want
 from .gwd_pipeline import letterbox, resize_batch, resize_taps  # noqa: F401  (letterbox: re-exported under the reference's name)
 
 AB_BITS = 10                      # OpenCV's fixed point of the inverse map
@@ -223,9 +224,8 @@ def _pad_table(pad, C, device):
 def device_tables(flags, warp, B, S, device):
     """(B,) flags and (B, 4, S) warp tables as the int32 device tensors the launch reads; device tensors pass through."""
     if torch.is_tensor(flags) and torch.is_tensor(warp):
-        if flags.dtype != torch.int32 or warp.dtype != torch.int32 or flags.numel() != B or warp.numel() != B * 4 * S:
-            raise ValueError("detector_input: flags (B,) and warp (B, 4, S) as int32 tensors")
-        return flags.to(device).contiguous(), warp.to(device).contiguous()
+        flags, warp = flags.to(device).contiguous(), warp.to(device).contiguous()
+        return want(flags, "detector_input: flags", torch.int32, numel=B), want(warp, "detector_input: warp", torch.int32, numel=B * 4 * S)
     flags_d = torch.from_numpy(np.ascontiguousarray(np.asarray(flags, dtype=np.uint32).reshape(B)).view(np.int32)).to(device)
     warp_d = torch.from_numpy(np.ascontiguousarray(np.asarray(warp, dtype=np.int32).reshape(B, 4, S))).to(device)
     return flags_d, warp_d
@@ -236,7 +236,7 @@ def detector_input(rep, img_size, row_taps, col_taps, nh, nw, top, left, pad=114
     """One launch of evrep_detector_input.  rep: (B, H, W, C) float64/float32 CUDA tensor; row_taps / col_taps: (start, count,
     weights, T) device tables for the ``nh`` rows and ``nw`` columns of the resized rectangle; flags: (B,) uint32 values
     (_lib.DETIN_*) with warp: (B, 4, S) int32 tables (numpy, or int32 device tensors that are used as they are), or both None.  Returns the (B, C, S, S) float32 tensor."""
-    lib = _lib.load()
+    api = _lib.api()
     if not rep.is_cuda:
         raise _lib.EvrepError("detector_input needs a CUDA tensor; there is no CPU fallback")
     if rep.dtype not in (torch.float64, torch.float32):
@@ -255,12 +255,10 @@ def detector_input(rep, img_size, row_taps, col_taps, nh, nw, top, left, pad=114
         flags_d, warp_d = device_tables(flags, warp, B, S, dev)
     if out is None:
         out = torch.empty((B, C, S, S), dtype=torch.float32, device=dev)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
     with torch.cuda.device(dev):
-        _lib.check(lib.evrep_detector_input(ptr(rep), _lib.F64 if rep.dtype == torch.float64 else _lib.F32, B, H, W, C, int(nh), int(nw),
-                                            T, ptr(ys), ptr(yc), ptr(yw), ptr(xs), ptr(xc), ptr(xw), S, int(top), int(left), ptr(pad_d),
-                                            ptr(flags_d), ptr(warp_d), 1.0 if scale is None else float(scale), ptr(out),
-                                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "evrep_detector_input")
+        api.evrep_detector_input(ptr(rep), _lib.F64 if rep.dtype == torch.float64 else _lib.F32, B, H, W, C, int(nh), int(nw), T, ptr(ys),
+                                 ptr(yc), ptr(yw), ptr(xs), ptr(xc), ptr(xw), S, int(top), int(left), ptr(pad_d), ptr(flags_d),
+                                 ptr(warp_d), 1.0 if scale is None else float(scale), ptr(out), stream_ptr())
     return out
 
 
@@ -529,8 +527,8 @@ class DetectorFrontEnd:
         dev = frames[0].device
         if out is None:
             out = torch.empty((B, C, S, S), dtype=torch.float32, device=dev)
-        elif tuple(out.shape) != (B, C, S, S) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-            raise ValueError("prepare_frames: out must be a contiguous float32 tensor of shape %r on %s" % ((B, C, S, S), dev))
+        else:
+            want(out, "prepare_frames: out", torch.float32, (B, C, S, S), device=dev)
         if params is None:
             params = self.draw(B)
         table, host, n_axes, max_dst, rows_total, wt_total = self.frame_tables(sizes, geos, params)
@@ -538,26 +536,22 @@ class DetectorFrontEnd:
         keep = [f if f.is_contiguous() else f.contiguous() for f in frames]
         table["src"] = [f.data_ptr() for f in keep]
         has_warp = host.size > n_axes * _lib.TAPS_AXIS_FIELDS
-        lib = _lib.load()
+        api = _lib.api()
         up = torch.from_numpy(host).to(dev)                                    # the one upload
         axes_d = up[:n_axes * _lib.TAPS_AXIS_FIELDS]
         warp_d = up[n_axes * _lib.TAPS_AXIS_FIELDS:] if has_warp else None
         idx = torch.empty(2 * rows_total, dtype=torch.int32, device=dev)
         start_d, count_d = idx[:rows_total], idx[rows_total:]
         wt_d = torch.empty(wt_total, dtype=torch.float64, device=dev)
-        frames_d = torch.empty(int(lib.evrep_detector_input_frames_scratch_bytes(B)) // 8, dtype=torch.int64, device=dev)
+        frames_d = torch.empty(api.evrep_detector_input_frames_scratch_bytes(B) // 8, dtype=torch.int64, device=dev)
         pad_d = _pad_table(pad, C, dev)
         images = out
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _lib.check(lib.evrep_resize_tap_tables(ptr(axes_d), n_axes, max_dst, ptr(start_d), ptr(count_d), ptr(wt_d),
-                                                   rows_total, wt_total, stream), "evrep_resize_tap_tables")
-            _lib.check(lib.evrep_detector_input_frames(ctypes.c_void_p(table.ctypes.data), B,
-                                                       _lib.F64 if frames[0].dtype == torch.float64 else _lib.F32, C, S, ptr(start_d),
-                                                       ptr(count_d), ptr(wt_d), rows_total, wt_total, ptr(pad_d), ptr(warp_d),
-                                                       1.0 if scale is None else float(scale), ptr(frames_d), ptr(images), stream),
-                       "evrep_detector_input_frames")
+            stream = stream_ptr()
+            api.evrep_resize_tap_tables(ptr(axes_d), n_axes, max_dst, ptr(start_d), ptr(count_d), ptr(wt_d), rows_total, wt_total, stream)
+            api.evrep_detector_input_frames(ctypes.c_void_p(table.ctypes.data), B, _lib.F64 if frames[0].dtype == torch.float64 else _lib.F32,
+                                            C, S, ptr(start_d), ptr(count_d), ptr(wt_d), rows_total, wt_total, ptr(pad_d), ptr(warp_d),
+                                            1.0 if scale is None else float(scale), ptr(frames_d), ptr(images), stream)
         return images, targets, shapes
 
 
@@ -573,7 +567,7 @@ def area_taps_bound(src, dst):
 def resize_tap_tables(axes, device):
     """One launch of evrep_resize_tap_tables for ``axes``, a list of (src, dst, interpolation, T) with interpolation "linear" /
     "area" / "identity".  Returns per axis the (start, count, weights, T) device tables, views into three tensors."""
-    lib = _lib.load()
+    api = _lib.api()
     codes = {"linear": _lib.TAPS_LINEAR, "area": _lib.TAPS_AREA, "identity": _lib.TAPS_IDENTITY}
     desc, rows, wts = [], 0, 0
     for src, dst, interp, T in axes:
@@ -583,8 +577,6 @@ def resize_tap_tables(axes, device):
     start = torch.empty(rows, dtype=torch.int32, device=device)
     count = torch.empty(rows, dtype=torch.int32, device=device)
     wt = torch.empty(wts, dtype=torch.float64, device=device)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
     with torch.cuda.device(device):
-        _lib.check(lib.evrep_resize_tap_tables(ptr(axes_d), len(desc), max(d[1] for d in desc), ptr(start), ptr(count), ptr(wt), rows, wts,
-                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "evrep_resize_tap_tables")
+        api.evrep_resize_tap_tables(ptr(axes_d), len(desc), max(d[1] for d in desc), ptr(start), ptr(count), ptr(wt), rows, wts, stream_ptr())
     return [(start[r:r + dst], count[r:r + dst], wt[w:w + dst * T].view(dst, T), T) for (_, dst, _, T, r, w) in desc]

@@ -15,23 +15,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Plan, check
-
-
-def _require_gpu():
-    if not torch.cuda.is_available():
-        raise _lib.EvrepError("no HIP device visible: the builders run on an MI355X only (no CPU fallback)")
-
+from ._lib import Plan, want
+from ._lib import ptr as _ptr, require_gpu as _require_gpu, stream_ptr as _stream_ptr
 
 _NO_GUARD = contextlib.nullcontext()
-
-
-def _stream_ptr():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 class EventBatch:
@@ -45,10 +32,8 @@ class EventBatch:
 
     def __init__(self, events, offsets, height, width, max_events_per_window=None, plan_flags=None, pacing=None):
         _require_gpu()
-        self.lib = _lib.load()
-        if events.dtype != torch.int32 or events.dim() != 2 or events.shape[1] != 4 or not events.is_cuda:
-            raise ValueError("events must be a (total, 4) int32 CUDA tensor")
-        self.events = events.contiguous()
+        self.lib, self.api = _lib.load(), _lib.api()      # .lib: the raw C ABI (bench.py, tests, tools); .api: what this package calls
+        self.events = want(events.contiguous(), "events", torch.int32, (None, 4), device="cuda")
         self.device = events.device
         off_host = offsets.detach().cpu().to(torch.int64) if isinstance(offsets, torch.Tensor) else \
             torch.as_tensor(np.asarray(offsets, dtype=np.int64))
@@ -61,13 +46,11 @@ class EventBatch:
         self.total = int(self.events.shape[0])
         self.plan = Plan()
         flags = _lib.plan_flags_from_env() if plan_flags is None else int(plan_flags)
-        check(self.lib.evrep_plan_init_ex(ctypes.byref(self.plan), self.B, self.H, self.W, self.total,
-                                          int(max_events_per_window), flags), "evrep_plan_init_ex")
+        self.api.evrep_plan_init_ex(ctypes.byref(self.plan), self.B, self.H, self.W, self.total, int(max_events_per_window), flags)
         pacing = _lib.pacing_from_env() if pacing is None else int(pacing)
         if pacing is not None:
-            check(self.lib.evrep_plan_set_pacing(ctypes.byref(self.plan), pacing), "evrep_plan_set_pacing")
-        nbytes = int(self.lib.evrep_workspace_bytes(ctypes.byref(self.plan)))
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self.api.evrep_plan_set_pacing(ctypes.byref(self.plan), pacing)
+        self.workspace = _lib.scratch(self.api.evrep_workspace_bytes(ctypes.byref(self.plan)), self.device)
         self._binned = False
         self.t_base = None      # numpy int64 (B,): absolute time of t == 0 per window, set by DeviceRecording.windows; no builder reads it
         # The per-sample wrappers (representations/_common.py) keep one pooled batch per (host thread, device, stream) and only use
@@ -100,11 +83,15 @@ class EventBatch:
     def _args(self):
         return ctypes.byref(self.plan), _ptr(self.events), _ptr(self.offsets), _ptr(self.workspace)
 
+    def _launch(self, fn, *args):
+        """fn(plan, events, offsets, workspace, *args, stream) with the batch's device current."""
+        with self._dev():
+            return fn(*self._args(), *args, self._sp())
+
     def bin(self):
         """Run the (y,x) binning pass (idempotent)."""
         if not self._binned:
-            with self._dev():
-                check(self.lib.evrep_bin_events(*self._args(), self._sp()), "evrep_bin_events")
+            self._launch(self.api.evrep_bin_events)
             self._binned = True
         return self
 
@@ -117,8 +104,7 @@ class EventBatch:
         self.bin()
         st = np.zeros(self.B, dtype=np.uint32)
         with self._dev():
-            check(self.lib.evrep_read_status(ctypes.byref(self.plan), _ptr(self.workspace),
-                                             st.ctypes.data_as(ctypes.c_void_p), self._sp()), "evrep_read_status")
+            self.api.evrep_read_status(ctypes.byref(self.plan), _ptr(self.workspace), st.ctypes.data, self._sp())
         return st
 
     def check_built(self, what="builder"):
@@ -136,8 +122,7 @@ class EventBatch:
         self.bin()
         bb = np.zeros((self.B, 4), dtype=np.int32)
         with self._dev():
-            check(self.lib.evrep_read_bbox(ctypes.byref(self.plan), _ptr(self.workspace),
-                                           bb.ctypes.data_as(ctypes.c_void_p), self._sp()), "evrep_read_bbox")
+            self.api.evrep_read_bbox(ctypes.byref(self.plan), _ptr(self.workspace), bb.ctypes.data, self._sp())
         return bb
 
     # ------------------------------------------------------------------ builders
@@ -145,9 +130,7 @@ class EventBatch:
         shape = (self.B, self.H, self.W, C)
         if out is None:
             return torch.empty(shape, dtype=dtype, device=self.device)
-        if tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != self.device:
-            raise ValueError("out must be a contiguous %s tensor of shape %r on %s" % (dtype, shape, self.device))
-        return out
+        return want(out, "out", dtype, shape, device=self.device)
 
     @staticmethod
     def _dt(dtype):
@@ -163,8 +146,8 @@ class EventBatch:
         bounds = torch.empty((self.B, 8, 2), dtype=torch.int32, device=self.device)
         flags = torch.empty((self.B, 2), dtype=torch.int32, device=self.device)
         with self._dev():
-            check(self.lib.evrep_mdes_sbt_windows(_ptr(self.events), _ptr(self.offsets), self.B, self.H, self.W,
-                                                  _ptr(bounds), _ptr(flags), self._sp()), "evrep_mdes_sbt_windows")
+            self.api.evrep_mdes_sbt_windows(_ptr(self.events), _ptr(self.offsets), self.B, self.H, self.W, _ptr(bounds), _ptr(flags),
+                                            self._sp())
         return bounds, flags
 
     def mdes(self, windows, funcs, aggs, scale=1.0, dtype=torch.float64, out=None, stacking="SBN"):
@@ -180,13 +163,9 @@ class EventBatch:
         a = [-1 if v is None else (_lib.AGGS.index(v) if isinstance(v, str) else int(v)) for v in aggs]
         if C <= _lib.MAX_CHANNELS:
             out = self._out(out, C, dtype)
-            null = ctypes.c_void_p(None)
             bounds, flags = self.sbt_windows() if stacking == "SBT" else (None, None)
-            with self._dev():
-                check(self.lib.evrep_mdes_ex(*self._args(), C, _lib.int32_array(w), _lib.int32_array(f),
-                                             _lib.int32_array(a), float(scale), self._dt(dtype), _ptr(out),
-                                             _ptr(bounds) if bounds is not None else null,
-                                             _ptr(flags) if flags is not None else null, self._sp()), "evrep_mdes_ex")
+            self._launch(self.api.evrep_mdes_ex, C, _lib.int32_array(w), _lib.int32_array(f), _lib.int32_array(a), float(scale),
+                         self._dt(dtype), _ptr(out), _ptr(bounds), _ptr(flags))
             return out
         parts = [self.mdes(w[i:i + 16], f[i:i + 16], a[i:i + 16], scale, dtype, stacking=stacking) for i in range(0, C, 16)]
         res = torch.cat(parts, dim=3)
@@ -199,9 +178,7 @@ class EventBatch:
         """get_optimized_representation (ERGO-12) for every window -> (B, H, W, 12)."""
         self.bin()
         out = self._out(out, 12, dtype)
-        with self._dev():
-            check(self.lib.evrep_optimized(*self._args(), float(scale), self._dt(dtype), _ptr(out), self._sp()),
-                  "evrep_optimized")
+        self._launch(self.api.evrep_optimized, float(scale), self._dt(dtype), _ptr(out))
         return out
 
     def event_stack(self, stack_size=12, premap=True, scale=1.0, out=None):
@@ -210,22 +187,22 @@ class EventBatch:
         already holds the final int8 polarity value (EventStack.pre_stack forms it on the host)."""
         self.bin()
         out = self._out(out, stack_size, torch.float32)
-        with self._dev():
-            check(self.lib.evrep_event_stack(*self._args(), int(stack_size), int(premap), float(scale),
-                                             _ptr(out), self._sp()), "evrep_event_stack")
+        self._launch(self.api.evrep_event_stack, int(stack_size), int(premap), float(scale), _ptr(out))
         return out
 
     def _i32_dev(self, values, per_window):
-        """None -> NULL; else a (B, per_window) int32 device tensor (a list is taken as one row per window)."""
+        """None -> None; else a (B, per_window) int32 device tensor (a list is taken as one row per window)."""
         if values is None:
-            return None, ctypes.c_void_p(None)
+            return None
         t = torch.as_tensor(np.asarray(values, dtype=np.int32)).reshape(-1)
         if t.numel() == per_window and self.B > 1:
             t = t.repeat(self.B)
         if t.numel() != self.B * per_window:
             raise ValueError("expected %d x %d int32 values" % (self.B, per_window))
-        t = t.to(self.device)
-        return t, _ptr(t)
+        return t.to(self.device)
+
+    def _per_event(self, t, what, dtype=torch.float64):
+        return want(t, what, dtype, numel=self.total, device=self.device)
 
     def time_surface(self, slices=6, tau=50000.0, premap=True, scale=1.0, dtype=torch.float64, out=None, indices=None, times_f64=None):
         """ToTimesurface for every window -> (B, H, W, 2*slices), channel c = 2*s + p.  indices=None: the
@@ -234,19 +211,13 @@ class EventBatch:
         needs explicit indices)."""
         self.bin()
         out = self._out(out, 2 * slices, dtype)
-        keep, iptr = self._i32_dev(indices, slices)
-        fptr = ctypes.c_void_p(None)
+        idx = self._i32_dev(indices, slices)
         if times_f64 is not None:      # float64 timestamps, one per event (the events' own t column then only orders them)
-            if times_f64.dtype != torch.float64 or times_f64.device != self.device or times_f64.numel() != self.total \
-                    or not times_f64.is_contiguous():
-                raise ValueError("times_f64 must be a contiguous float64 tensor with one entry per event on %s" % self.device)
+            self._per_event(times_f64, "times_f64")
             if indices is None:
                 raise ValueError("times_f64 needs explicit indices")
-            fptr = _ptr(times_f64)
-        with self._dev():
-            check(self.lib.evrep_time_surface_ftime(*self._args(), int(slices), iptr, fptr, float(tau), int(premap),
-                                              float(scale), self._dt(dtype), _ptr(out), self._sp()),
-                  "evrep_time_surface")
+        self._launch(self.api.evrep_time_surface_ftime, int(slices), _ptr(idx), _ptr(times_f64), float(tau), int(premap),
+                     float(scale), self._dt(dtype), _ptr(out))
         return out
 
     def tore(self, k=6, frame_mode=0, scale=1.0, out=None, sample_times=None, times_f64=None, sample_times_f64=None):
@@ -258,32 +229,21 @@ class EventBatch:
         float64 sample time per window, as a host sequence or as a (B,) float64 tensor already on the batch's device."""
         self.bin()
         out = self._out(out, 2 * k, torch.float32)
-        keep, tptr = self._i32_dev(sample_times, 1)
-        fptr, sfptr, keep_f = ctypes.c_void_p(None), ctypes.c_void_p(None), None
+        st, st_f = self._i32_dev(sample_times, 1), None
         if sample_times_f64 is not None and times_f64 is None:
             # the C ABI rejects the pair (EINVAL); silently falling back to the int32 sample times would return a
             # plausible but different tensor
             raise ValueError("sample_times_f64 needs times_f64 (float64 event times)")
         if times_f64 is not None:      # float64 timestamps, one per event (the events' own t column is then not used)
-            if times_f64.dtype != torch.float64 or times_f64.device != self.device or times_f64.numel() != self.total \
-                    or not times_f64.is_contiguous():
-                raise ValueError("times_f64 must be a contiguous float64 tensor with one entry per event on %s" % self.device)
-            fptr = _ptr(times_f64)
+            self._per_event(times_f64, "times_f64")
             if isinstance(sample_times_f64, torch.Tensor) and sample_times_f64.is_cuda:
                 # made on the device (evrep_nimg_study_rows): taken as it lies, nothing crosses to the host and back
-                keep_f = sample_times_f64
-                if keep_f.dtype != torch.float64 or keep_f.device != self.device or tuple(keep_f.shape) != (self.B,) \
-                        or not keep_f.is_contiguous():
-                    raise ValueError("a device sample_times_f64 must be a contiguous (B,) float64 tensor on %s" % self.device)
-                sfptr = _ptr(keep_f)
+                st_f = want(sample_times_f64, "a device sample_times_f64", torch.float64, (self.B,), device=self.device)
             elif sample_times_f64 is not None:
-                keep_f = torch.as_tensor(np.asarray(sample_times_f64, dtype=np.float64)).reshape(-1).to(self.device)
-                if keep_f.numel() != self.B:
+                st_f = torch.as_tensor(np.asarray(sample_times_f64, dtype=np.float64)).reshape(-1).to(self.device)
+                if st_f.numel() != self.B:
                     raise ValueError("sample_times_f64 must hold one time per window")
-                sfptr = _ptr(keep_f)
-        with self._dev():
-            check(self.lib.evrep_tore_ftime(*self._args(), int(k), int(frame_mode), tptr, fptr, sfptr, float(scale), _ptr(out),
-                                            self._sp()), "evrep_tore_ftime")
+        self._launch(self.api.evrep_tore_ftime, int(k), int(frame_mode), _ptr(st), _ptr(times_f64), _ptr(st_f), float(scale), _ptr(out))
         if frame_mode != 0:
             return out
         bb = self.bbox()
@@ -303,46 +263,36 @@ class EventBatch:
         events_to_voxel_grid (t_range: optional (B, 2) int64 [t0_us, t1_us] per window, mode 2 only)."""
         self.bin()
         out = self._out(out, bins, torch.float64)
-        rptr = ctypes.c_void_p(None)
-        if t_range is not None:
-            tr = torch.as_tensor(np.asarray(t_range, dtype=np.int64)).reshape(-1)
-            if tr.numel() != 2 * self.B:
-                raise ValueError("t_range must hold (t0, t1) for each of the %d windows" % self.B)
-            tr = tr.to(self.device)
-            rptr = _ptr(tr)
-        with self._dev():
-            check(self.lib.evrep_voxel_range(*self._args(), int(bins), int(mode), float(scale), rptr, _ptr(out),
-                                             self._sp()), "evrep_voxel_range")
+        tr = self._t_range(t_range)
+        self._launch(self.api.evrep_voxel_range, int(bins), int(mode), float(scale), _ptr(tr), _ptr(out))
         return out
+
+    def _t_range(self, t_range):
+        """None -> None; else the (B, 2) int64 [t0_us, t1_us] per window as a flat device tensor."""
+        if t_range is None:
+            return None
+        tr = torch.as_tensor(np.asarray(t_range, dtype=np.int64)).reshape(-1)
+        if tr.numel() != 2 * self.B:
+            raise ValueError("t_range must hold (t0, t1) for each of the %d windows" % self.B)
+        return tr.to(self.device)
 
     def voxel_tnorm(self, tnorm, bins=5, scale=1.0, out=None):
         """compute_repr with the caller's own normalised time (gromov_wasserstein.py:72-82) -> (B, H, W, bins) float64.
         tnorm: float64 device tensor, one value per event (indexed like the events)."""
         self.bin()
-        if tnorm.dtype != torch.float64 or tnorm.device != self.device or tnorm.numel() != self.total or not tnorm.is_contiguous():
-            raise ValueError("tnorm must be a contiguous float64 tensor with one entry per event on %s" % self.device)
+        self._per_event(tnorm, "tnorm")
         out = self._out(out, bins, torch.float64)
-        with self._dev():
-            check(self.lib.evrep_voxel_tnorm(*self._args(), _ptr(tnorm), int(bins), float(scale), _ptr(out), self._sp()),
-                  "evrep_voxel_tnorm")
+        self._launch(self.api.evrep_voxel_tnorm, _ptr(tnorm), int(bins), float(scale), _ptr(out))
         return out
 
     def voxel_subpixel(self, xy, bins=5, t_range=None, out=None):
         """ev-licious events_to_voxel_grid for sub-pixel coordinates -> (B, H, W, bins) float32.  The batch holds the
         truncated coordinates; xy: (total, 2) float64 device tensor with every event's original (x, y)."""
         self.bin()
-        if xy.dtype != torch.float64 or xy.device != self.device or tuple(xy.shape) != (self.total, 2) or not xy.is_contiguous():
-            raise ValueError("xy must be a contiguous (total, 2) float64 tensor on %s" % self.device)
+        want(xy, "xy", torch.float64, (self.total, 2), device=self.device)
         out = self._out(out, bins, torch.float32)
-        rptr, keep = ctypes.c_void_p(None), None
-        if t_range is not None:
-            keep = torch.as_tensor(np.asarray(t_range, dtype=np.int64)).reshape(-1).to(self.device)
-            if keep.numel() != 2 * self.B:
-                raise ValueError("t_range must hold (t0, t1) for each of the %d windows" % self.B)
-            rptr = _ptr(keep)
-        with self._dev():
-            check(self.lib.evrep_voxel_subpixel(*self._args(), _ptr(xy), int(bins), rptr, _ptr(out), self._sp()),
-                  "evrep_voxel_subpixel")
+        tr = self._t_range(t_range)
+        self._launch(self.api.evrep_voxel_subpixel, _ptr(xy), int(bins), _ptr(tr), _ptr(out))
         return out
 
     def evl_voxel_grid(self, num_bins, normalize=True, t_range=None, xy=None, out=None, return_stats=False):
@@ -372,60 +322,44 @@ class EventBatch:
         stat = np.ascontiguousarray(stat, dtype=np.int32)
         if pol.shape != stat.shape or pol.ndim != 1:
             raise ValueError("pol and stat must be 1-D and of equal length")
-        if tnorm.dtype != torch.float64 or tnorm.device != self.device or tnorm.numel() != self.total \
-                or not tnorm.is_contiguous():
-            raise ValueError("tnorm must be a contiguous float64 tensor with one entry per event on %s" % self.device)
+        self._per_event(tnorm, "tnorm")
         out = self._out(out, len(pol), torch.float32)
-        with self._dev():
-            check(self.lib.evrep_polstats(*self._args(), _ptr(tnorm), len(pol), pol.ctypes.data_as(ctypes.c_void_p),
-                                          stat.ctypes.data_as(ctypes.c_void_p), float(tau), _ptr(out), self._sp()),
-                  "evrep_polstats")
+        self._launch(self.api.evrep_polstats, _ptr(tnorm), len(pol), pol.ctypes.data, stat.ctypes.data, float(tau), _ptr(out))
         return out
+
+    def _est_inputs(self, tnorm, segments, buckets):
+        self._per_event(tnorm, "tnorm", torch.float32)
+        want(segments, "segments", torch.float64, (None, 3), device=self.device)
+        want(buckets, "buckets", torch.int32, device=self.device)
 
     def est_voxel(self, tnorm, C, segments, buckets, lo, hi, out=None):
         """EST quantisation layer forward (learned_repr.py:143-179) -> (B, H, W, 2C) float32; the value MLP is
         passed as its piecewise-linear table (est.PiecewiseLinearKernel.device_table)."""
         self.bin()
-        if tnorm.dtype != torch.float32 or tnorm.device != self.device or tnorm.numel() != self.total \
-                or not tnorm.is_contiguous():
-            raise ValueError("tnorm must be a contiguous float32 tensor with one entry per event on %s" % self.device)
-        if segments.dtype != torch.float64 or segments.dim() != 2 or segments.shape[1] != 3 or buckets.dtype != torch.int32:
-            raise ValueError("segments must be float64 (nseg, 3), buckets int32")
+        self._est_inputs(tnorm, segments, buckets)
         out = self._out(out, 2 * int(C), torch.float32)
-        with self._dev():
-            check(self.lib.evrep_est_voxel(*self._args(), _ptr(tnorm), int(C), _ptr(segments), int(segments.shape[0]),
-                                           _ptr(buckets), int(buckets.numel()), float(lo), float(hi), _ptr(out),
-                                           self._sp()), "evrep_est_voxel")
+        self._launch(self.api.evrep_est_voxel, _ptr(tnorm), int(C), _ptr(segments), int(segments.shape[0]), _ptr(buckets),
+                     int(buckets.numel()), float(lo), float(hi), _ptr(out))
         return out
 
     def est_voxel_backward(self, tnorm, C, segments, buckets, lo, hi, grad_out):
         """The gradient of a loss with respect to the (a, c) columns of the table ``est_voxel`` was called with, from
         ``grad_out`` = dL/d est_voxel (B, H, W, 2C) float32 contiguous -> (nseg, 2) float64 {dL/da, dL/dc}.  A keyed
         float64 reduction over the events in array order (no binning pass); bit-reproducible between calls."""
-        if tnorm.dtype != torch.float32 or tnorm.device != self.device or tnorm.numel() != self.total \
-                or not tnorm.is_contiguous():
-            raise ValueError("tnorm must be a contiguous float32 tensor with one entry per event on %s" % self.device)
-        if segments.dtype != torch.float64 or segments.dim() != 2 or segments.shape[1] != 3 or buckets.dtype != torch.int32 \
-                or not segments.is_contiguous() or not buckets.is_contiguous():
-            raise ValueError("segments must be contiguous float64 (nseg, 3), buckets contiguous int32")
+        self._est_inputs(tnorm, segments, buckets)
         nseg = int(segments.shape[0])
         if not 1 <= nseg <= _lib.EST_BWD_MAX_SEG:
             raise ValueError("the table has %d pieces; the backward holds at most EVREP_EST_BWD_MAX_SEG = %d"
                              % (nseg, _lib.EST_BWD_MAX_SEG))
-        shape = (self.B, self.H, self.W, 2 * int(C))
-        if tuple(grad_out.shape) != shape or grad_out.dtype != torch.float32 or grad_out.device != self.device \
-                or not grad_out.is_contiguous():
-            raise ValueError("grad_out must be a contiguous float32 tensor of shape %r on %s" % (shape, self.device))
+        want(grad_out, "grad_out", torch.float32, (self.B, self.H, self.W, 2 * int(C)), device=self.device)
         grad = torch.empty((nseg, 2), dtype=torch.float64, device=self.device)
         if self.total == 0:
             return grad.zero_()
-        scratch = torch.empty(int(self.lib.evrep_est_backward_scratch_bytes(self.total, nseg)), dtype=torch.uint8,
-                              device=self.device)
+        scratch = _lib.scratch(self.api.evrep_est_backward_scratch_bytes(self.total, nseg), self.device)
         with self._dev():
-            check(self.lib.evrep_est_voxel_backward(_ptr(self.events), _ptr(self.offsets), self.B, self.H, self.W, _ptr(tnorm),
-                                                    int(C), _ptr(segments), nseg, _ptr(buckets), int(buckets.numel()),
-                                                    float(lo), float(hi), _ptr(grad_out), _ptr(grad), _ptr(scratch),
-                                                    self._sp()), "evrep_est_voxel_backward")
+            self.api.evrep_est_voxel_backward(_ptr(self.events), _ptr(self.offsets), self.B, self.H, self.W, _ptr(tnorm), int(C),
+                                              _ptr(segments), nseg, _ptr(buckets), int(buckets.numel()), float(lo), float(hi),
+                                              _ptr(grad_out), _ptr(grad), _ptr(scratch), self._sp())
         return grad
 
     # ------------------------------------------------------------------ event filters (ev-licious tools/filters.py)
@@ -437,18 +371,16 @@ class EventBatch:
         shape = (self.B, self.H, self.W)
         if state is None:
             return torch.full(shape, fill, dtype=dtype, device=self.device)
-        if tuple(state.shape) != shape or state.dtype != dtype or not state.is_contiguous() or state.device != self.device:
-            raise ValueError("state must be a contiguous %s tensor of shape %r on %s" % (dtype, shape, self.device))
-        return state
+        return want(state, "state", dtype, shape, device=self.device)
 
     def _t_base(self, t_base):
         """None -> NULL; else one absolute int64 time per window (a scalar serves every window), kept alive on the batch."""
         if t_base is None:
             self._t_base_host = None
-            return ctypes.c_void_p(None)
+            return None
         tb = np.ascontiguousarray(np.broadcast_to(np.asarray(t_base, dtype=np.int64).reshape(-1), (self.B,)))
         self._t_base_host = tb
-        return tb.ctypes.data_as(ctypes.c_void_p)
+        return tb.ctypes.data
 
     def _filter_fsm(self, kind, param, state, dtype, fill, t_base=None):
         if not float(param) > 0:
@@ -456,9 +388,7 @@ class EventBatch:
         self.bin()
         state = self._filter_state(state, dtype, fill)
         keep = torch.empty(self.total, dtype=torch.uint8, device=self.device)
-        with self._dev():
-            check(self.lib.evrep_filter_pixel_fsm(*self._args(), int(kind), float(param), self._t_base(t_base), _ptr(state),
-                                                  _ptr(keep), self._sp()), "evrep_filter_pixel_fsm")
+        self._launch(self.api.evrep_filter_pixel_fsm, int(kind), float(param), self._t_base(t_base), _ptr(state), _ptr(keep))
         return keep, state
 
     def filter_refractory(self, period, state=None, t_base=None):
@@ -476,9 +406,7 @@ class EventBatch:
         self.bin()
         state = self._filter_state(state, torch.float64, -np.inf)
         keep = torch.empty(self.total, dtype=torch.uint8, device=self.device)
-        with self._dev():
-            check(self.lib.evrep_filter_background(*self._args(), float(depth_us), int(radius), self._t_base(t_base), _ptr(state),
-                                                   _ptr(keep), self._sp()), "evrep_filter_background")
+        self._launch(self.api.evrep_filter_background, float(depth_us), int(radius), self._t_base(t_base), _ptr(state), _ptr(keep))
         return keep, state
 
     def filter_resize(self, height, width, state=None):
@@ -492,8 +420,7 @@ class EventBatch:
         ev = torch.empty_like(self.events)
         if self.total:
             with self._dev():
-                check(self.lib.evrep_filter_cell_map(_ptr(self.events), self.total, self.H, self.W, fy, fx, _ptr(ev), self._sp()),
-                      "evrep_filter_cell_map")
+                self.api.evrep_filter_cell_map(_ptr(self.events), self.total, self.H, self.W, fy, fx, _ptr(ev), self._sp())
         cells = EventBatch(ev, self.offsets_host, self.H // fy, self.W // fx,
                            max_events_per_window=int(self.plan.max_events_per_window), plan_flags=int(self.plan.flags))
         cells._pinned_stream = self._pinned_stream
@@ -513,9 +440,8 @@ class EventBatch:
         keep = torch.empty(self.total, dtype=torch.uint8, device=self.device)
         if self.total:
             with self._dev():
-                check(self.lib.evrep_filter_mask_gather(_ptr(self.events), _ptr(self.offsets), self.B, self.H, self.W,
-                                                        int(self.plan.max_events_per_window), _ptr(m), _ptr(keep), self._sp()),
-                      "evrep_filter_mask_gather")
+                self.api.evrep_filter_mask_gather(_ptr(self.events), _ptr(self.offsets), self.B, self.H, self.W,
+                                                  int(self.plan.max_events_per_window), _ptr(m), _ptr(keep), self._sp())
         return keep, m
 
     def pixel_counts(self):
@@ -527,16 +453,14 @@ class EventBatch:
         """The kept rows of every window, in order, as a new EventBatch on the same device and stream (ready for
         .optimized() / .tore() / ...).  The compaction and the new offsets are formed on the device; ONE host
         synchronisation follows: the read of the new offsets, which sizes the new batch's plan."""
-        if keep.dtype != torch.uint8 or keep.numel() != self.total or keep.device != self.device or not keep.is_contiguous():
-            raise ValueError("keep must be a contiguous uint8 tensor with one entry per event on %s" % self.device)
+        self._per_event(keep, "keep", torch.uint8)
         off_out = torch.zeros(self.B + 1, dtype=torch.int64, device=self.device)
         ev_out = torch.empty((max(self.total, 1), 4), dtype=torch.int32, device=self.device)
         if self.total:
-            scratch = torch.empty(int(self.lib.evrep_filter_compact_scratch_bytes(self.B, self.total)), dtype=torch.uint8,
-                                  device=self.device)
+            scratch = _lib.scratch(self.api.evrep_filter_compact_scratch_bytes(self.B, self.total), self.device)
             with self._dev():
-                check(self.lib.evrep_filter_compact(_ptr(self.events), _ptr(self.offsets), self.B, _ptr(keep), _ptr(ev_out),
-                                                    _ptr(off_out), _ptr(scratch), self._sp()), "evrep_filter_compact")
+                self.api.evrep_filter_compact(_ptr(self.events), _ptr(self.offsets), self.B, _ptr(keep), _ptr(ev_out), _ptr(off_out),
+                                              _ptr(scratch), self._sp())
         off_host = off_out.cpu()
         out = EventBatch(ev_out[: int(off_host[-1])], off_host, self.H, self.W, plan_flags=int(self.plan.flags))
         out._pinned_stream = self._pinned_stream
@@ -544,9 +468,8 @@ class EventBatch:
 
 
 def _check_evl_out(out, shape, device):
-    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != torch.float32
-                            or not out.is_contiguous() or out.device != device):
-        raise ValueError("out must be a contiguous torch.float32 tensor of shape %r on %s" % (tuple(shape), device))
+    if out is not None:
+        want(out, "out", torch.float32, shape, device=device)
 
 
 def voxel_normalize(grid, normalize=True, out=None, return_stats=False, stream=None):
@@ -555,9 +478,8 @@ def voxel_normalize(grid, normalize=True, out=None, return_stats=False, stream=N
     else only cast and transposed.  return_stats: also (B, 4) float64 {n, mean, std, applied}.  Three launches on the current
     stream (`stream`: a stream pointer the caller has pinned), no read-back."""
     _require_gpu()
-    lib = _lib.load()
-    if not isinstance(grid, torch.Tensor) or not grid.is_cuda or grid.dim() != 4 or not grid.is_contiguous():
-        raise ValueError("grid must be a contiguous (B, H, W, bins) CUDA tensor")
+    api = _lib.api()
+    want(grid, "grid", (torch.float64, torch.float32), (None, None, None, None), device="cuda")
     B, H, W, bins = (int(v) for v in grid.shape)
     _check_evl_out(out, (B, bins, H, W), grid.device)
     if return_stats and not normalize:
@@ -566,15 +488,10 @@ def voxel_normalize(grid, normalize=True, out=None, return_stats=False, stream=N
     if out is None:
         out = torch.empty((B, bins, H, W), dtype=torch.float32, device=grid.device)
     stats = torch.empty((B, 4), dtype=torch.float64, device=grid.device) if return_stats else None
-    null = ctypes.c_void_p(None)
-    scratch = None
-    if normalize:
-        scratch = torch.empty(max(int(lib.evrep_voxel_normalize_scratch_bytes(B, H, W, bins)), 16), dtype=torch.uint8,
-                              device=grid.device)
+    scratch = _lib.scratch(max(api.evrep_voxel_normalize_scratch_bytes(B, H, W, bins), 16), grid.device) if normalize else None
     with torch.cuda.device(grid.device) if stream is None else _NO_GUARD:
-        check(lib.evrep_voxel_normalize(_ptr(grid), dt, B, H, W, bins, _lib.VOXNORM_NORMALIZE if normalize else 0, _ptr(out),
-                                        _ptr(stats) if return_stats else null, _ptr(scratch) if normalize else null,
-                                        _stream_ptr() if stream is None else stream), "evrep_voxel_normalize")
+        api.evrep_voxel_normalize(_ptr(grid), dt, B, H, W, bins, _lib.VOXNORM_NORMALIZE if normalize else 0, _ptr(out), _ptr(stats),
+                                  _ptr(scratch), _stream_ptr() if stream is None else stream)
     return (out, stats) if return_stats else out
 
 
@@ -585,22 +502,22 @@ def est_prepare(events5, B, H, W):
     ``packed``, (B + 2,) int64 (status is the low half of its last word), so one small copy brings both to the host.
     Asynchronous on the current stream: nothing is read back here."""
     _require_gpu()
-    lib = _lib.load()
-    if not isinstance(events5, torch.Tensor) or not events5.is_cuda or events5.dtype != torch.float32 or events5.dim() != 2 \
-            or events5.shape[1] != 5 or events5.shape[0] == 0 or not events5.is_contiguous():
-        raise ValueError("events5 must be a non-empty contiguous (n, 5) float32 CUDA tensor")
+    api = _lib.api()
+    want(events5, "events5", torch.float32, (None, 5), device="cuda")
     n, B, dev = int(events5.shape[0]), int(B), events5.device
-    nbytes = int(lib.evrep_est_prepare_scratch_bytes(n, B))
+    if n == 0:
+        raise ValueError("events5 must be non-empty")
+    nbytes = api.evrep_est_prepare_scratch_bytes(n, B)
     if nbytes == 0:
         raise ValueError("1 <= B <= %d batch items, got %d" % (_lib.EST_PREP_MAX_B, B))
     rows = torch.empty((n, 4), dtype=torch.int32, device=dev)
     tnorm = torch.empty(n, dtype=torch.float32, device=dev)
     packed = torch.empty(B + 2, dtype=torch.int64, device=dev)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    scratch = _lib.scratch(nbytes, dev)
     offsets, status = packed[:B + 1], packed[B + 1:].view(torch.int32)[:1]
     with torch.cuda.device(dev):
-        check(lib.evrep_est_prepare(_ptr(events5), n, B, int(H), int(W), _ptr(rows), _ptr(offsets), _ptr(tnorm), _ptr(status),
-                                    _ptr(scratch), _stream_ptr()), "evrep_est_prepare")
+        api.evrep_est_prepare(_ptr(events5), n, B, int(H), int(W), _ptr(rows), _ptr(offsets), _ptr(tnorm), _ptr(status), _ptr(scratch),
+                              _stream_ptr())
     return rows, offsets, tnorm, status, packed
 
 
@@ -683,11 +600,10 @@ def probe_output_placement(shape, dtype, launch=None, candidates=8, launches=10,
     keep_first: also return the FIRST candidate (what a caller that does not probe would have got), as a 4th element."""
     _require_gpu()
     device = torch.device(device)
-    lib = _lib.load()
     if launch is None:
         def launch(o):
             with torch.cuda.device(device):
-                check(lib.evrep_probe_store(_ptr(o), o.numel() * o.element_size(), _stream_ptr()), "evrep_probe_store")
+                _lib.api().evrep_probe_store(_ptr(o), o.numel() * o.element_size(), _stream_ptr())
     outs, times = [], []
     limit = int(max_candidates) if max_candidates else int(candidates)
     while len(outs) < limit:
@@ -718,23 +634,18 @@ def gwd_padded_l1(Xs, Xt, h=0.7, out=None):
     `out`: optional one-element float64 cuda tensor (e.g. ``costs[i:i+1]``) the kernel writes into directly --
     no host synchronisation, so a list of solves queues back to back."""
     _require_gpu()
-    lib = _lib.load()
+    api = _lib.api()
     dev = Xs.device if isinstance(Xs, torch.Tensor) and Xs.is_cuda else torch.device("cuda", torch.cuda.current_device())
     a = torch.as_tensor(np.asarray(Xs) if not isinstance(Xs, torch.Tensor) else Xs).to(dev, torch.float64).contiguous()
     b = torch.as_tensor(np.asarray(Xt) if not isinstance(Xt, torch.Tensor) else Xt).to(dev, torch.float64).contiguous()
     if a.dim() != 2 or b.dim() != 2 or a.shape[0] == 0 or b.shape[0] == 0:
         raise ValueError("Xs and Xt must be non-empty 2-D point clouds")
     n, m = int(a.shape[0]), int(b.shape[0])
-    scratch = torch.empty(int(lib.evrep_gwd_scratch_bytes(n, m)), dtype=torch.uint8, device=dev)
-    if out is not None:
-        if out.dtype != torch.float64 or out.numel() != 1 or not out.is_cuda:
-            raise ValueError("out must be a one-element float64 CUDA tensor")
-        cost = out
-    else:
-        cost = torch.empty((), dtype=torch.float64, device=dev)
+    scratch = _lib.scratch(api.evrep_gwd_scratch_bytes(n, m), dev)
+    cost = torch.empty((), dtype=torch.float64, device=dev) if out is None else want(out, "out", torch.float64, numel=1, device="cuda")
     with torch.cuda.device(dev):
-        check(lib.evrep_gwd_padded_l1(_ptr(a), n, int(a.shape[1]), _ptr(b), m, int(b.shape[1]), float(h),
-                                      _ptr(scratch), _ptr(cost), _stream_ptr()), "evrep_gwd_padded_l1")
+        api.evrep_gwd_padded_l1(_ptr(a), n, int(a.shape[1]), _ptr(b), m, int(b.shape[1]), float(h), _ptr(scratch), _ptr(cost),
+                                _stream_ptr())
     return cost
 
 
@@ -775,31 +686,24 @@ def gwd_padded_l1_batch(Xs, n, Xt, m, n_cap, m_cap, xs_row=None, xt_row=None, h=
     may come straight from the device harness).  n_cap, m_cap: host upper bounds of the sizes.  Returns (P,) float64
     costs on the device (NaN for an empty or oversized cloud)."""
     _require_gpu()
-    lib = _lib.load()
+    api = _lib.api()
+    want(Xs, "Xs", torch.float64, (None, None), device="cuda")
     dev = Xs.device
+    want(Xt, "Xt", torch.float64, (None, None), device=dev)
     P = int(n.numel())
-    for t, nm in ((Xs, "Xs"), (Xt, "Xt")):
-        if t.dtype != torch.float64 or t.dim() != 2 or not t.is_cuda or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous 2-D float64 CUDA tensor" % nm)
     for t, nm in ((n, "n"), (m, "m"), (xs_row, "xs_row"), (xt_row, "xt_row")):
-        if t is not None and (t.dtype != torch.int64 or t.numel() != P or not t.is_cuda or not t.is_contiguous()):
-            raise ValueError("%s must be a contiguous int64 CUDA tensor of length %d" % (nm, P))
+        if t is not None:
+            want(t, nm, torch.int64, numel=P, device=dev)
     ds, dt = int(Xs.shape[1]), int(Xt.shape[1])
     ws = workspace or _default_workspace(dev)
-    nbytes = int(lib.evrep_gwd_batch_scratch_bytes(P, ds, dt, int(n_cap), int(m_cap)))
+    nbytes = api.evrep_gwd_batch_scratch_bytes(P, ds, dt, int(n_cap), int(m_cap))
     if nbytes == 0:
         raise ValueError("bad batch geometry (P=%d, ds=%d, dt=%d, n_cap=%d, m_cap=%d)" % (P, ds, dt, n_cap, m_cap))
     scratch = ws.get("gwd_scratch", nbytes)
-    if out is None:
-        out = torch.empty(P, dtype=torch.float64, device=dev)
-    elif out.dtype != torch.float64 or out.numel() != P or not out.is_cuda or not out.is_contiguous():
-        raise ValueError("out must be a contiguous float64 CUDA tensor of length %d" % P)
-    null = ctypes.c_void_p(None)
+    out = torch.empty(P, dtype=torch.float64, device=dev) if out is None else want(out, "out", torch.float64, numel=P, device=dev)
     with torch.cuda.device(dev):
-        check(lib.evrep_gwd_padded_l1_batch(P, _ptr(Xs), _ptr(xs_row) if xs_row is not None else null, _ptr(n), ds,
-                                            _ptr(Xt), _ptr(xt_row) if xt_row is not None else null, _ptr(m), dt,
-                                            int(n_cap), int(m_cap), float(h), _ptr(scratch), _ptr(out), _stream_ptr()),
-              "evrep_gwd_padded_l1_batch")
+        api.evrep_gwd_padded_l1_batch(P, _ptr(Xs), _ptr(xs_row), _ptr(n), ds, _ptr(Xt), _ptr(xt_row), _ptr(m), dt, int(n_cap),
+                                      int(m_cap), float(h), _ptr(scratch), _ptr(out), _stream_ptr())
     return out
 
 
@@ -809,8 +713,8 @@ def otmi_event_clouds(events, offsets, height, width, cap=None, workspace=None):
     The returned tensors are VIEWS of `workspace` (default: the device's shared GwdWorkspace): the next call with the same
     workspace overwrites them -- clone what must outlive it, or pass a GwdWorkspace of your own (one per host thread / stream)."""
     _require_gpu()
-    lib = _lib.load()
-    dev = events.device
+    api = _lib.api()
+    dev = want(events, "events", torch.int32, (None, 4), device="cuda").device
     off_host = offsets.detach().cpu() if isinstance(offsets, torch.Tensor) else torch.as_tensor(np.asarray(offsets, dtype=np.int64))
     B = int(off_host.numel() - 1)
     if cap is None:
@@ -820,10 +724,10 @@ def otmi_event_clouds(events, offsets, height, width, cap=None, workspace=None):
     Xs = ws.typed("otmi_xs", (B, 3, int(cap), 4), torch.float64)
     n = ws.typed("otmi_n", (B, 3), torch.int64)
     quad = ws.typed("otmi_quad", (B, 3), torch.int32)
-    scratch = ws.typed("otmi_ev_scratch", (int(lib.evrep_otmi_scratch_bytes(B)),), torch.uint8)
+    scratch = ws.typed("otmi_ev_scratch", (api.evrep_otmi_scratch_bytes(B),), torch.uint8)
     with torch.cuda.device(dev):
-        check(lib.evrep_otmi_event_clouds(_ptr(events), _ptr(off_dev), B, int(height), int(width), int(cap), _ptr(Xs),
-                                          _ptr(n), _ptr(quad), _ptr(scratch), _stream_ptr()), "evrep_otmi_event_clouds")
+        api.evrep_otmi_event_clouds(_ptr(events), _ptr(off_dev), B, int(height), int(width), int(cap), _ptr(Xs), _ptr(n), _ptr(quad),
+                                    _ptr(scratch), _stream_ptr())
     return Xs, n, quad
 
 
@@ -832,7 +736,7 @@ def otmi_rep_clouds(reps, quad, B, workspace=None, slot="otmi_xt"):
     belongs to window i % B), quad (B, 3) int32 from otmi_event_clouds -> (Xt (items, 3, m_cap, C + 2) float64,
     m (items, 3) int64).  Views of `workspace`, like otmi_event_clouds' results."""
     _require_gpu()
-    lib = _lib.load()
+    api = _lib.api()
     dev = reps.device
     reps = reps.contiguous()
     items, S, S2, C = (int(v) for v in reps.shape)
@@ -843,10 +747,10 @@ def otmi_rep_clouds(reps, quad, B, workspace=None, slot="otmi_xt"):
     Xt = ws.typed(slot, (items, 3, m_cap, C + 2), torch.float64)
     m = ws.typed(slot + "_m", (items, 3), torch.int64)
     dt = {torch.float64: _lib.F64, torch.float32: _lib.F32}[reps.dtype]
-    scratch = ws.typed("otmi_rep_scratch", (int(lib.evrep_otmi_scratch_bytes(items)),), torch.uint8)
+    scratch = ws.typed("otmi_rep_scratch", (api.evrep_otmi_scratch_bytes(items),), torch.uint8)
     with torch.cuda.device(dev):
-        check(lib.evrep_otmi_rep_clouds(_ptr(reps), dt, items, int(B), S, C, _ptr(quad), int(m_cap), _ptr(Xt), _ptr(m),
-                                        _ptr(scratch), _stream_ptr()), "evrep_otmi_rep_clouds")
+        api.evrep_otmi_rep_clouds(_ptr(reps), dt, items, int(B), S, C, _ptr(quad), int(m_cap), _ptr(Xt), _ptr(m), _ptr(scratch),
+                                  _stream_ptr())
     return Xt, m, m_cap
 
 

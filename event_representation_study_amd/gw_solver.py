@@ -8,13 +8,11 @@ MFMA GEMMs -- restated from POT's published ``entropic_gromov_wasserstein`` with
 UNPINNED against POT (absent); checked against ``oracle/gw_oracle.py``.  Its scores are NOT comparable with the
 C_p values the reference publishes (those come from A9).
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check
+from ._lib import ptr, stream_ptr
 
 LOSSES = {"square_loss": 0, "kl_loss": 1}
 
@@ -26,7 +24,7 @@ def entropic_gromov_wasserstein(C1, C2, p=None, q=None, loss_fun="square_loss", 
     float64 loss, both left on the device (no host synchronisation)."""
     if not torch.cuda.is_available():
         raise _lib.EvrepError("no HIP device visible: the solver runs on an MI355X only (no CPU fallback)")
-    lib = _lib.load()
+    api = _lib.api()
     dev = torch.device(device) if device is not None else (
         C1.device if isinstance(C1, torch.Tensor) and C1.is_cuda else torch.device("cuda", torch.cuda.current_device()))
     as_dev = lambda x: (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))).to(dev, torch.float64).contiguous()  # noqa: E731
@@ -41,14 +39,12 @@ def entropic_gromov_wasserstein(C1, C2, p=None, q=None, loss_fun="square_loss", 
     if loss_fun not in LOSSES:
         raise ValueError("loss_fun must be 'square_loss' or 'kl_loss'")
     prec = {"f64": _lib.F64, "f32": _lib.F32}[precision]
-    scratch = torch.empty(int(lib.evrep_gw_scratch_bytes(n, m, prec)), dtype=torch.uint8, device=dev)
+    scratch = _lib.scratch(api.evrep_gw_scratch_bytes(n, m, prec), dev)
     T = torch.empty((n, m), dtype=torch.float64, device=dev) if return_plan else None
     gw = torch.empty((), dtype=torch.float64, device=dev)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
     with torch.cuda.device(dev):
-        check(lib.evrep_entropic_gw(ptr(A), n, ptr(Bm), m, ptr(pv), ptr(qv), LOSSES[loss_fun], float(epsilon),
-                                    int(outer_iters), int(sinkhorn_iters), prec, ptr(scratch), ptr(T), ptr(gw),
-                                    ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "evrep_entropic_gw")
+        api.evrep_entropic_gw(ptr(A), n, ptr(Bm), m, ptr(pv), ptr(qv), LOSSES[loss_fun], float(epsilon), int(outer_iters),
+                              int(sinkhorn_iters), prec, ptr(scratch), ptr(T), ptr(gw), stream_ptr())
     return T, gw
 
 

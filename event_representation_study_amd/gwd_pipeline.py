@@ -81,9 +81,9 @@ def resize_taps(src, dst, interpolation, device):
 def resize_batch(rep, new_h, new_w, interpolation="area", scale=1.0, out_dtype=torch.float64, out=None):
     """rep: (B, H, W, C) float64/float32 CUDA tensor -> (B, new_h, new_w, C) of out_dtype; every channel on its
     own, like the reference's per-channel cv2.resize.  One launch of k_resize_taps (evrep_resize_taps)."""
-    import ctypes
     from . import _lib
-    lib = _lib.load()
+    from ._lib import ptr
+    api = _lib.api()
     rep = rep.contiguous()
     B, H, W, C = (int(v) for v in rep.shape)
     ys, yc, yw, Ty = resize_taps(H, new_h, interpolation, rep.device)
@@ -96,11 +96,9 @@ def resize_batch(rep, new_h, new_w, interpolation="area", scale=1.0, out_dtype=t
     if out is None:
         out = torch.empty((B, int(new_h), int(new_w), C), dtype=out_dtype, device=rep.device)
     dt = {torch.float64: _lib.F64, torch.float32: _lib.F32}
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
     with torch.cuda.device(rep.device):
-        _lib.check(lib.evrep_resize_taps(ptr(rep), dt[rep.dtype], B, H, W, C, int(new_h), int(new_w), T, ptr(ys), ptr(yc),
-                                         ptr(yw), ptr(xs), ptr(xc), ptr(xw), float(scale), dt[out.dtype], ptr(out),
-                                         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "evrep_resize_taps")
+        api.evrep_resize_taps(ptr(rep), dt[rep.dtype], B, H, W, C, int(new_h), int(new_w), T, ptr(ys), ptr(yc), ptr(yw), ptr(xs), ptr(xc),
+                              ptr(xw), float(scale), dt[out.dtype], ptr(out), _lib.stream_ptr())
     return out
 
 

@@ -55,6 +55,8 @@ The product path needs the HIP library and an MI355X; there is no CPU fallback.
 import numpy as np
 import torch
 
+from . import _lib
+from ._lib import ptr, stream_ptr
 from .engine import EventBatch
 
 IMAGE_H = 224    # imagenet.py:17-18
@@ -242,22 +244,18 @@ DIST_POL, DIST_STAT = [POS, POS, POS, NEG, NEG, NEG], [COUNT, TMAX, TMIN, COUNT,
 def _dist(batch, tnorm, clip_rate=CLIP_COUNT_RATE, alpha=DISC_ALPHA):
     """The part of dist_batch behind the upload (n_imagenet_front.dist_device enters here with device-made rows): the polstats
     builder, then evrep_dist (csrc/evrep_dist.hip: clip, 5x5 discount, dense rank) on its output.  Nothing waits for the device."""
-    import ctypes
-    from ._lib import check
     prim = batch.polstats(tnorm, DIST_POL, DIST_STAT)                                   # (B, H, W, 6) float32
     B, H, W = batch.B, batch.H, batch.W
     out = torch.empty((B, 2, H, W), dtype=torch.float32, device=batch.device)
     if B == 0:
         return out
-    lib = batch.lib
-    nbytes = int(lib.evrep_dist_scratch_bytes(B, H, W))
+    api = batch.api
+    nbytes = api.evrep_dist_scratch_bytes(B, H, W)
     if nbytes == 0:
         raise ValueError("evrep_dist does not take %d windows of %dx%d" % (B, H, W))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=batch.device)
+    scratch = _lib.scratch(nbytes, batch.device)
     with torch.cuda.device(batch.device):
-        check(lib.evrep_dist(ctypes.c_void_p(prim.data_ptr()), B, H, W, float(clip_rate), float(alpha), ctypes.c_void_p(out.data_ptr()),
-                             ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-              "evrep_dist")
+        api.evrep_dist(ptr(prim), B, H, W, float(clip_rate), float(alpha), ptr(out), ptr(scratch), stream_ptr())
     return out
 
 
@@ -403,10 +401,6 @@ def _sort(batch, t, global_time, strict, classes, qs, use_image):
 
     strict=True feeds polstats the consecutive rank whatever global_time is: the dense rank of the per-pixel maxima does not change
     under a strictly increasing map of the indices, and the rank, unlike a raw microsecond index beyond 2^24, is exact in float32."""
-    import ctypes
-    from . import _lib
-    from ._lib import check
-    from .engine import _ptr, _stream_ptr
     B, H, W, K = batch.B, batch.H, batch.W, len(classes)
     if B == 0:
         raise ValueError("no window")
@@ -414,27 +408,26 @@ def _sort(batch, t, global_time, strict, classes, qs, use_image):
     if strict and int(lengths.max()) >= SORT_MAX_WINDOW:
         raise ValueError("strict=True takes windows below %d events (sample %d holds %d)"
                          % (SORT_MAX_WINDOW, int(lengths.argmax()), int(lengths.max())))
-    if t.dtype != torch.float64 or t.device != batch.device or t.numel() != batch.total or not t.is_contiguous():
-        raise ValueError("one contiguous float64 time per event on %s" % batch.device)
-    lib, dev = batch.lib, batch.device
+    batch._per_event(t, "t")
+    api, dev = batch.api, batch.device
     rows = max(batch.total, 1)
     tval = torch.empty(rows, dtype=torch.float64, device=dev)
     status = torch.empty(B, dtype=torch.uint32, device=dev)
     nsort = max(len(qs), 1)
     out = torch.empty((B, K * (int(bool(use_image)) + nsort), H, W), dtype=torch.float32, device=dev)
-    n_ti, n_img = int(lib.evrep_time_index_scratch_bytes(B, batch.total)), int(lib.evrep_sort_image_scratch_bytes(B, H, W, K))
+    n_ti, n_img = api.evrep_time_index_scratch_bytes(B, batch.total), api.evrep_sort_image_scratch_bytes(B, H, W, K)
     if n_ti == 0 or n_img == 0:
         raise ValueError("the sorted timestamp image does not take %d windows of %dx%d with %d events" % (B, H, W, batch.total))
-    scratch = torch.empty(max(n_ti, n_img), dtype=torch.uint8, device=dev)
+    scratch = _lib.scratch(max(n_ti, n_img), dev)
     mode = _lib.TIME_INDEX_RANK if (global_time or strict) else _lib.TIME_INDEX_RAW
     with torch.cuda.device(dev):
-        check(lib.evrep_time_index(_ptr(t) if batch.total else _ptr(tval), _ptr(batch.offsets), B, mode, _ptr(tval), _ptr(status),
-                                   _ptr(scratch), _stream_ptr()), "evrep_time_index")
+        api.evrep_time_index(ptr(t) if batch.total else ptr(tval), ptr(batch.offsets), B, mode, ptr(tval), ptr(status), ptr(scratch),
+                             stream_ptr())
     prim = batch.polstats(tval[:batch.total], [c for c in classes for _ in (0, 1)], [FLAG, TMAX] * K)      # (B, H, W, 2K) float32
     flags = (_lib.SORT_STRICT if strict else 0) | (_lib.SORT_USE_IMAGE if use_image else 0)
     with torch.cuda.device(dev):
-        check(lib.evrep_sort_image(_ptr(prim), B, H, W, K, flags, _lib.int32_array(qs) if qs else None, len(qs), _ptr(out), _ptr(status),
-                                   _ptr(scratch), _stream_ptr()), "evrep_sort_image")
+        api.evrep_sort_image(ptr(prim), B, H, W, K, flags, _lib.int32_array(qs) if qs else None, len(qs), ptr(out), ptr(status),
+                             ptr(scratch), stream_ptr())
     return out, status
 
 
@@ -454,7 +447,6 @@ def sort_batch(event_tensors, global_time, neglect_polarity, use_image, strict, 
     2^24 events and more."""
     classes, qs = _sort_options(neglect_polarity, use_image, quantize_sort, denoise_image, denoise_sort)
     wins = [_as_f64(e) for e in event_tensors]
-    from . import _lib
     status = np.zeros(len(wins), np.uint32)
     for b, w in enumerate(wins):
         if len(w) == 0:
@@ -540,7 +532,6 @@ def _study_name(name):
         reshape_then_time_surface(None)           # the reference cannot run it: its IndexError
     if name not in STUDY_NAMES:
         raise KeyError(name)
-    from . import _lib
     return {"optimized": _lib.STUDY_MDES, "event_stack": _lib.STUDY_STACK, "tore": _lib.STUDY_TORE}[name]
 
 
@@ -569,21 +560,16 @@ def _study_rows(batch, t, xy, want):
     """evrep_nimg_study_rows on the rows of `batch` ([x.long(), y.long(), 0, sign p]), their float64 times and untruncated
     coordinates -> dict of device tensors: "mdes" / "stack" / "tore" ((total, 4) int32, the wanted sets only), "sample_times"
     ((B,) float64, with "tore"), "status" ((B,) uint32).  Nothing waits for the device."""
-    import ctypes
-    from . import _lib
-    from ._lib import check
-    from .engine import _ptr, _stream_ptr
-    B, total, dev, lib = batch.B, batch.total, batch.device, batch.lib
+    B, total, dev, api = batch.B, batch.total, batch.device, batch.api
     if B == 0:
         raise ValueError("no window")
-    if t.dtype != torch.float64 or t.device != dev or t.numel() != total or not t.is_contiguous():
-        raise ValueError("one contiguous float64 time per event on %s" % dev)
+    batch._per_event(t, "t")
     if int(batch.offsets_host[0]) != 0 or int(batch.offsets_host[-1]) != total:
         raise ValueError("the batch's offsets must run from 0 to its %d rows: the row sets are written at the offsets" % total)
     tore = bool(want & _lib.STUDY_TORE)
-    if tore and (xy is None or xy.dtype != torch.float64 or xy.device != dev or tuple(xy.shape) != (total, 2) or not xy.is_contiguous()):
-        raise ValueError("TORE needs the untruncated coordinates: a contiguous (total, 2) float64 tensor on %s" % dev)
-    nbytes = int(lib.evrep_nimg_study_rows_scratch_bytes(B, total))
+    if tore:
+        _lib.want(xy, "xy (TORE needs the untruncated coordinates)", torch.float64, (total, 2), device=dev)
+    nbytes = api.evrep_nimg_study_rows_scratch_bytes(B, total)
     if nbytes == 0:
         raise ValueError("evrep_nimg_study_rows does not take %d windows" % B)
     n = max(total, 1)
@@ -597,12 +583,10 @@ def _study_rows(batch, t, xy, want):
         rows_in, t_in, xy_in = out.new_zeros((1, 4)), meta.new_zeros(8).view(torch.float64), meta.new_zeros(16).view(torch.float64)
     else:
         rows_in, t_in, xy_in = batch.events, t, xy
-    null = ctypes.c_void_p(None)
     with torch.cuda.device(dev):
-        check(lib.evrep_nimg_study_rows(_ptr(rows_in), _ptr(t_in), _ptr(xy_in) if tore else null, _ptr(batch.offsets), B, batch.H, batch.W,
-                                        int(want), *[_ptr(res[k]) if k in res else null for k in ("mdes", "stack", "tore")],
-                                        _ptr(res["sample_times"]) if tore else null, _ptr(res["status"]), _ptr(meta), _stream_ptr()),
-              "evrep_nimg_study_rows")
+        api.evrep_nimg_study_rows(ptr(rows_in), ptr(t_in), ptr(xy_in) if tore else None, ptr(batch.offsets), B, batch.H, batch.W,
+                                  int(want), *[ptr(res.get(k)) for k in ("mdes", "stack", "tore")],
+                                  ptr(res["sample_times"]) if tore else None, ptr(res["status"]), ptr(meta), stream_ptr())
     for k in sets:
         res[k] = res[k][:total]
     return res

@@ -39,15 +39,14 @@ in the reference); ``accumulate_device("acc_sort", aug)`` (acc_sort is no
 ``SPECS`` accumulator: ``sort_device`` is its device-input form); the ``denoise_*`` options, which the reference reads and never
 defines.  There is no CPU fallback for the device path: without a HIP device it raises ``EvrepError``.
 """
-import ctypes
 import random
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check
-from .engine import EventBatch, _ptr, _require_gpu, _stream_ptr
+from ._lib import ptr, require_gpu, stream_ptr
+from .engine import EventBatch
 
 SENSOR_H = 480     # imagenet.py:16-21
 SENSOR_W = 640
@@ -295,8 +294,8 @@ class NImageNetFrontEnd:
                 _RESHAPE[method](None, *self.sensor, *self.image)
             if method == "no_sample":
                 self.sx, self.sy = self.image[1] / self.sensor[1], self.image[0] / self.sensor[0]   # new_w / orig_w, new_h / orig_h
-        _require_gpu()
-        self.lib = _lib.load()
+        require_gpu()
+        self.api = _lib.api()
 
     def draw(self, lengths):
         """The (B,) PARAMS_DTYPE table of one batch, consuming `random` and `np.random` as B reference calls do."""
@@ -323,14 +322,12 @@ class NImageNetFrontEnd:
         t_out, tn_out = f64[:rows], f64[rows:2 * rows]
         xy_out = f64[2 * rows:].view(rows, 2) if want_xy else None
         meta = torch.empty((B + 1) * 8 + B * 4, dtype=torch.uint8, device=dev)      # offsets_out then status_out
-        scratch = torch.empty(int(self.lib.evrep_nimg_prepare_scratch_bytes(B, total)), dtype=torch.uint8, device=dev)
+        scratch = _lib.scratch(self.api.evrep_nimg_prepare_scratch_bytes(B, total), dev)
         flags = (_lib.NIMG_P_UINT8 if p_as_uint8 else 0) | (_lib.NIMG_TRAIN if self.mode == "train" else 0)
         with torch.cuda.device(dev):
-            check(self.lib.evrep_nimg_prepare(_ptr(batch.events), _ptr(batch.offsets), B, _ptr(table[B * 48:]), _ptr(table),
-                                              float(self.sx), float(self.sy), self.image[0], self.image[1], flags, _ptr(ev_out),
-                                              _ptr(t_out), _ptr(tn_out), _ptr(xy_out) if want_xy else ctypes.c_void_p(None),
-                                              _ptr(meta), _ptr(meta[(B + 1) * 8:]), _ptr(scratch), _stream_ptr()),
-                  "evrep_nimg_prepare")
+            self.api.evrep_nimg_prepare(ptr(batch.events), ptr(batch.offsets), B, ptr(table[B * 48:]), ptr(table), float(self.sx),
+                                        float(self.sy), self.image[0], self.image[1], flags, ptr(ev_out), ptr(t_out), ptr(tn_out),
+                                        ptr(xy_out), ptr(meta), ptr(meta[(B + 1) * 8:]), ptr(scratch), stream_ptr())
         host = meta.cpu().numpy()                                                    # the one synchronisation
         off = host[:(B + 1) * 8].view(np.int64).copy()
         status = host[(B + 1) * 8:].view(np.uint32).copy()

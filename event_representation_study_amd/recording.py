@@ -24,7 +24,6 @@ record) or of an N-Caltech / N-MNIST ``.bin`` file (5 bytes per record) as it li
 ``evlicious.io.load_events_from_path`` does.  ``DatDeviceRecording`` answers ``get_between_idx``, ``get_between_time`` and
 ``seek_time`` as the reference's ``DatEventHandle`` does (``dat_seek_index`` states the seek in numpy).
 """
-import ctypes
 import os
 import pathlib
 
@@ -32,8 +31,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check
-from .engine import EventBatch, _ptr, _require_gpu, _stream_ptr
+from ._lib import ptr, require_gpu, stream_ptr
+from .engine import EventBatch
 
 QUERY_LIMIT_US = 1 << 43
 _UNITS = ("nr", "us")
@@ -242,8 +241,8 @@ class DeviceRecording:
         cols = [_column(x, np.uint16, "x"), _column(y, np.uint16, "y"), _column(t, np.int64, "t"), _column(p, np.int8, "p")]
         if len({len(c) for c in cols}) != 1:
             raise ValueError("x, y, t, p must have the same length")
-        _require_gpu()
-        self.lib = _lib.load()
+        require_gpu()
+        self.lib, self.api = _lib.load(), _lib.api()
         self.device = torch.device(device)
         self.height, self.width, self.divider = int(height), int(width), 1
         self.n = len(cols[2])
@@ -272,7 +271,7 @@ class DeviceRecording:
         over windows of several of them.  t is not ascending across the joints: only ``windows`` may be asked of the result."""
         first = recordings[0]
         rec = cls.__new__(cls)
-        rec.lib, rec.device, rec.height, rec.width, rec.divider = first.lib, first.device, first.height, first.width, 1
+        rec.lib, rec.api, rec.device, rec.height, rec.width, rec.divider = first.lib, first.api, first.device, first.height, first.width, 1
         rec.x, rec.y, rec.t, rec.p = (torch.cat([getattr(r, c) for r in recordings]) for c in "xytp")
         rec.n, rec._limits = int(rec.t.numel()), None
         return rec
@@ -325,18 +324,18 @@ class DeviceRecording:
         height, width = int(height), int(width)
         if height < 1 or width < 1:
             raise ValueError("the sensor size must be positive")
-        _require_gpu()
+        require_gpu()
         rec = cls.__new__(cls)
-        rec.lib, rec.device = _lib.load(), torch.device(device)
+        rec.lib, rec.api, rec.device = _lib.load(), _lib.api(), torch.device(device)
         rec.height, rec.width, rec.divider = height, width, 1
-        lib, dev = rec.lib, rec.device
+        api, dev = rec.api, rec.device
         flags = _lib.DECODE_DROP_OOB if out_of_bounds == "drop" else _lib.DECODE_STRICT
         cols = [torch.empty(n, dtype=d, device=dev) for d in (torch.uint16, torch.uint16, torch.int64, torch.int8)]
         state = torch.empty(len(_lib.DECODE_STATE_FIELDS), dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
-            check(lib.evrep_decode_state_init(_ptr(state), _stream_ptr()), "evrep_decode_state_init")
+            api.evrep_decode_state_init(ptr(state), stream_ptr())
             if n:
-                scratch = torch.empty(lib.evrep_decode_scratch_bytes(min(n, chunk_events)), dtype=torch.uint8, device=dev)
+                scratch = _lib.scratch(api.evrep_decode_scratch_bytes(min(n, chunk_events)), dev)
                 room = (min(n, chunk_events) * rec_bytes + 15) // 16 * 16        # whole 16-byte pieces: the kernels read those
                 pinned = [torch.empty(room, dtype=torch.uint8).pin_memory() for _ in range(2)]
                 staged = [torch.empty(room, dtype=torch.uint8, device=dev) for _ in range(2)]
@@ -353,12 +352,12 @@ class DeviceRecording:
                         padded = (nbytes + 15) // 16 * 16
                         staged[b][:padded].copy_(pinned[b][:padded], non_blocking=True)
                         copied[b].record()
-                        args = (first, height, width, flags, _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(cols[3]), n,
-                                _ptr(state), _ptr(scratch), _stream_ptr())
+                        args = (first, height, width, flags, ptr(cols[0]), ptr(cols[1]), ptr(cols[2]), ptr(cols[3]), n,
+                                ptr(state), ptr(scratch), stream_ptr())
                         if fmt == "dat":
-                            check(lib.evrep_decode_dat(_ptr(staged[b]), m, rec_bytes, *args), "evrep_decode_dat")
+                            api.evrep_decode_dat(ptr(staged[b]), m, rec_bytes, *args)
                         else:
-                            check(lib.evrep_decode_bin5(_ptr(staged[b]), m, *args), "evrep_decode_bin5")
+                            api.evrep_decode_bin5(ptr(staged[b]), m, *args)
             st = dict(zip(_lib.DECODE_STATE_FIELDS, (int(v) for v in state.cpu().numpy())))      # the one read-back
         if st["n_in"] != n:
             raise _lib.EvrepError("decode of %s: state %r after %d records" % (path, st, n))
@@ -407,8 +406,7 @@ class DeviceRecording:
         if k.size:
             q = torch.from_numpy(k).to(self.device)
             with torch.cuda.device(self.device):
-                check(self.lib.evrep_time_to_index(_ptr(self.t), self.n, _ptr(q), k.size, _ptr(out), _stream_ptr()),
-                      "evrep_time_to_index")
+                self.api.evrep_time_to_index(ptr(self.t), self.n, ptr(q), k.size, ptr(out), stream_ptr())
         return out
 
     def find_index_from_timestamp(self, t_us):
@@ -481,13 +479,12 @@ class DeviceRecording:
         parts = [a, e, offs] + ([given] if given is not None else [])
         table = torch.from_numpy(np.concatenate(parts)).to(self.device)            # one small upload
         d_i0, d_i1, d_off = table[:B], table[B:2 * B], table[2 * B:3 * B + 1]
-        d_given = _ptr(table[3 * B + 1:]) if given is not None else ctypes.c_void_p(None)
+        d_given = ptr(table[3 * B + 1:]) if given is not None else None
         events = torch.empty((max(total, 1), 4), dtype=torch.int32, device=self.device)
         meta = torch.empty(B * 12, dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
-            check(self.lib.evrep_windows_gather(_ptr(self.x), _ptr(self.y), _ptr(self.t), _ptr(self.p), self.n, _ptr(d_i0),
-                                                _ptr(d_i1), _ptr(d_off), B, mode, d_given, _ptr(events), _ptr(meta),
-                                                _ptr(meta[B * 8:]), _stream_ptr()), "evrep_windows_gather")
+            self.api.evrep_windows_gather(ptr(self.x), ptr(self.y), ptr(self.t), ptr(self.p), self.n, ptr(d_i0), ptr(d_i1), ptr(d_off),
+                                          B, mode, d_given, ptr(events), ptr(meta), ptr(meta[B * 8:]), stream_ptr())
         batch = EventBatch(events[:total], torch.from_numpy(offs), self.height, self.width,
                            max_events_per_window=int((e - a).max()))
         return batch, meta
@@ -537,8 +534,7 @@ class DatDeviceRecording(DeviceRecording):
         if flat.size:
             d_q = torch.from_numpy(flat).to(self.device)
             with torch.cuda.device(self.device):
-                check(self.lib.evrep_dat_seek_time(_ptr(self.t), self.n, _ptr(d_q), flat.size, int(term), _ptr(out), _stream_ptr()),
-                      "evrep_dat_seek_time")
+                self.api.evrep_dat_seek_time(ptr(self.t), self.n, ptr(d_q), flat.size, int(term), ptr(out), stream_ptr())
         idx = out.cpu().numpy().reshape(q.shape)
         return idx if q.ndim else idx[()]
 

@@ -24,7 +24,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..engine import EventBatch, _ptr, _require_gpu
+from .._lib import ptr, require_gpu
+from ..engine import EventBatch
 from ..synthetic import from_structured, narrow_to_int32
 
 RESULT_POOL_DEPTH = int(os.environ.get("EVREP_RESULT_POOL", os.environ.get("EVREP_RESULT_RING", "8")))
@@ -185,17 +186,14 @@ class SampleBatch:
         out = self.out(2 * k, torch.float32)
         b = self.batch
         b.bin()
-        null = ctypes.c_void_p(None)
-        with b._dev():
-            _lib.check(b.lib.evrep_tore_ftime(*b._args(), int(k), int(frame_mode), null, null, null, float(scale), _ptr(out),
-                                              b._sp()), "evrep_tore_ftime")
+        b._launch(b.api.evrep_tore_ftime, int(k), int(frame_mode), None, None, None, float(scale), ptr(out))
         return out
 
 
 def sample_batch(event_sequence, height, width, truncate=False, rebase_t=False, device_out=False):
     """Structured x,y,t,p record array (or (n,4) array) -> the pooled one-window batch, events on their way to the GPU.
     device_out: the builders write into a FRESH device tensor and finish() returns it (no D2H)."""
-    _require_gpu()                 # no CPU fallback: without the HIP library or a GPU the wrappers raise
+    require_gpu()                  # no CPU fallback: without the HIP library or a GPU the wrappers raise
     _lib.load()
     if isinstance(event_sequence, np.ndarray) and event_sequence.dtype.names:
         ev = from_structured(event_sequence, truncate=truncate, rebase_t=rebase_t)
@@ -220,8 +218,7 @@ def finish(sb, dev_out, allow_oob=False, what="builder", out=None, tore_k=None, 
     ctx, b = sb.ctx, sb.batch
     b.bin()
     with b._dev():
-        _lib.check(b.lib.evrep_copy_window_meta_async(ctypes.byref(b.plan), _ptr(b.workspace), _ptr(ctx.meta_pinned),
-                                                      b._sp()), "evrep_copy_window_meta_async")
+        b.api.evrep_copy_window_meta_async(ctypes.byref(b.plan), ptr(b.workspace), ptr(ctx.meta_pinned), b._sp())
     shape = tuple(dev_out.shape[1:])
     slot = host = None
     if not sb.device_out:

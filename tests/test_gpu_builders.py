@@ -298,3 +298,22 @@ def test_to_timesurface_with_float_timestamps():
         assert got.shape == want.shape
         np.testing.assert_allclose(got, want, rtol=1e-10, atol=0)      # budget 1e-5 (x * (1/tau) instead of x / tau: ~1e-14 here)
         assert np.array_equal(got == 0, want == 0)
+
+
+def test_refusals_surface_through_the_checked_handle(eng, oracle):
+    """A status the C entry returns reaches the caller as EvrepError naming the entry point, a tensor that is not what the
+    kernel would read as ValueError, and neither leaves the batch unusable.  Two windows on 8 x 8: three events and none."""
+    from event_representation_study_amd import _lib
+    ev = np.array([[1, 2, 10, 1], [3, 3, 20, -1], [1, 2, 30, 1]], dtype=np.int32)
+    eb = eng.EventBatch.from_numpy([ev, np.zeros((0, 4), np.int32)], 8, 8)
+    before = eb.optimized()[0].cpu().numpy()
+    with pytest.raises(_lib.EvrepError, match=r"^evrep_voxel_range failed: EVREP_EINVAL"):
+        eb.voxel(bins=17)
+    with pytest.raises(_lib.EvrepError, match=r"^evrep_event_stack failed: EVREP_EINVAL"):
+        eb.event_stack(stack_size=17)
+    with pytest.raises(ValueError, match="^out must be"):
+        eb.time_surface(slices=6, out=torch.empty((2, 8, 8, 6), dtype=torch.float64, device=eb.device))
+    got = eb.optimized()[0].cpu().numpy()
+    assert_bit_equal(got, oracle.ergo12(ev, 8, 8), "after the refusals")
+    assert_bit_equal(got, before, "as before the refusals")
+    assert [int(s) & _lib.ST_EMPTY for s in eb.status()] == [0, _lib.ST_EMPTY]

@@ -204,7 +204,7 @@ class _Spy:
 
     def __init__(self, monkeypatch):
         from event_representation_study_amd import _lib
-        self.lib, self.taps, self.frames, self.src = _lib.load(), 0, 0, []
+        self.lib, self.taps, self.frames, self.src = _lib.api(), 0, 0, []      # the handle the package calls through
         real_taps, real_frames = self.lib.evrep_resize_tap_tables, self.lib.evrep_detector_input_frames
 
         def taps(*a):

@@ -731,7 +731,8 @@ def test_detector_input_frames_table(B, monkeypatch):
     mats0, flips0 = F._train_mix()
     mats, flips = [mats0[b % 7] for b in range(B)], [flips0[b % 7] for b in range(B)]
     want = F._want(frames, True, mats, flips)
-    real = lib.evrep_detector_input_frames
+    api = _lib.api()                                  # the handle prepare_frames calls through
+    real = api.evrep_detector_input_frames
     state = {}
 
     def carved_call(table, B_, dt, C, S, start, count, wts, n_rows, n_wt, pad, warp, scale, frames_dev, out, stream):
@@ -740,7 +741,7 @@ def test_detector_input_frames_table(B, monkeypatch):
         state["dev"] = g.scratch(nbytes, "frames_dev")
         return real(table, B_, dt, C, S, start, count, wts, n_rows, n_wt, pad, warp, scale, g.p(state["dev"]), out, stream)
 
-    monkeypatch.setattr(lib, "evrep_detector_input_frames", carved_call)
+    monkeypatch.setattr(api, "evrep_detector_input_frames", carved_call)
 
     def call(g):
         state["g"] = g
