@@ -96,6 +96,7 @@ SYMBOLS = {
     "evrep_otmi_scratch_bytes": (ctypes.c_size_t, [_i32]),
     "evrep_otmi_event_clouds": _st([_vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
     "evrep_otmi_rep_clouds": _st([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "evrep_otmi_rep_clouds_bank": _st([_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _I32P, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
     "evrep_filter_pixel_fsm": _st([_PP, _vp, _vp, _vp, _i32, _f64, _vp, _vp, _vp, _vp]),
     "evrep_filter_background": _st([_PP, _vp, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _vp]),
     "evrep_filter_mask_gather": _st([_vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp]),

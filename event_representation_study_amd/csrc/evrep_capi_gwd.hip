@@ -302,6 +302,43 @@ int evrep_otmi_rep_clouds(const void *rep, int32_t rep_dtype, int32_t items, int
     return EVREP_OK;
 }
 
+int evrep_otmi_rep_clouds_bank(const void *base, const void *bank, int32_t dtype, int32_t B, int32_t S, int32_t C, int32_t R,
+                               int32_t slot, const int32_t *cand, int32_t n_cand, const int32_t *quad, int64_t m_cap,
+                               double *Xt, int64_t *m_out, void *scratch, void *stream_) {
+    if (!base || !bank || !cand || !quad || !Xt || !m_out || !scratch || B <= 0 || n_cand <= 0 || S < 4 || C <= 0 || C + 2 > kGwdMaxD ||
+        R <= 0 || m_cap <= 0 || slot < 0 || slot >= C)
+        return EVREP_EINVAL;
+    if (dtype != EVREP_F64 && dtype != EVREP_F32) return EVREP_EINVAL;
+    if ((int64_t)n_cand * B > 65535) return EVREP_EINVAL;
+    for (int32_t j = 0; j < n_cand; ++j)
+        if (cand[j] < 0 || cand[j] >= R) return EVREP_EINVAL;
+    if (reinterpret_cast<uintptr_t>(scratch) & 15u) return EVREP_EINVAL;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    uint32_t *cnt = static_cast<uint32_t *>(scratch);
+    const size_t lds = (size_t)kOtmiBankWaves * otmi_bank_lds_doubles(C + 2) * sizeof(double);
+    // the candidates' bank channels reach the device as kernel arguments (cand is HOST memory and is not read after the
+    // call returns), kOtmiBankMaxCand per pair of launches
+    OtmiBankCands cs;
+    for (int32_t first = 0; first < n_cand; first += kOtmiBankMaxCand) {
+        cs.first = first;
+        cs.n = n_cand - first < kOtmiBankMaxCand ? n_cand - first : kOtmiBankMaxCand;
+        for (int32_t j = 0; j < kOtmiBankMaxCand; ++j) cs.idx[j] = j < cs.n ? cand[first + j] : 0;
+        const int groups = (cs.n + kOtmiBankGroup - 1) / kOtmiBankGroup;
+        const dim3 grid(kOtmiRepSlices / kOtmiBankWaves, 3, (unsigned)(groups * B));
+#define OTMI_BANK(T)                                                                                                          \
+    do {                                                                                                                      \
+        k_otmi_rep_bank<T, false><<<grid, kOtmiBankWaves * 64, 0, stream>>>(static_cast<const T *>(base), static_cast<const T *>(bank), \
+                                                                            B, S, C, R, slot, cs, quad, m_cap, cnt, Xt, m_out);          \
+        k_otmi_rep_bank<T, true><<<grid, kOtmiBankWaves * 64, lds, stream>>>(static_cast<const T *>(base), static_cast<const T *>(bank), \
+                                                                             B, S, C, R, slot, cs, quad, m_cap, cnt, Xt, m_out);         \
+    } while (0)
+        if (dtype == EVREP_F64) OTMI_BANK(double); else OTMI_BANK(float);
+#undef OTMI_BANK
+        LAUNCH_CHECK("k_otmi_rep_bank");
+    }
+    return EVREP_OK;
+}
+
 size_t evrep_gw_scratch_bytes(int64_t n, int64_t m, int32_t precision) {
     if (n <= 0 || m <= 0) return 0;
     return precision == EVREP_F32 ? gw_carve<float>(nullptr, n, m).bytes : gw_carve<double>(nullptr, n, m).bytes;

@@ -253,4 +253,130 @@ __global__ __launch_bounds__(kOtmiThreads) void k_otmi_rep(const RepT *__restric
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the search step
+// Candidate clouds from a shared base and a bank (evrep_otmi_rep_clouds_bank): item (candidate j, window b) is the base
+// stack of window b with channel `slot` taken from bank channel cand[j].  What k_otmi_rep writes for the materialised
+// items, but a pixel's base values, its "a base channel is non-zero / NaN" bits and its two positional values are formed
+// ONCE per group of kOtmiBankGroup candidates, and the kept rows leave through LDS as whole 8-byte runs:
+//   * a wave is one of the kOtmiRepSlices slices of a quadrant (the count layout of k_otmi_rep), lane = pixel, 64 pixels
+//     per step; waves never meet, so there is no workgroup barrier;
+//   * the bank is channel-last: the group's candidates of a pixel are neighbours (16 consecutive float64 = one 128-byte line);
+//   * ballot + popcount rank the kept pixels of a step (STABLE: steps in order, lanes in order); the rows of a step are
+//     contiguous in Xt, so lane e stores double e of the run;
+//   * the running row position of candidate jj lives in lane jj.
+constexpr int kOtmiBankGroup = 16;
+constexpr int kOtmiBankWaves = 2;        // waves per workgroup: 34 KB of LDS at the widest row (32 doubles)
+constexpr int kOtmiBankMaxCand = 512;    // candidates per launch: their bank channels ride the kernel arguments
+static_assert(kOtmiRepSlices % kOtmiBankWaves == 0 && kOtmiRepSlices <= 64, "a wave per slice; the slice counts fit one wave");
+struct OtmiBankCands {
+    int32_t n, first;                    // candidates of this launch; position of the first in the caller's list
+    int32_t idx[kOtmiBankMaxCand];
+};
+__host__ __device__ inline size_t otmi_bank_lds_doubles(int D) { return (size_t)64 * D + 64 + 32; }   // rows | candidate values | kept lanes
+
+__device__ inline void otmi_wave_phase() {   // orders the LDS phases of ONE wave (its LDS operations execute in program order)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ inline uint32_t otmi_wave_sum(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+// grid (kOtmiRepSlices / kOtmiBankWaves, 3, groups * B), kOtmiBankWaves * 64 threads, blockIdx.z = group * B + window.
+// WRITE = false: kept pixels per (item, slot, slice) -> cnt, as k_otmi_rep; WRITE = true: the rows and m_out.
+template <typename RepT, bool WRITE>
+__global__ __launch_bounds__(kOtmiBankWaves * 64) void k_otmi_rep_bank(const RepT *__restrict__ base, const RepT *__restrict__ bank,
+                                                                      int B, int S, int C, int R, int slot, const OtmiBankCands cands,
+                                                                      const int32_t *__restrict__ quad, int64_t m_cap,
+                                                                      uint32_t *__restrict__ cnt, double *__restrict__ Xt,
+                                                                      int64_t *__restrict__ m_out) {
+    extern __shared__ double otmi_bank_lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sl = blockIdx.x * kOtmiBankWaves + wave, k = blockIdx.y;
+    const int g = blockIdx.z / B, b = blockIdx.z - g * B;
+    const int j0 = g * kOtmiBankGroup, ng = min(kOtmiBankGroup, cands.n - j0);
+    const int q = quad[b * 3 + k];
+    const int ih = S / 2 - 1;                                        // the cut of k_otmi_rep
+    const int x0 = (q & 1) ? ih : 0, x1 = (q & 1) ? S - 1 : ih;
+    const int y0 = (q & 2) ? ih : 0, y1 = (q & 2) ? S - 1 : ih;
+    const int nrows = y1 - y0 + 1, ncols = x1 - x0 + 1, npx = nrows * ncols;
+    const int per_slice = (npx + kOtmiRepSlices - 1) / kOtmiRepSlices;
+    const int s0 = min(sl * per_slice, npx), s1 = min(s0 + per_slice, npx);
+    const int D = C + 2;
+    const uint32_t magic = 0xffffffffu / (uint32_t)D + 1u;           // __umulhi(e, magic) == e / D for e < 64 * 32
+    double *rows = otmi_bank_lds + (size_t)wave * otmi_bank_lds_doubles(D);
+    double *candv = rows + 64 * D;
+    uint32_t *kept = reinterpret_cast<uint32_t *>(candv + 64);
+    // item of candidate jj of this group, slot k -> its slice counts
+    auto item_of = [&](int jj) -> size_t { return (size_t)(cands.first + j0 + jj) * B + b; };
+
+    uint32_t mine = 0;                                               // lane jj: candidate jj's kept count (count) / next row (write)
+    if (WRITE) {
+        for (int jj = 0; jj < ng; ++jj) {
+            const uint32_t *c = cnt + (item_of(jj) * 3 + k) * kOtmiRepSlices;
+            const uint32_t v = lane < kOtmiRepSlices ? c[lane] : 0u;
+            const uint32_t before = otmi_wave_sum(lane < sl ? v : 0u), all = otmi_wave_sum(v);
+            if (lane == jj) mine = before;
+            if (sl == 0 && lane == 0) m_out[item_of(jj) * 3 + k] = (int64_t)all;
+        }
+    }
+    for (int c0 = s0; c0 < s1; c0 += 64) {
+        const int px = c0 + lane;
+        const bool in = px < s1;
+        bool anyb = false, nanb = false;
+        double cv[kOtmiBankGroup];
+        if (WRITE) otmi_wave_phase();                                // the previous step's rows have been read
+        if (in) {
+            const int r = px / ncols, cc = px - r * ncols;
+            const size_t pix = ((size_t)b * S + (y0 + r)) * S + (x0 + cc);
+            const RepT *f = base + pix * C;
+            for (int ch = 0; ch < C; ++ch) {
+                const double v = (double)f[ch];
+                if (WRITE) rows[lane * D + ch] = v;
+                if (ch != slot) { anyb |= v != 0.0; nanb |= v != v; }
+            }
+            if (WRITE) {
+                rows[lane * D + C] = (double)r / (double)(nrows - 1);
+                rows[lane * D + C + 1] = (double)cc / (double)(ncols - 1);
+            }
+            const RepT *bk = bank + pix * R;
+#pragma unroll
+            for (int jj = 0; jj < kOtmiBankGroup; ++jj) cv[jj] = jj < ng ? (double)bk[cands.idx[j0 + jj]] : 0.0;
+        } else {
+#pragma unroll
+            for (int jj = 0; jj < kOtmiBankGroup; ++jj) cv[jj] = 0.0;
+        }
+#pragma unroll
+        for (int jj = 0; jj < kOtmiBankGroup; ++jj) {
+            if (jj < ng) {                                           // uniform
+                const double v = cv[jj];
+                // np.abs(feat).sum(-1) > 0 and not NaN, as in k_otmi_rep: one channel non-zero, none NaN
+                const bool keep = in && (anyb || v != 0.0) && !(nanb || v != v);
+                const uint64_t mask = __ballot(keep);
+                const uint32_t nk = (uint32_t)__popcll(mask);
+                if (WRITE && nk != 0) {                              // uniform
+                    otmi_wave_phase();                               // the previous candidate's run has been read
+                    candv[lane] = v;
+                    if (keep) kept[__popcll(mask & ((1ull << lane) - 1ull))] = (uint32_t)lane;
+                    otmi_wave_phase();
+                    const uint32_t pos = __shfl(mine, jj, 64);
+                    const int64_t room = m_cap - (int64_t)pos;
+                    const uint32_t nrow = room <= 0 ? 0u : (room < (int64_t)nk ? (uint32_t)room : nk);
+                    double *dst = Xt + ((item_of(jj) * 3 + k) * (size_t)m_cap + pos) * D;
+                    for (uint32_t e = lane; e < nrow * (uint32_t)D; e += 64) {
+                        const uint32_t ri = __umulhi(e, magic), ch = e - ri * (uint32_t)D;
+                        const uint32_t src = kept[ri];
+                        dst[e] = (int)ch == slot ? candv[src] : rows[src * D + ch];
+                    }
+                }
+                if (lane == jj) mine += nk;
+            }
+        }
+    }
+    if (!WRITE && lane < ng) cnt[(item_of(lane) * 3 + k) * kOtmiRepSlices + sl] = mine;
+}
+
 }  // namespace evrep

@@ -754,6 +754,36 @@ def otmi_rep_clouds(reps, quad, B, workspace=None, slot="otmi_xt"):
     return Xt, m, m_cap
 
 
+def otmi_rep_clouds_bank(base, bank, slot, cand, quad, B, workspace=None):
+    """The clouds of len(cand) candidate stacks that differ in one channel (one step of the representation search):
+    base (B, S, S, C) letterboxed stack of the channels chosen so far, bank (B, S, S, R) letterboxed candidate channels
+    (same dtype, float64 / float32), item j * B + b = base[b] with channel `slot` replaced by bank[b, ..., cand[j]].
+    cand: host integers in [0, R).  Returns (Xt (items, 3, m_cap, C + 2) float64, m (items, 3) int64, m_cap): what
+    otmi_rep_clouds gives for the materialised items, as views of `workspace`."""
+    _require_gpu()
+    api = _lib.api()
+    dt = {torch.float64: _lib.F64, torch.float32: _lib.F32}
+    want(base, "base", (torch.float64, torch.float32), (int(B), None, None, None), device="cuda")
+    dev = base.device
+    Bn, S, S2, C = (int(v) for v in base.shape)
+    if S != S2:
+        raise ValueError("letterboxed representations are square")
+    want(bank, "bank", base.dtype, (Bn, S, S, None), device=dev)
+    want(quad, "quad", torch.int32, (Bn, 3), device=dev)
+    R = int(bank.shape[3])
+    cand = [int(c) for c in cand]
+    items = len(cand) * Bn
+    m_cap = (S - (S // 2 - 1)) ** 2
+    ws = workspace or _default_workspace(dev)
+    Xt = ws.typed("otmi_xt", (items, 3, m_cap, C + 2), torch.float64)
+    m = ws.typed("otmi_xt_m", (items, 3), torch.int64)
+    scratch = ws.typed("otmi_rep_scratch", (api.evrep_otmi_scratch_bytes(items),), torch.uint8)
+    with torch.cuda.device(dev):
+        api.evrep_otmi_rep_clouds_bank(_ptr(base), _ptr(bank), dt[base.dtype], Bn, S, C, R, int(slot), _lib.int32_array(cand), len(cand),
+                                       _ptr(quad), int(m_cap), _ptr(Xt), _ptr(m), _ptr(scratch), _stream_ptr())
+    return Xt, m, m_cap
+
+
 def otmi_batch(events, offsets, reps, height, width, h=0.7, workspace=None):
     """otmi(events_b, rep_{r,b}, height, width, S) for R representations x B windows, entirely on the device:
     events (total, 4) int32 cuda tensor + offsets (B+1), reps (R, B, S, S, C) letterboxed representations ->

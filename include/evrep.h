@@ -408,6 +408,22 @@ int evrep_otmi_event_clouds(const int32_t *events, const int64_t *offsets, int32
 int evrep_otmi_rep_clouds(const void *rep, int32_t rep_dtype, int32_t items, int32_t B, int32_t S, int32_t C,
                           const int32_t *quad, int64_t m_cap, double *Xt, int64_t *m_out, void *scratch, void *stream);
 
+/* One step of the representation search (representation_search/optimization.py:116-304): the clouds of n_cand candidate
+ * stacks that differ in ONE channel, without materialising them.
+ * base DEVICE (B, S, S, C): the letterboxed stack of the channels chosen so far (the others as the reference leaves them:
+ *   zeros inside the image, 114 in the letterbox rows); bank DEVICE (B, S, S, R): R letterboxed candidate channels,
+ *   channel-last; both of `dtype` (EVREP_F64 / EVREP_F32).  cand HOST int32 [n_cand], each in [0, R) (repeats allowed;
+ *   read before the call returns).
+ * Item i = j * B + b is candidate cand[j] on window b: base[b, y, x, :] with channel `slot` replaced by
+ *   bank[b, y, x, cand[j]].  Xt DEVICE double [items][3][m_cap][C+2] and m_out DEVICE int64 [items][3] receive exactly
+ *   what evrep_otmi_rep_clouds writes for these items = n_cand * B representations (quadrant cuts by quad, positional
+ *   channels, rows with sum |feat| > 0 and no NaN, STABLE order; rows from m_out on are left untouched).
+ * scratch DEVICE, 16-byte aligned, of evrep_otmi_scratch_bytes(items).  EVREP_EINVAL before any launch for a null
+ *   pointer, slot outside [0, C), a cand[j] outside [0, R), items > 65535, C + 2 > 32, S < 4, a misaligned scratch. */
+int evrep_otmi_rep_clouds_bank(const void *base, const void *bank, int32_t dtype, int32_t B, int32_t S, int32_t C, int32_t R,
+                               int32_t slot, const int32_t *cand, int32_t n_cand, const int32_t *quad, int64_t m_cap,
+                               double *Xt, int64_t *m_out, void *scratch, void *stream);
+
 /* Per-channel resize of a channel-last representation (B,H,W,C) -> (B,Ho,Wo,C), what resize_image /
  * resize_image_process do with cv2.resize per channel before a representation is stored or scored
  * (ev-YOLOv6/yolov6/data/gen4/precompute_reps.py:179-260,424; gen1_2yolo.py:230-265).  The interpolation is given as
