@@ -140,7 +140,7 @@ int evrep_bin_events(const evrep_plan *plan, const int32_t *events, const int64_
                      void *stream_) {
     int rc = check_common(plan, events, offsets, workspace);
     if (rc) return rc;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     const int B = plan->B, H = plan->H, W = plan->W, chunk = plan->chunk, nblk = plan->nblk;
     const int4 *ev = reinterpret_cast<const int4 *>(events);
     WindowMeta *meta = WS(WindowMeta, off_meta);
@@ -244,7 +244,7 @@ static int read_meta_field(const evrep_plan *plan, const void *workspace, size_t
 
 int evrep_copy_window_meta_async(const evrep_plan *plan, const void *workspace, void *meta_out, void *stream_) {
     if (!plan || plan->abi_version != EVREP_ABI_VERSION || !workspace || !meta_out) return EVREP_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     const char *meta = static_cast<const char *>(workspace) + plan->off_meta;
     if (plan->reserved == 2) {  // the key-sorted pass leaves the block statistics unmerged: merge them now
         char *ws = const_cast<char *>(static_cast<const char *>(workspace));
@@ -260,14 +260,14 @@ int evrep_copy_window_meta_async(const evrep_plan *plan, const void *workspace, 
 int evrep_read_status(const evrep_plan *plan, const void *workspace, uint32_t *status, void *stream_) {
     if (!plan || !workspace || !status) return EVREP_EINVAL;
     return read_meta_field(plan, workspace, offsetof(WindowMeta, status), sizeof(uint32_t), status,
-                           static_cast<hipStream_t>(stream_));
+                           as_stream(stream_));
 }
 
 int evrep_read_bbox(const evrep_plan *plan, const void *workspace, int32_t *bbox, void *stream_) {
     if (!plan || !workspace || !bbox) return EVREP_EINVAL;
     static_assert(offsetof(WindowMeta, ymax) - offsetof(WindowMeta, xmin) == 12, "xmin, xmax, ymin, ymax are contiguous");
     int rc = read_meta_field(plan, workspace, offsetof(WindowMeta, xmin), 4 * sizeof(int32_t), bbox,
-                             static_cast<hipStream_t>(stream_));
+                             as_stream(stream_));
     if (rc) return rc;
     for (int b = 0; b < plan->B; ++b) {  // stored xmin, xmax, ymin, ymax -> reported xmin, ymin, xmax, ymax
         const int32_t t = bbox[4 * b + 1];

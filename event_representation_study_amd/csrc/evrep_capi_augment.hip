@@ -6,8 +6,6 @@
 using namespace evrep;
 using evrep_host::hip_check;
 
-static inline bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-static inline bool bad_ptr(const void *p, uintptr_t a) { return !p || misaligned(p, a); }
 
 extern "C" {
 
@@ -26,7 +24,7 @@ int evrep_nimg_prepare(const int32_t *events, const int64_t *offsets, int32_t B,
     if (bad_ptr(events_out, 16) || bad_ptr(t_out, 8) || bad_ptr(tnorm_out, 8) || misaligned(xy_out, 16)) return EVREP_EINVAL;
     if (bad_ptr(offsets_out, 8) || bad_ptr(status_out, 4) || bad_ptr(scratch, 16)) return EVREP_EINVAL;
     if (B == 0) return EVREP_OK;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     char *sc = static_cast<char *>(scratch);
     uint32_t *slice_cnt = reinterpret_cast<uint32_t *>(sc);
     AugWindow *table = reinterpret_cast<AugWindow *>(sc + aug_off_table());

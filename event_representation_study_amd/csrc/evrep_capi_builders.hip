@@ -19,7 +19,7 @@ int evrep_event_stack(const evrep_plan *plan, const int32_t *events, const int64
     int rc = check_common(plan, events, offsets, workspace);
     if (rc) return rc;
     if (stack_size <= 0 || stack_size > EVREP_MAX_CHANNELS || !out) return EVREP_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     if (stream_allowed(plan, EVREP_PLAN_X_ESTACK_ORDERED)) {
         // after the key-sorted pass: the streaming form (k_event_stack_stream) -- one launch, every unit, no hot list
         const UnitCfg us = stream_cfg(plan, unit_cfg(plan, (size_t)stack_size * 4, 0, true, false));
@@ -65,8 +65,8 @@ int evrep_time_surface_ftime(const evrep_plan *plan, const int32_t *events, cons
     if (rc) return rc;
     if (tf && !indices) return EVREP_EINVAL;   // the dispatcher's cut search is defined on its integer timestamps
     if (slices <= 0 || slices > kMaxSlices || !out || !(tau > 0.0)) return EVREP_EINVAL;
-    if (out_dtype != EVREP_F64 && out_dtype != EVREP_F32) return EVREP_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!is_float_dtype(out_dtype)) return EVREP_EINVAL;
+    hipStream_t stream = as_stream(stream_);
     TsCuts *cuts = WS(TsCuts, off_cuts);
     // (the window statistics as a stream builder reads them: after the key-sorted pass, the block statistics of every run)
     k_ts_cuts<<<plan->B, 64, 0, stream>>>(bin_view(plan, events, workspace, true), reinterpret_cast<const int4 *>(events), offsets,
@@ -128,7 +128,7 @@ int evrep_tore_ftime(const evrep_plan *plan, const int32_t *events, const int64_
     if (rc) return rc;
     if (k <= 0 || k > kMaxToreK || frame_mode < 0 || frame_mode > 2 || !out) return EVREP_EINVAL;
     if (sample_times_f && !tf) return EVREP_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     if (stream_allowed(plan, EVREP_PLAN_X_TORE_ORDERED) && tf == nullptr && scale >= 0.0f) {
         // after the key-sorted pass, integer times: the streaming form (k_tore_stream) -- one launch, every unit and frame, no hot list
         const UnitCfg us = stream_cfg(plan, unit_cfg(plan, (size_t)2 * k * 4, 1));
@@ -192,7 +192,7 @@ static int voxel_launch(const evrep_plan *plan, const int32_t *events, const int
     if (rc) return rc;
     if (bins <= 0 || bins > EVREP_MAX_CHANNELS || mode < 0 || mode > 2 || !out) return EVREP_EINVAL;
     if (t_range && mode != 2) return EVREP_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     if (stream_allowed(plan, EVREP_PLAN_X_VOXEL_ORDERED)) {
         // after the key-sorted pass: the streaming form (k_voxel_stream) -- one launch, every unit, no hot list
         UnitCfg us = stream_cfg(plan, unit_cfg(plan, (size_t)bins * 8));
@@ -252,7 +252,7 @@ int evrep_voxel_subpixel(const evrep_plan *plan, const int32_t *events, const in
     int rc = check_common(plan, events, offsets, workspace);
     if (rc) return rc;
     if (bins <= 0 || bins > EVREP_MAX_CHANNELS || !out || (plan->total_events > 0 && !xy)) return EVREP_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     const dim3 grid((unsigned)(((size_t)plan->H * plan->W + kThreads - 1) / kThreads), (unsigned)plan->B);
     rc = ensure_column_sorted(plan, events, offsets, workspace, stream);
     if (rc) return rc;
@@ -280,7 +280,7 @@ int evrep_polstats(const evrep_plan *plan, const int32_t *events, const int64_t 
         P.pol[c] = pol[c];
         P.stat[c] = stat[c];
     }
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     UnitCfg uc = unit_cfg(plan, (size_t)C * 4, 0, true);  // float32 pixels of <= 64 B: 128-pixel part tiles (see UnitCfg)
     const int span = uc.span;
     // every statistic is order-free: two-chunk units (sparse windows) go to the hot launch whole as well -- measured, r05b: 1 Mpx
@@ -341,7 +341,7 @@ int evrep_est_voxel(const evrep_plan *plan, const int32_t *events, const int64_t
     P.C = C; P.nseg = nseg; P.nbucket = nbucket;
     P.lo = lo; P.inv_width = (double)nbucket / (hi - lo);
     for (int i = 0; i < C; ++i) P.shift[i] = (float)((double)i / (double)(C - 1));
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     if (int rc3 = ensure_pixel_stream(plan, events, offsets, workspace, stream)) return rc3;
     const UnitCfg uc = unit_cfg(plan, (size_t)2 * C * 4);
     const int seg = (uc.span + uc.merge) * kChunkPx;
@@ -360,8 +360,8 @@ int evrep_resize_taps(const void *in, int32_t in_dtype, int32_t B, int32_t H, in
                       const int32_t *xcount, const double *xwt, double scale, int32_t out_dtype, void *out, void *stream_) {
     if (!in || !out || !ystart || !ycount || !ywt || !xstart || !xcount || !xwt) return EVREP_EINVAL;
     if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || C <= 0 || Ho <= 0 || Wo <= 0 || T <= 0) return EVREP_EINVAL;
-    if ((in_dtype != EVREP_F64 && in_dtype != EVREP_F32) || (out_dtype != EVREP_F64 && out_dtype != EVREP_F32)) return EVREP_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!is_float_dtype(in_dtype) || !is_float_dtype(out_dtype)) return EVREP_EINVAL;
+    hipStream_t stream = as_stream(stream_);
     ResizeTaps tp;
     tp.ystart = ystart; tp.ycount = ycount; tp.xstart = xstart; tp.xcount = xcount; tp.ywt = ywt; tp.xwt = xwt; tp.T = T;
     const size_t per = (size_t)Ho * Wo * C;
@@ -376,10 +376,10 @@ int evrep_resize_taps(const void *in, int32_t in_dtype, int32_t B, int32_t H, in
 }
 
 int evrep_probe_store(void *out, size_t bytes, void *stream_) {
-    if (!out || (reinterpret_cast<uintptr_t>(out) & 15u)) return EVREP_EINVAL;
+    if (bad_ptr(out, 16)) return EVREP_EINVAL;
     const size_t tiles = bytes / 12288;
     if (tiles == 0 || tiles > 0x7fffffffu) return EVREP_EINVAL;
-    k_store_probe<<<(unsigned)tiles, kWave, 8320, static_cast<hipStream_t>(stream_)>>>(static_cast<float *>(out), (int)tiles);
+    k_store_probe<<<(unsigned)tiles, kWave, 8320, as_stream(stream_)>>>(static_cast<float *>(out), (int)tiles);
     LAUNCH_CHECK("k_store_probe");
     return EVREP_OK;
 }

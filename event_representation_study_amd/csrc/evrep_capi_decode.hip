@@ -6,8 +6,6 @@
 using namespace evrep;
 using evrep_host::hip_check;
 
-static inline bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-static inline bool bad_ptr(const void *p, uintptr_t a) { return !p || misaligned(p, a); }
 
 template <int F>
 static int decode_call(const void *raw, int64_t n, int32_t stride, int64_t first_index, int32_t H, int32_t W, uint32_t flags,
@@ -20,7 +18,7 @@ static int decode_call(const void *raw, int64_t n, int32_t stride, int64_t first
     if (misaligned(x, 16) || misaligned(y, 16) || misaligned(t, 16) || misaligned(p, 16)) return EVREP_EINVAL;
     if (n > 0 && (!raw || !x || !y || !t || !p || (flags == EVREP_DECODE_DROP_OOB && !scratch_))) return EVREP_EINVAL;
     if (n == 0) return EVREP_OK;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     const DecodeArgs a = {static_cast<const uint8_t *>(raw), n, first_index, stride, H, W, x, y, t, p, capacity, state};
     if (flags == EVREP_DECODE_STRICT) {
         k_decode_pass<F, kPassStrict><<<kDecGrid, kDecThreads, 0, stream>>>(a, nullptr);
@@ -50,7 +48,7 @@ size_t evrep_decode_scratch_bytes(int64_t n) {
 
 int evrep_decode_state_init(evrep_decode_state *state, void *stream_) {
     if (bad_ptr(state, 8)) return EVREP_EINVAL;
-    k_decode_init<<<1, 1, 0, static_cast<hipStream_t>(stream_)>>>(state);
+    k_decode_init<<<1, 1, 0, as_stream(stream_)>>>(state);
     LAUNCH_CHECK("k_decode_init");
     return EVREP_OK;
 }
@@ -73,7 +71,7 @@ int evrep_dat_seek_time(const int64_t *t, int64_t n, const int64_t *queries, int
     if (misaligned(queries, 8) || misaligned(out_idx, 8) || (nq > 0 && (!queries || !out_idx))) return EVREP_EINVAL;
     if (nq == 0) return EVREP_OK;
     const unsigned grid = (unsigned)((nq + kWinThreads / kWave - 1) / (kWinThreads / kWave));
-    k_dat_seek_time<<<grid, kWinThreads, 0, static_cast<hipStream_t>(stream_)>>>(t, n, queries, nq, term, out_idx);
+    k_dat_seek_time<<<grid, kWinThreads, 0, as_stream(stream_)>>>(t, n, queries, nq, term, out_idx);
     LAUNCH_CHECK("k_dat_seek_time");
     return EVREP_OK;
 }

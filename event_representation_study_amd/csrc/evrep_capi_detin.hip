@@ -9,8 +9,6 @@
 using namespace evrep;
 using evrep_host::hip_check;
 
-static inline bool bad_ptr(const void *p, uintptr_t a) { return !p || (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 template <typename T>
 static int detin_launch(const DetinArgs<double> &d, const void *rep, int32_t B, hipStream_t stream) {
     DetinArgs<T> a;
@@ -32,7 +30,7 @@ int evrep_detector_input(const void *rep, int32_t rep_dtype, int32_t B, int32_t 
                          int32_t T, const int32_t *ystart, const int32_t *ycount, const double *ywt, const int32_t *xstart,
                          const int32_t *xcount, const double *xwt, int32_t S, int32_t top, int32_t left, const double *pad,
                          const uint32_t *flags, const int32_t *warp, float scale, float *out, void *stream_) {
-    if (rep_dtype != EVREP_F64 && rep_dtype != EVREP_F32) return EVREP_EINVAL;
+    if (!is_float_dtype(rep_dtype)) return EVREP_EINVAL;
     if (B <= 0 || B > 65535 || C < 1 || C > EVREP_MAX_CHANNELS) return EVREP_EINVAL;
     if (H < 1 || W < 1 || H > EVREP_MAX_DIM || W > EVREP_MAX_DIM || S < 1 || S > EVREP_MAX_DIM) return EVREP_EINVAL;
     if (nh < 1 || nw < 1 || top < 0 || left < 0 || nh > S - top || nw > S - left || T < 1 || T > EVREP_MAX_DIM) return EVREP_EINVAL;
@@ -47,7 +45,7 @@ int evrep_detector_input(const void *rep, int32_t rep_dtype, int32_t B, int32_t 
     d.pad = pad; d.flags = flags; d.warp = warp; d.out = out;
     d.H = H; d.W = W; d.C = C; d.nh = nh; d.nw = nw; d.Tt = T; d.S = S; d.top = top; d.left = left;
     d.scale = scale;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     if (rep_dtype == EVREP_F64) return detin_launch<double>(d, rep, B, stream);
     return detin_launch<float>(d, rep, B, stream);
 }
@@ -60,13 +58,16 @@ int evrep_resize_tap_tables(const int32_t *axes, int32_t n_axes, int32_t max_dst
     TapTableArgs a;
     a.axes = axes; a.start = start; a.count = count; a.wt = weights; a.n_rows = n_rows; a.n_wt = n_wt; a.n_axes = n_axes;
     const dim3 grid((unsigned)n_axes, (unsigned)((max_dst + kThreads - 1) / kThreads));
-    k_resize_tap_tables<<<grid, kThreads, 0, static_cast<hipStream_t>(stream_)>>>(a);
+    k_resize_tap_tables<<<grid, kThreads, 0, as_stream(stream_)>>>(a);
     LAUNCH_CHECK("k_resize_tap_tables");
     return EVREP_OK;
 }
 
+// frames_dev: the device copy of the B frame descriptors
+static inline size_t detin_frames_bytes(int32_t B) { return (size_t)B * sizeof(evrep_detin_frame); }
+
 size_t evrep_detector_input_frames_scratch_bytes(int32_t B) {
-    return (B < 1 || B > 65535) ? 0 : (size_t)B * sizeof(evrep_detin_frame);
+    return (B < 1 || B > 65535) ? 0 : detin_frames_bytes(B);
 }
 
 // offset >= 0 and [offset, offset + n * per) inside [0, limit)
@@ -77,7 +78,7 @@ static inline bool run_inside(int32_t off, int32_t n, int32_t per, int64_t limit
 int evrep_detector_input_frames(const evrep_detin_frame *frames, int32_t B, int32_t rep_dtype, int32_t C, int32_t S,
                                 const int32_t *start, const int32_t *count, const double *weights, int64_t n_rows, int64_t n_wt,
                                 const double *pad, const int32_t *warp, float scale, void *frames_dev, float *out, void *stream_) {
-    if (rep_dtype != EVREP_F64 && rep_dtype != EVREP_F32) return EVREP_EINVAL;
+    if (!is_float_dtype(rep_dtype)) return EVREP_EINVAL;
     if (B <= 0 || B > 65535 || C < 1 || C > EVREP_MAX_CHANNELS || S < 1 || S > EVREP_MAX_DIM) return EVREP_EINVAL;
     if (n_rows < 1 || n_wt < 1 || n_rows > INT32_MAX || n_wt > INT32_MAX) return EVREP_EINVAL;
     if (!(scale == scale)) return EVREP_EINVAL;   // NaN
@@ -104,8 +105,8 @@ int evrep_detector_input_frames(const evrep_detin_frame *frames, int32_t B, int3
         warps = warps || (f.flags & EVREP_DETIN_WARP) != 0u;
     }
     if (warps ? bad_ptr(warp, 4) : warp != nullptr) return EVREP_EINVAL;   // the flag and the tables come together
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc = hip_check(hipMemcpyAsync(frames_dev, frames, (size_t)B * sizeof(evrep_detin_frame), hipMemcpyHostToDevice, stream),
+    hipStream_t stream = as_stream(stream_);
+    int rc = hip_check(hipMemcpyAsync(frames_dev, frames, detin_frames_bytes(B), hipMemcpyHostToDevice, stream),
                        "hipMemcpyAsync(frames)");
     if (rc != EVREP_OK) return rc;
     const int P = kThreads / ((C + kDetinGroup - 1) / kDetinGroup);   // pixels of a workgroup (evrep_detin.hip)

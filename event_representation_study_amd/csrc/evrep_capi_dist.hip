@@ -5,8 +5,6 @@
 
 using namespace evrep;
 
-static inline bool bad_ptr(const void *p, uintptr_t a) { return !p || (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 static inline bool dist_shape_ok(int32_t B, int32_t H, int32_t W) {
     return B > 0 && B <= EVREP_DIST_MAX_B && H > 0 && W > 0 && H <= EVREP_MAX_DIM && W <= EVREP_MAX_DIM;
 }
@@ -27,7 +25,7 @@ int evrep_dense_rank_f32(const float *keys, const int64_t *seg_offsets, int32_t 
                          void *stream_) {
     if (S <= 0 || S > EVREP_RANK_MAX_SEGMENTS) return EVREP_EINVAL;
     if (bad_ptr(keys, 4) || bad_ptr(seg_offsets, 8) || bad_ptr(out, 4) || bad_ptr(scratch, 16)) return EVREP_EINVAL;
-    if (reinterpret_cast<uintptr_t>(n_distinct_out) & 3u) return EVREP_EINVAL;
+    if (misaligned(n_distinct_out, 4)) return EVREP_EINVAL;
     RankArgs a;
     a.keys = keys;
     a.offsets = seg_offsets;      // read on the device: the scratch arrays are laid out by seg_offsets[S] there
@@ -36,7 +34,7 @@ int evrep_dense_rank_f32(const float *keys, const int64_t *seg_offsets, int32_t 
     a.scratch = static_cast<char *>(scratch);
     a.out = out;
     a.n_distinct = n_distinct_out;
-    k_dense_rank<<<S, kDistThreads, 0, static_cast<hipStream_t>(stream_)>>>(a);
+    k_dense_rank<<<S, kDistThreads, 0, as_stream(stream_)>>>(a);
     LAUNCH_CHECK("k_dense_rank");
     return EVREP_OK;
 }
@@ -51,7 +49,7 @@ int evrep_dist(const float *prim, int32_t B, int32_t H, int32_t W, double clip_r
     if (!dist_shape_ok(B, H, W) || dist_tiles(H, W) * 2 * B > INT32_MAX) return EVREP_EINVAL;
     if (!(clip_rate >= 0.0) || !(alpha == alpha)) return EVREP_EINVAL;      // (NaN fails)
     if (bad_ptr(prim, 4) || bad_ptr(out, 4) || bad_ptr(scratch, 16)) return EVREP_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     const size_t npx = (size_t)H * (size_t)W;
     const int S = 2 * B;
     char *sc = static_cast<char *>(scratch);

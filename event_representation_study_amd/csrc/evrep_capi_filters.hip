@@ -7,8 +7,6 @@
 using namespace evrep;
 using evrep_host::hip_check;
 
-static inline bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 // the window time bases, HOST -> the workspace slot that evrep_time_surface's cuts use between its own launches (every
 // time-surface call forms its cuts anew): B * 8 of its B * kTsCutsBytes bytes.  NULL stays NULL (base 0).
 static int stage_t_base(const evrep_plan *plan, void *workspace, const int64_t *t_base, hipStream_t stream, const int64_t **dev) {
@@ -38,10 +36,10 @@ int evrep_filter_pixel_fsm(const evrep_plan *plan, const int32_t *events, const 
     int rc = check_common(plan, events, offsets, workspace);
     if (rc) return rc;
     if (kind != EVREP_FILTER_REFRACTORY && kind != EVREP_FILTER_CONTRAST && kind != EVREP_FILTER_CHANGE_MAP) return EVREP_EINVAL;
-    if (!(param > 0.0) || !state || misaligned(state, kind == EVREP_FILTER_REFRACTORY ? 8 : 4)) return EVREP_EINVAL;
+    if (!(param > 0.0) || bad_ptr(state, kind == EVREP_FILTER_REFRACTORY ? 8 : 4)) return EVREP_EINVAL;
     if (plan->total_events > 0 && !keep) return EVREP_EINVAL;
     if (plan->total_events == 0) return EVREP_OK;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     if (int rc2 = pixel_stream(plan, events, offsets, workspace, stream)) return rc2;
     const int64_t *tb = nullptr;
     if (kind == EVREP_FILTER_REFRACTORY) if (int rc2 = stage_t_base(plan, workspace, t_base, stream, &tb)) return rc2;
@@ -69,10 +67,10 @@ int evrep_filter_background(const evrep_plan *plan, const int32_t *events, const
                             int32_t radius, const int64_t *t_base, double *state, uint8_t *keep, void *stream_) {
     int rc = check_common(plan, events, offsets, workspace);
     if (rc) return rc;
-    if (!(depth > 0.0) || radius < 1 || radius > EVREP_FILTER_MAX_RADIUS || !state || misaligned(state, 8)) return EVREP_EINVAL;
+    if (!(depth > 0.0) || radius < 1 || radius > EVREP_FILTER_MAX_RADIUS || bad_ptr(state, 8)) return EVREP_EINVAL;
     if (plan->total_events > 0 && !keep) return EVREP_EINVAL;
     if (plan->total_events == 0) return EVREP_OK;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     if (int rc2 = pixel_stream(plan, events, offsets, workspace, stream)) return rc2;
     const int64_t *tb = nullptr;
     if (int rc2 = stage_t_base(plan, workspace, t_base, stream, &tb)) return rc2;
@@ -93,10 +91,10 @@ int evrep_filter_mask_gather(const int32_t *events, const int64_t *offsets, int3
                              int64_t max_events_per_window, const uint8_t *mask, uint8_t *keep, void *stream_) {
     if (!offsets || !mask || !keep || B <= 0 || B > 65535 || H <= 0 || W <= 0 || H > EVREP_MAX_DIM || W > EVREP_MAX_DIM) return EVREP_EINVAL;
     if (max_events_per_window < 0 || max_events_per_window >= (int64_t)1 << 31) return EVREP_EINVAL;
-    if (max_events_per_window > 0 && (!events || misaligned(events, 16))) return EVREP_EINVAL;
+    if (max_events_per_window > 0 && bad_ptr(events, 16)) return EVREP_EINVAL;
     if (max_events_per_window == 0) return EVREP_OK;
     const dim3 grid((unsigned)((max_events_per_window + kFiltThreads - 1) / kFiltThreads), (unsigned)B);
-    k_filter_mask_gather<<<grid, kFiltThreads, 0, static_cast<hipStream_t>(stream_)>>>(reinterpret_cast<const int4 *>(events), offsets, H, W, mask, keep);
+    k_filter_mask_gather<<<grid, kFiltThreads, 0, as_stream(stream_)>>>(reinterpret_cast<const int4 *>(events), offsets, H, W, mask, keep);
     LAUNCH_CHECK("k_filter_mask_gather");
     return EVREP_OK;
 }
@@ -105,11 +103,11 @@ int evrep_filter_cell_map(const int32_t *events, int64_t total, int32_t H, int32
                           void *stream_) {
     if (total < 0 || total >= (int64_t)1 << 31 || H <= 0 || W <= 0 || H > EVREP_MAX_DIM || W > EVREP_MAX_DIM) return EVREP_EINVAL;
     if (fx < 1 || fy < 1 || fx > W || fy > H) return EVREP_EINVAL;
-    if (total > 0 && (!events || !events_out || misaligned(events, 16) || misaligned(events_out, 16))) return EVREP_EINVAL;
+    if (total > 0 && (bad_ptr(events, 16) || bad_ptr(events_out, 16))) return EVREP_EINVAL;
     if (total == 0) return EVREP_OK;
     const uint32_t mx = fx == 1 ? 0u : (uint32_t)(((uint64_t)1 << 32) / (uint32_t)fx + 1u);
     const uint32_t my = fy == 1 ? 0u : (uint32_t)(((uint64_t)1 << 32) / (uint32_t)fy + 1u);
-    k_filter_cell_map<<<(unsigned)((total + kFiltThreads - 1) / kFiltThreads), kFiltThreads, 0, static_cast<hipStream_t>(stream_)>>>(
+    k_filter_cell_map<<<(unsigned)((total + kFiltThreads - 1) / kFiltThreads), kFiltThreads, 0, as_stream(stream_)>>>(
         reinterpret_cast<const int4 *>(events), total, H, W, mx, my, reinterpret_cast<int4 *>(events_out));
     LAUNCH_CHECK("k_filter_cell_map");
     return EVREP_OK;
@@ -122,10 +120,9 @@ size_t evrep_filter_compact_scratch_bytes(int32_t B, int64_t total) {
 
 int evrep_filter_compact(const int32_t *events, const int64_t *offsets, int32_t B, const uint8_t *keep, int32_t *events_out,
                          int64_t *offsets_out, void *scratch, void *stream_) {
-    if (!offsets || !offsets_out || !scratch || B <= 0 || B > 65535) return EVREP_EINVAL;
-    if (!events || !keep || !events_out) return EVREP_EINVAL;   // (a batch without events still owns one-row allocations)
-    if (misaligned(events, 16) || misaligned(events_out, 16) || misaligned(offsets_out, 8) || misaligned(scratch, 16)) return EVREP_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!offsets || !keep || B <= 0 || B > 65535) return EVREP_EINVAL;   // (a batch without events still owns one-row allocations)
+    if (bad_ptr(events, 16) || bad_ptr(events_out, 16) || bad_ptr(offsets_out, 8) || bad_ptr(scratch, 16)) return EVREP_EINVAL;
+    hipStream_t stream = as_stream(stream_);
     const int4 *ev = reinterpret_cast<const int4 *>(events);
     uint32_t *sc = static_cast<uint32_t *>(scratch);
     k_filter_compact<false><<<kCompactSlices, kCompactThreads, 0, stream>>>(ev, offsets, B, keep, sc, nullptr);

@@ -8,45 +8,57 @@
 using namespace evrep;
 using evrep_host::hip_check;
 
+// The compile-time form of a pair's tile kernel.  SPLIT (clouds of <= kGwdSplitMaxD dimensions): S, T = gwd_split_steps of
+// ds, dt and the LDS holds the column tile's operands; else S, T = gwd_steps and it holds the row + column tile of both clouds.
+template <bool SPLIT, int S, int T>
+struct GwdForm { static constexpr size_t lds = SPLIT ? (size_t)2 * (S + T) * kTile * 16 : (size_t)2 * (2 * S + 2 * T) * kTile * sizeof(float); };
 
-template <int NSS, int NST>
-static int gwd_launch_tiles(const GwdTileArgs &P, hipStream_t stream) {
-    const size_t lds = (size_t)2 * (2 * NSS + 2 * NST) * kTile * sizeof(float);  // row + column tile of both clouds
-    // the widest instantiations need > 64 KB of dynamic LDS.  The opt-in is a property of (function, DEVICE); it is
-    // renewed on every launch that needs it instead of being remembered in a process-wide flag (a second device or a
-    // second host thread would find the flag set and the attribute missing)
-    if (lds > 64 * 1024) {
-        int rc = hip_check(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gwd_tiles<NSS, NST>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute(k_gwd_tiles)");
-        if (rc) return rc;
+// launch(GwdForm<...>()) for the form of (ds, dt): the one place that knows the forms, for the single and the batched solve.
+// (Split forms first, then float32 row by row: the order of first instantiation fixes the layout of the code object.)
+template <typename Launch>
+static int gwd_dispatch(int ds, int dt, Launch &&launch) {
+    if (gwd_use_split(ds, dt)) {
+        const int ms = gwd_split_steps(ds), mt = gwd_split_steps(dt);
+        if (ms == 2 && mt == 2) return launch(GwdForm<true, 2, 2>());
+        if (ms == 2) return launch(GwdForm<true, 2, 6>());
+        if (mt == 2) return launch(GwdForm<true, 6, 2>());
+        return launch(GwdForm<true, 6, 6>());
     }
-    k_gwd_tiles<NSS, NST><<<P.ntiles, kThreads, lds, stream>>>(P);
-    return EVREP_OK;
+    const int ss = gwd_steps(ds), st = gwd_steps(dt);
+    if (ss == 3) return st == 3 ? launch(GwdForm<false, 3, 3>()) : st == 8 ? launch(GwdForm<false, 3, 8>()) : launch(GwdForm<false, 3, 17>());
+    if (ss == 8) return st == 3 ? launch(GwdForm<false, 8, 3>()) : st == 8 ? launch(GwdForm<false, 8, 8>()) : launch(GwdForm<false, 8, 17>());
+    return st == 3 ? launch(GwdForm<false, 17, 3>()) : st == 8 ? launch(GwdForm<false, 17, 8>()) : launch(GwdForm<false, 17, 17>());
 }
 
-// split-form tiles (clouds of <= kGwdSplitMaxD dimensions): LDS = the column tile's operands
-template <int MS, int MT>
-static int gwd_launch_tiles_split(const GwdTileArgs &P, hipStream_t stream) {
-    const size_t lds = (size_t)2 * (MS + MT) * kTile * 16;
-    k_gwd_tiles_split<MS, MT><<<P.ntiles, kThreads, lds, stream>>>(P);
-    return EVREP_OK;
-}
-template <int MS, int MT>
-static int gwd_launch_tiles_split_batch(const GwdPair *pairs, int P, int64_t tile_cap, hipStream_t stream) {
-    const size_t lds = (size_t)2 * (MS + MT) * kTile * 16;
-    k_gwd_tiles_split_batch<MS, MT><<<dim3((unsigned)tile_cap, (unsigned)P), kThreads, lds, stream>>>(pairs);
-    return EVREP_OK;
+// The widest float32 instantiations need > 64 KB of dynamic LDS (the split forms never do).  The opt-in is a property of
+// (function, DEVICE); it is renewed on every launch that needs it instead of being remembered in a process-wide flag (a
+// second device or a second host thread would find the flag set and the attribute missing)
+static int gwd_lds_opt_in(const void *kernel, size_t lds, const char *what) {
+    if (lds <= 64 * 1024) return EVREP_OK;
+    return hip_check(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), what);
 }
 
-template <int NSS, int NST>
-static int gwd_launch_tiles_batch(const GwdPair *pairs, int P, int64_t tile_cap, hipStream_t stream) {
-    const size_t lds = (size_t)2 * (2 * NSS + 2 * NST) * kTile * sizeof(float);
-    if (lds > 64 * 1024) {
-        int rc = hip_check(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gwd_tiles_batch<NSS, NST>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute(k_gwd_tiles_batch)");
-        if (rc) return rc;
+// one workgroup per tile
+template <bool SPLIT, int S, int T>
+static int gwd_launch_tiles(GwdForm<SPLIT, S, T> form, const GwdTileArgs &P, hipStream_t stream) {
+    if constexpr (SPLIT) {
+        k_gwd_tiles_split<S, T><<<P.ntiles, kThreads, form.lds, stream>>>(P);
+    } else {
+        if (int rc = gwd_lds_opt_in(reinterpret_cast<const void *>(&k_gwd_tiles<S, T>), form.lds, "hipFuncSetAttribute(k_gwd_tiles)")) return rc;
+        k_gwd_tiles<S, T><<<P.ntiles, kThreads, form.lds, stream>>>(P);
     }
-    k_gwd_tiles_batch<NSS, NST><<<dim3((unsigned)tile_cap, (unsigned)P), kThreads, lds, stream>>>(pairs);
+    return EVREP_OK;
+}
+// workgroup (t, p): tile t of pair p; tile_cap = the tile count of the caller's size bounds
+template <bool SPLIT, int S, int T>
+static int gwd_launch_tiles_batch(GwdForm<SPLIT, S, T> form, const GwdPair *pairs, int P, int64_t tile_cap, hipStream_t stream) {
+    const dim3 grid((unsigned)tile_cap, (unsigned)P);
+    if constexpr (SPLIT) {
+        k_gwd_tiles_split_batch<S, T><<<grid, kThreads, form.lds, stream>>>(pairs);
+    } else {
+        if (int rc = gwd_lds_opt_in(reinterpret_cast<const void *>(&k_gwd_tiles_batch<S, T>), form.lds, "hipFuncSetAttribute(k_gwd_tiles_batch)")) return rc;
+        k_gwd_tiles_batch<S, T><<<grid, kThreads, form.lds, stream>>>(pairs);
+    }
     return EVREP_OK;
 }
 
@@ -61,22 +73,20 @@ struct GwScratch {
 template <typename T>
 static GwScratch<T> gw_carve(void *scratch, int64_t n, int64_t m) {
     GwScratch<T> w;
-    char *p = static_cast<char *>(scratch);
-    size_t o = 0;
-    auto take = [&](size_t b) { char *r = p ? p + o : nullptr; o += up256(b); return r; };
+    Carver c(scratch);
     w.ldn = gw_ld((int)n, sizeof(T)); w.ldm = gw_ld((int)m, sizeof(T));
-    w.hC1 = reinterpret_cast<T *>(take((size_t)n * w.ldn * sizeof(T)));
-    w.hC2 = reinterpret_cast<T *>(take((size_t)m * w.ldm * sizeof(T)));
-    w.ai = reinterpret_cast<T *>(take((size_t)n * sizeof(T)));
-    w.bj = reinterpret_cast<T *>(take((size_t)m * sizeof(T)));
-    w.Tp = reinterpret_cast<T *>(take((size_t)n * w.ldm * sizeof(T)));
-    w.G = reinterpret_cast<T *>(take((size_t)n * w.ldm * sizeof(T)));
-    w.Km = reinterpret_cast<T *>(take((size_t)n * w.ldm * sizeof(T)));
-    w.u = reinterpret_cast<double *>(take((size_t)n * sizeof(double)));
-    w.v = reinterpret_cast<double *>(take((size_t)m * sizeof(double)));
-    w.colpart = reinterpret_cast<double *>(take((size_t)kGwSlices * m * sizeof(double)));
-    w.losspart = reinterpret_cast<double *>(take((size_t)n * sizeof(double)));   // one loss partial per row
-    w.bytes = o;
+    w.hC1 = c.take<T>((size_t)n * w.ldn * sizeof(T));
+    w.hC2 = c.take<T>((size_t)m * w.ldm * sizeof(T));
+    w.ai = c.take<T>((size_t)n * sizeof(T));
+    w.bj = c.take<T>((size_t)m * sizeof(T));
+    w.Tp = c.take<T>((size_t)n * w.ldm * sizeof(T));
+    w.G = c.take<T>((size_t)n * w.ldm * sizeof(T));
+    w.Km = c.take<T>((size_t)n * w.ldm * sizeof(T));
+    w.u = c.take<double>((size_t)n * sizeof(double));
+    w.v = c.take<double>((size_t)m * sizeof(double));
+    w.colpart = c.take<double>((size_t)kGwSlices * m * sizeof(double));
+    w.losspart = c.take<double>((size_t)n * sizeof(double));   // one loss partial per row
+    w.bytes = c.off;
     return w;
 }
 
@@ -131,68 +141,64 @@ static int64_t pad_tile(int64_t n) { return (n + kTile - 1) / kTile * kTile; }
 constexpr size_t kGwdFormBytesMax = 192;
 static_assert(kGwdFormBytesMax >= 6 * 32 && kGwdFormBytesMax >= 2 * 17 * sizeof(float), "kGwdFormBytesMax");
 
+// scratch of one solve.  The scaled clouds are sized for the widest form, so the size depends on n and m alone.
+struct GwdScratch {
+    double *stat;                   // [2][kStatBlocks][2 * kGwdMaxD] partial sums, then [2][kGwdFin] final statistics
+    float *YsA, *YsB, *YtA, *YtB;   // scaled clouds s and t: row + column form
+    double *partial;                // per-tile, per-wave sums
+    size_t bytes;
+};
+constexpr size_t kGwdStatPartials = (size_t)2 * kStatBlocks * 2 * kGwdMaxD;
+static int64_t gwd_tiles_per_edge(int64_t n, int64_t m) { return pad_tile(n > m ? n : m) / kTile; }
+static GwdScratch gwd_carve(void *scratch, int64_t n, int64_t m) {
+    GwdScratch w;
+    Carver c(scratch);
+    const int64_t T = gwd_tiles_per_edge(n, m);
+    const size_t sbytes = kGwdFormBytesMax * (size_t)pad_tile(n), tbytes = kGwdFormBytesMax * (size_t)pad_tile(m);
+    w.stat = c.take<double>((kGwdStatPartials + 2 * kGwdFin) * sizeof(double));
+    w.YsA = c.take<float>(sbytes);
+    w.YsB = c.take<float>(sbytes);
+    w.YtA = c.take<float>(tbytes);
+    w.YtB = c.take<float>(tbytes);
+    w.partial = c.take<double>((size_t)(T * (T + 1) / 2) * kWaves * sizeof(double));
+    w.bytes = c.off;
+    return w;
+}
+
 size_t evrep_gwd_scratch_bytes(int64_t n, int64_t m) {
     if (n <= 0 || m <= 0) return 0;
-    const int64_t L = n > m ? n : m;
-    const int64_t T = pad_tile(L) / kTile;
-    size_t o = 0;
-    o += up256(((size_t)2 * kStatBlocks * 2 * kGwdMaxD + 2 * kGwdFin) * sizeof(double));   // statistics: partial sums + final
-    o += 2 * up256(kGwdFormBytesMax * (size_t)pad_tile(n));  // scaled cloud s: row + column form
-    o += 2 * up256(kGwdFormBytesMax * (size_t)pad_tile(m));  // scaled cloud t
-    o += up256((size_t)(T * (T + 1) / 2) * kWaves * sizeof(double));             // per-tile, per-wave sums
-    return o;
+    return gwd_carve(nullptr, n, m).bytes;
 }
 
 int evrep_gwd_padded_l1(const double *Xs, int64_t n, int32_t ds, const double *Xt, int64_t m, int32_t dt, double h,
                         void *scratch, double *cost, void *stream_) {
-    if (!Xs || !Xt || !scratch || !cost || n <= 0 || m <= 0 || ds <= 0 || dt <= 0 || ds > kGwdMaxD || dt > kGwdMaxD)
+    if (!Xs || !Xt || !cost || n <= 0 || m <= 0 || ds <= 0 || dt <= 0 || ds > kGwdMaxD || dt > kGwdMaxD)
         return EVREP_EINVAL;
-    if (!(h > 0.0) || (reinterpret_cast<uintptr_t>(scratch) & 255u)) return EVREP_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!(h > 0.0) || bad_ptr(scratch, 256)) return EVREP_EINVAL;
+    hipStream_t stream = as_stream(stream_);
     const int64_t L = n > m ? n : m;
-    const int T = (int)(pad_tile(L) / kTile);
+    const int T = (int)gwd_tiles_per_edge(n, m);
     if ((int64_t)T * (T + 1) / 2 * kWaves > 0x7fffffff) return EVREP_EINVAL;
-    char *p = static_cast<char *>(scratch);
-    double *stat_partial = reinterpret_cast<double *>(p); p += up256(((size_t)2 * kStatBlocks * 2 * kGwdMaxD + 2 * kGwdFin) * sizeof(double));
-    double *fin = stat_partial + (size_t)2 * kStatBlocks * 2 * kGwdMaxD;
+    const GwdScratch w = gwd_carve(scratch, n, m);
+    double *fin = w.stat + kGwdStatPartials;
     const int64_t npad = pad_tile(n), mpad = pad_tile(m);
-    const size_t sbytes = up256(kGwdFormBytesMax * (size_t)npad);
-    const size_t tbytes = up256(kGwdFormBytesMax * (size_t)mpad);
-    float *YsA = reinterpret_cast<float *>(p); p += sbytes;
-    float *YsB = reinterpret_cast<float *>(p); p += sbytes;
-    float *YtA = reinterpret_cast<float *>(p); p += tbytes;
-    float *YtB = reinterpret_cast<float *>(p); p += tbytes;
-    double *partial = reinterpret_cast<double *>(p);
-    // four launches per solve: the clouds' partial sums; one prep launch for both clouds (every block finishes
-    // the statistics itself); the tiles; the final sum
-    k_gwd_stats<<<dim3(kStatBlocks, 2), kThreads, 0, stream>>>(Xs, n, ds, Xt, m, dt, stat_partial);
+    // five launches per solve: the clouds' partial sums; their final statistics; one scaling launch for both clouds; the
+    // tiles; the final sum
+    k_gwd_stats<<<dim3(kStatBlocks, 2), kThreads, 0, stream>>>(Xs, n, ds, Xt, m, dt, w.stat);
     LAUNCH_CHECK("k_gwd_stats");
     const int sblocks = (int)((npad + kThreads - 1) / kThreads), tblocks = (int)((mpad + kThreads - 1) / kThreads);
-    k_gwd_stats_finish<<<2, 64, 0, stream>>>(stat_partial, n, ds, m, dt, h, fin);
+    k_gwd_stats_finish<<<2, 64, 0, stream>>>(w.stat, n, ds, m, dt, h, fin);
     LAUNCH_CHECK("k_gwd_stats_finish");
     // the split form spreads a point's chunks over blockIdx.z
     const int prep_z = gwd_use_split(ds, dt) ? 2 * gwd_split_steps(ds > dt ? ds : dt) : 1;
-    k_gwd_prep<<<dim3(sblocks + tblocks, 1, prep_z), kThreads, 0, stream>>>(Xs, n, ds, npad, Xt, m, dt, mpad, fin, sblocks, YsA, YsB, YtA, YtB);
+    k_gwd_prep<<<dim3(sblocks + tblocks, 1, prep_z), kThreads, 0, stream>>>(Xs, n, ds, npad, Xt, m, dt, mpad, fin, sblocks, w.YsA, w.YsB, w.YtA, w.YtB);
     LAUNCH_CHECK("k_gwd_prep");
     GwdTileArgs P;
-    P.YsA = YsA; P.YsB = YsB; P.YtA = YtA; P.YtB = YtB; P.n = n; P.m = m; P.npad = npad; P.mpad = mpad;
-    P.T = T; P.ntiles = T * (T + 1) / 2; P.partial = partial;
-    int rc = EVREP_OK;
-    const int ss = gwd_steps(ds), st = gwd_steps(dt);
-    if (gwd_use_split(ds, dt)) {
-        const int ms = gwd_split_steps(ds), mt = gwd_split_steps(dt);
-        if (ms == 2 && mt == 2) rc = gwd_launch_tiles_split<2, 2>(P, stream);
-        else if (ms == 2) rc = gwd_launch_tiles_split<2, 6>(P, stream);
-        else if (mt == 2) rc = gwd_launch_tiles_split<6, 2>(P, stream);
-        else rc = gwd_launch_tiles_split<6, 6>(P, stream);
-    } else
-#define GWD_CASE(A, B) if (ss == A && st == B) rc = gwd_launch_tiles<A, B>(P, stream)
-    GWD_CASE(3, 3); else GWD_CASE(3, 8); else GWD_CASE(3, 17); else GWD_CASE(8, 3); else GWD_CASE(8, 8);
-    else GWD_CASE(8, 17); else GWD_CASE(17, 3); else GWD_CASE(17, 8); else GWD_CASE(17, 17);
-#undef GWD_CASE
-    if (rc) return rc;
+    P.YsA = w.YsA; P.YsB = w.YsB; P.YtA = w.YtA; P.YtB = w.YtB; P.n = n; P.m = m; P.npad = npad; P.mpad = mpad;
+    P.T = T; P.ntiles = T * (T + 1) / 2; P.partial = w.partial;
+    if (int rc = gwd_dispatch(ds, dt, [&](auto form) { return gwd_launch_tiles(form, P, stream); })) return rc;
     LAUNCH_CHECK("k_gwd_tiles");
-    k_gwd_finish<<<1, 1024, 0, stream>>>(partial, P.ntiles * kWaves, (double)L, cost);
+    k_gwd_finish<<<1, 1024, 0, stream>>>(w.partial, P.ntiles * kWaves, (double)L, cost);
     LAUNCH_CHECK("k_gwd_finish");
     return EVREP_OK;
 }
@@ -205,13 +211,12 @@ size_t evrep_gwd_batch_scratch_bytes(int32_t P, int32_t ds, int32_t dt, int64_t 
 int evrep_gwd_padded_l1_batch(int32_t P, const double *Xs, const int64_t *xs_row, const int64_t *n, int32_t ds,
                               const double *Xt, const int64_t *xt_row, const int64_t *m, int32_t dt, int64_t n_cap,
                               int64_t m_cap, double h, void *scratch, double *costs, void *stream_) {
-    if (P <= 0 || P > 65535 || !Xs || !Xt || !n || !m || !scratch || !costs) return EVREP_EINVAL;
+    if (P <= 0 || P > 65535 || !Xs || !Xt || !n || !m || !costs) return EVREP_EINVAL;
     if (ds <= 0 || dt <= 0 || ds > kGwdMaxD || dt > kGwdMaxD || n_cap <= 0 || m_cap <= 0 || !(h > 0.0)) return EVREP_EINVAL;
-    if (reinterpret_cast<uintptr_t>(scratch) & 255u) return EVREP_EINVAL;
-    const int64_t Lc = n_cap > m_cap ? n_cap : m_cap;
-    const int64_t Tc = pad_tile(Lc) / kTile;
+    if (bad_ptr(scratch, 256)) return EVREP_EINVAL;
+    const int64_t Tc = gwd_tiles_per_edge(n_cap, m_cap);
     if (Tc * (Tc + 1) / 2 * kWaves > 0x7fffffff) return EVREP_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     const GwdBatchLayout L = gwd_batch_layout(P, ds, dt, n_cap, m_cap);
     GwdBatchArgs B;
     B.Xs = Xs; B.Xt = Xt; B.xs_row = xs_row; B.xt_row = xt_row; B.n = n; B.m = m; B.P = P; B.ds = ds; B.dt = dt;
@@ -220,8 +225,8 @@ int evrep_gwd_padded_l1_batch(int32_t P, const double *Xs, const int64_t *xs_row
     B.pairs = reinterpret_cast<GwdPair *>(B.scratch + L.off_pairs);
     B.total_tiles = reinterpret_cast<int64_t *>(B.scratch + L.off_total);
     B.partial = reinterpret_cast<double *>(B.scratch + L.off_partial);
-    // four launches for ALL pairs: the pair table; the clouds' partial sums; the scaling pass; the tiles (a fixed grid
-    // striding over the concatenated tile list, so no size has to be known on the host); the final sums
+    // six launches for ALL pairs: the pair table; the clouds' partial sums; their final statistics; the scaling pass; the
+    // tiles (a grid sized by the caller's bounds, so no size has to be known on the host); the final sums
     k_gwd_batch_setup<<<1, kThreads, 0, stream>>>(B);
     LAUNCH_CHECK("k_gwd_batch_setup");
     k_gwd_stats_batch<<<dim3(kStatBlocks, 2, P), kThreads, 0, stream>>>(B.pairs, ds, dt);
@@ -235,21 +240,8 @@ int evrep_gwd_padded_l1_batch(int32_t P, const double *Xs, const int64_t *xs_row
     if (P >= 8 && prep_z > 3) prep_z = 3;
     k_gwd_prep_batch<<<dim3(sblocks + tblocks, P, prep_z), kThreads, 0, stream>>>(B.pairs, ds, dt, sblocks);
     LAUNCH_CHECK("k_gwd_prep_batch");
-    int rc = EVREP_OK;
-    const int ss = gwd_steps(ds), st = gwd_steps(dt);
-    if (gwd_use_split(ds, dt)) {
-        const int ms = gwd_split_steps(ds), mt = gwd_split_steps(dt);
-        const int64_t cap = Tc * (Tc + 1) / 2;
-        if (ms == 2 && mt == 2) rc = gwd_launch_tiles_split_batch<2, 2>(B.pairs, P, cap, stream);
-        else if (ms == 2) rc = gwd_launch_tiles_split_batch<2, 6>(B.pairs, P, cap, stream);
-        else if (mt == 2) rc = gwd_launch_tiles_split_batch<6, 2>(B.pairs, P, cap, stream);
-        else rc = gwd_launch_tiles_split_batch<6, 6>(B.pairs, P, cap, stream);
-    } else
-#define GWD_CASE(A, Bq) if (ss == A && st == Bq) rc = gwd_launch_tiles_batch<A, Bq>(B.pairs, P, Tc * (Tc + 1) / 2, stream)
-    GWD_CASE(3, 3); else GWD_CASE(3, 8); else GWD_CASE(3, 17); else GWD_CASE(8, 3); else GWD_CASE(8, 8);
-    else GWD_CASE(8, 17); else GWD_CASE(17, 3); else GWD_CASE(17, 8); else GWD_CASE(17, 17);
-#undef GWD_CASE
-    if (rc) return rc;
+    const int64_t tile_cap = Tc * (Tc + 1) / 2;
+    if (int rc = gwd_dispatch(ds, dt, [&](auto form) { return gwd_launch_tiles_batch(form, B.pairs, P, tile_cap, stream); })) return rc;
     LAUNCH_CHECK("k_gwd_tiles_batch");
     k_gwd_finish_batch<<<P, 1024, 0, stream>>>(B.pairs, costs);
     LAUNCH_CHECK("k_gwd_finish_batch");
@@ -264,10 +256,9 @@ size_t evrep_otmi_scratch_bytes(int32_t count) {
 
 int evrep_otmi_event_clouds(const int32_t *events, const int64_t *offsets, int32_t B, int32_t height, int32_t width,
                             int64_t cap, double *Xs, int64_t *n_out, int32_t *quad_out, void *scratch, void *stream_) {
-    if (!events || !offsets || !Xs || !n_out || !quad_out || !scratch || B <= 0 || B > 65535 || height <= 1 || width <= 1 || cap <= 0)
-        return EVREP_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(events) & 15u) || (reinterpret_cast<uintptr_t>(scratch) & 15u)) return EVREP_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!offsets || !Xs || !n_out || !quad_out || B <= 0 || B > 65535 || height <= 1 || width <= 1 || cap <= 0) return EVREP_EINVAL;
+    if (bad_ptr(events, 16) || bad_ptr(scratch, 16)) return EVREP_EINVAL;
+    hipStream_t stream = as_stream(stream_);
     const int4 *ev = reinterpret_cast<const int4 *>(events);
     const OtmiEvScratch w = otmi_ev_scratch(scratch, B);
     const dim3 grid(kOtmiEvSlices, B);
@@ -284,11 +275,10 @@ int evrep_otmi_event_clouds(const int32_t *events, const int64_t *offsets, int32
 
 int evrep_otmi_rep_clouds(const void *rep, int32_t rep_dtype, int32_t items, int32_t B, int32_t S, int32_t C,
                           const int32_t *quad, int64_t m_cap, double *Xt, int64_t *m_out, void *scratch, void *stream_) {
-    if (!rep || !quad || !Xt || !m_out || !scratch || items <= 0 || items > 65535 || B <= 0 || S < 4 || C <= 0 || C + 2 > kGwdMaxD || m_cap <= 0)
+    if (!rep || !quad || !Xt || !m_out || items <= 0 || items > 65535 || B <= 0 || S < 4 || C <= 0 || C + 2 > kGwdMaxD || m_cap <= 0)
         return EVREP_EINVAL;
-    if (rep_dtype != EVREP_F64 && rep_dtype != EVREP_F32) return EVREP_EINVAL;
-    if (reinterpret_cast<uintptr_t>(scratch) & 15u) return EVREP_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!is_float_dtype(rep_dtype) || bad_ptr(scratch, 16)) return EVREP_EINVAL;
+    hipStream_t stream = as_stream(stream_);
     uint32_t *cnt = static_cast<uint32_t *>(scratch);
     const dim3 grid(kOtmiRepSlices, 3, items);
 #define OTMI_REP(T)                                                                                                          \
@@ -305,15 +295,14 @@ int evrep_otmi_rep_clouds(const void *rep, int32_t rep_dtype, int32_t items, int
 int evrep_otmi_rep_clouds_bank(const void *base, const void *bank, int32_t dtype, int32_t B, int32_t S, int32_t C, int32_t R,
                                int32_t slot, const int32_t *cand, int32_t n_cand, const int32_t *quad, int64_t m_cap,
                                double *Xt, int64_t *m_out, void *scratch, void *stream_) {
-    if (!base || !bank || !cand || !quad || !Xt || !m_out || !scratch || B <= 0 || n_cand <= 0 || S < 4 || C <= 0 || C + 2 > kGwdMaxD ||
+    if (!base || !bank || !cand || !quad || !Xt || !m_out || B <= 0 || n_cand <= 0 || S < 4 || C <= 0 || C + 2 > kGwdMaxD ||
         R <= 0 || m_cap <= 0 || slot < 0 || slot >= C)
         return EVREP_EINVAL;
-    if (dtype != EVREP_F64 && dtype != EVREP_F32) return EVREP_EINVAL;
+    if (!is_float_dtype(dtype) || bad_ptr(scratch, 16)) return EVREP_EINVAL;
     if ((int64_t)n_cand * B > 65535) return EVREP_EINVAL;
     for (int32_t j = 0; j < n_cand; ++j)
         if (cand[j] < 0 || cand[j] >= R) return EVREP_EINVAL;
-    if (reinterpret_cast<uintptr_t>(scratch) & 15u) return EVREP_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     uint32_t *cnt = static_cast<uint32_t *>(scratch);
     const size_t lds = (size_t)kOtmiBankWaves * otmi_bank_lds_doubles(C + 2) * sizeof(double);
     // the candidates' bank channels reach the device as kernel arguments (cand is HOST memory and is not read after the
@@ -347,10 +336,10 @@ size_t evrep_gw_scratch_bytes(int64_t n, int64_t m, int32_t precision) {
 int evrep_entropic_gw(const double *C1, int64_t n, const double *C2, int64_t m, const double *p, const double *q,
                       int32_t loss, double epsilon, int32_t outer_iters, int32_t sinkhorn_iters, int32_t precision,
                       void *scratch, double *T_out, double *gw_out, void *stream_) {
-    if (!C1 || !C2 || !p || !q || !scratch || !gw_out || n <= 0 || m <= 0 || n > 46340 || m > 46340) return EVREP_EINVAL;
+    if (!C1 || !C2 || !p || !q || !gw_out || n <= 0 || m <= 0 || n > 46340 || m > 46340) return EVREP_EINVAL;
     if ((loss != 0 && loss != 1) || !(epsilon > 0.0) || outer_iters < 0 || sinkhorn_iters < 1) return EVREP_EINVAL;
-    if ((precision != EVREP_F64 && precision != EVREP_F32) || (reinterpret_cast<uintptr_t>(scratch) & 255u)) return EVREP_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!is_float_dtype(precision) || bad_ptr(scratch, 256)) return EVREP_EINVAL;
+    hipStream_t stream = as_stream(stream_);
     if (precision == EVREP_F32)
         return gw_solve<float>(C1, (int)n, C2, (int)m, p, q, loss, epsilon, outer_iters, sinkhorn_iters, scratch, T_out, gw_out, stream);
     return gw_solve<double>(C1, (int)n, C2, (int)m, p, q, loss, epsilon, outer_iters, sinkhorn_iters, scratch, T_out, gw_out, stream);

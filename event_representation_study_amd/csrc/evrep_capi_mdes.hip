@@ -7,9 +7,8 @@ extern "C" {
 
 int evrep_mdes_sbt_windows(const int32_t *events, const int64_t *offsets, int32_t B, int32_t H, int32_t W, int32_t *bounds,
                            uint32_t *flags, void *stream_) {
-    if (!events || !offsets || !bounds || !flags || B <= 0 || B > 65535 || H <= 0 || W <= 0) return EVREP_EINVAL;
-    if (reinterpret_cast<uintptr_t>(events) & 15u) return EVREP_EINVAL;
-    k_mdes_sbt_windows<<<B, 1024, 0, static_cast<hipStream_t>(stream_)>>>(reinterpret_cast<const int4 *>(events), offsets, H, W, bounds, flags);
+    if (bad_ptr(events, 16) || !offsets || !bounds || !flags || B <= 0 || B > 65535 || H <= 0 || W <= 0) return EVREP_EINVAL;
+    k_mdes_sbt_windows<<<B, 1024, 0, as_stream(stream_)>>>(reinterpret_cast<const int4 *>(events), offsets, H, W, bounds, flags);
     LAUNCH_CHECK("k_mdes_sbt_windows");
     return EVREP_OK;
 }
@@ -26,9 +25,9 @@ int evrep_mdes_ex(const evrep_plan *plan, const int32_t *events, const int64_t *
     int rc = check_common(plan, events, offsets, workspace);
     if (rc) return rc;
     if (C <= 0 || C > EVREP_MAX_CHANNELS || !window || !func || !agg || !out) return EVREP_EINVAL;
-    if (out_dtype != EVREP_F64 && out_dtype != EVREP_F32) return EVREP_EINVAL;
+    if (!is_float_dtype(out_dtype)) return EVREP_EINVAL;
     if ((bounds == nullptr) != (flags == nullptr)) return EVREP_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     MdesParams P;
     memset(&P, 0, sizeof(P));
     P.C = C;

@@ -1,6 +1,6 @@
-// evrep_capi_shared.h -- what the translation units of the extern "C" surface share on the host side (r05: the library is
-// built from four translation units compiled in parallel -- evrep_capi.hip: plan / binning / read-backs, evrep_capi_mdes.hip:
-// MixedDensityEventStack, evrep_capi_builders.hip: the other builders, evrep_capi_gwd.hip: GWD / OTMI clouds / entropic GW).
+// evrep_capi_shared.h -- what the translation units of the extern "C" surface share on the host side: the status plumbing,
+// the argument checks every entry point is written with, and the carver every scratch layout is written with.  The library is
+// built from fifteen translation units compiled in parallel (build.SOURCES; each says in its first line what it holds).
 // No allocation, no global state besides the thread-local last HIP error string, no environment variable read.
 #pragma once
 #include <stddef.h>
@@ -27,12 +27,34 @@ EVREP_HIDDEN int column_sort_keys(const evrep_plan *plan, const int32_t *events,
 
 static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// The argument checks of the entry points.  a: the alignment in bytes, a power of two.  An OPTIONAL pointer (NULL allowed) is
+// held to its alignment with misaligned(): NULL passes; a required one with bad_ptr().
+static inline bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+static inline bool bad_ptr(const void *p, uintptr_t a) { return !p || misaligned(p, a); }
+static inline bool is_float_dtype(int32_t dtype) { return dtype == EVREP_F64 || dtype == EVREP_F32; }
+static inline hipStream_t as_stream(void *stream) { return static_cast<hipStream_t>(stream); }
+
 static inline int check_common(const evrep_plan *plan, const void *events, const void *offsets, const void *ws) {
     if (!plan || plan->abi_version != EVREP_ABI_VERSION || !offsets || !ws) return EVREP_EINVAL;
     if (plan->total_events > 0 && !events) return EVREP_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(events) & 15u) || (reinterpret_cast<uintptr_t>(ws) & 255u)) return EVREP_EINVAL;
+    if (misaligned(events, 16) || misaligned(ws, 256)) return EVREP_EINVAL;
     return EVREP_OK;
 }
+
+// One description per scratch region: a layout function walks the region with a Carver, part by part, each part starting on a
+// 256-byte boundary.  The *_scratch_bytes function runs it over a null base and reads `off`; the entry point runs it over the
+// caller's scratch and reads the pointers.  (Regions a kernel carves too keep __host__ __device__ *_off_* functions instead.)
+struct Carver {
+    char *base;        // may be null: sizes only
+    size_t off = 0;    // bytes taken so far
+    explicit Carver(void *scratch) : base(static_cast<char *>(scratch)) {}
+    template <typename T>
+    T *take(size_t bytes) {
+        T *part = reinterpret_cast<T *>(base ? base + off : nullptr);
+        off += up256(bytes);
+        return part;
+    }
+};
 
 #define WS(type, field) reinterpret_cast<type *>(static_cast<char *>(workspace) + plan->field)
 #define CWS(type, field) reinterpret_cast<const type *>(static_cast<const char *>(workspace) + plan->field)

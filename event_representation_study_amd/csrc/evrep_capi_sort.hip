@@ -6,8 +6,6 @@
 using namespace evrep;
 using evrep_host::hip_check;
 
-static inline bool bad_ptr(const void *p, uintptr_t a) { return !p || (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 static inline bool sort_shape_ok(int32_t B, int32_t H, int32_t W, int32_t K) {
     return B > 0 && B <= EVREP_SORT_MAX_B && H > 0 && W > 0 && H <= EVREP_MAX_DIM && W <= EVREP_MAX_DIM && (K == 1 || K == 2);
 }
@@ -24,7 +22,7 @@ int evrep_time_index(const double *t, const int64_t *offsets, int32_t B, int32_t
     if (B < 0 || B > EVREP_SORT_MAX_B || (mode != EVREP_TIME_INDEX_RAW && mode != EVREP_TIME_INDEX_RANK)) return EVREP_EINVAL;
     if (bad_ptr(t, 8) || bad_ptr(offsets, 8) || bad_ptr(out, 8) || bad_ptr(status_out, 4) || bad_ptr(scratch, 16)) return EVREP_EINVAL;
     if (B == 0) return EVREP_OK;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     char *sc = static_cast<char *>(scratch);
     uint32_t *slice_cnt = reinterpret_cast<uint32_t *>(sc);
     uint32_t *win_start = reinterpret_cast<uint32_t *>(sc + ti_off_start());
@@ -70,7 +68,7 @@ int evrep_sort_image(const float *prim, int32_t B, int32_t H, int32_t W, int32_t
     a.strict = (flags & EVREP_SORT_STRICT) ? 1 : 0;
     a.use_image = (flags & EVREP_SORT_USE_IMAGE) ? 1 : 0;
     a.nq = nq;
-    k_sort_image<<<(unsigned)(B * K), kDistThreads, 0, static_cast<hipStream_t>(stream_)>>>(a);
+    k_sort_image<<<(unsigned)(B * K), kDistThreads, 0, as_stream(stream_)>>>(a);
     LAUNCH_CHECK("k_sort_image");
     return EVREP_OK;
 }

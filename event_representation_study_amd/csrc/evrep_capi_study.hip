@@ -7,8 +7,6 @@
 using namespace evrep;
 using evrep_host::hip_check;
 
-static inline bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-static inline bool bad_ptr(const void *p, uintptr_t a) { return !p || misaligned(p, a); }
 
 extern "C" {
 
@@ -27,7 +25,7 @@ int evrep_nimg_study_rows(const int32_t *rows, const double *t, const double *xy
     if ((want & EVREP_STUDY_STACK) && bad_ptr(rows_stack, 16)) return EVREP_EINVAL;
     if ((want & EVREP_STUDY_TORE) && (bad_ptr(rows_tore, 16) || bad_ptr(xy, 16) || bad_ptr(sample_times, 8))) return EVREP_EINVAL;
     if (B == 0) return EVREP_OK;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     StudyWindow *win = static_cast<StudyWindow *>(scratch);
     if (int rc = hip_check(hipMemsetAsync(win, 0xFF, study_scratch_bytes(B), stream), "hipMemsetAsync(study windows)")) return rc;
     StudyArgs a;

@@ -5,8 +5,6 @@
 
 using namespace evrep;
 
-static inline bool bad_ptr(const void *p, uintptr_t a) { return !p || (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 // values of a window, or 0 for sizes the entry points refuse
 static inline uint32_t voxnorm_window(int32_t B, int32_t H, int32_t W, int32_t bins) {
     if (B < 1 || B > 65535 || H < 1 || W < 1 || bins < 1 || bins > EVREP_MAX_CHANNELS) return 0;   // windows ride gridDim.y
@@ -23,8 +21,17 @@ static inline void voxnorm_geometry(uint32_t N, uint32_t V, VoxnormArgs &a) {
     a.slices = (a.groups + a.slice_groups - 1) / a.slice_groups;
 }
 
-// scratch: sum1, sum2 [B][slices] double, cnt [B][slices] uint32, head [B][2] double; each part sized for kMaxSlices slices
-static inline size_t voxnorm_part_bytes(int32_t B) { return up256((size_t)B * kMaxSlices * sizeof(double)); }
+// scratch: sum1, sum2 [B][slices] double, cnt [B][slices] uint32, each sized for kMaxSlices slices of double, then head [B][2]
+// double; into `a`.  Returns the region's bytes
+static inline size_t voxnorm_carve(void *scratch, int32_t B, VoxnormArgs &a) {
+    Carver c(scratch);
+    const size_t part = (size_t)B * kMaxSlices * sizeof(double);
+    a.sum1 = c.take<double>(part);
+    a.sum2 = c.take<double>(part);
+    a.cnt = c.take<uint32_t>(part);
+    a.head = c.take<double>((size_t)B * 2 * sizeof(double));
+    return c.off;
+}
 
 template <typename T, bool VEC>
 static int voxnorm_launch(const VoxnormArgs &a, int32_t B, hipStream_t stream) {
@@ -45,39 +52,33 @@ extern "C" {
 
 size_t evrep_voxel_normalize_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t bins) {
     if (!voxnorm_window(B, H, W, bins)) return 0;
-    return 3 * voxnorm_part_bytes(B) + up256((size_t)B * 2 * sizeof(double));
+    VoxnormArgs a;
+    return voxnorm_carve(nullptr, B, a);
 }
 
 int evrep_voxel_normalize(const void *grid, int32_t grid_dtype, int32_t B, int32_t H, int32_t W, int32_t bins, uint32_t flags,
                           float *out, double *stats_out, void *scratch, void *stream_) {
-    if (grid_dtype != EVREP_F64 && grid_dtype != EVREP_F32) return EVREP_EINVAL;
+    if (!is_float_dtype(grid_dtype)) return EVREP_EINVAL;
     if (flags & ~EVREP_VOXNORM_NORMALIZE) return EVREP_EINVAL;
     const uint32_t N = voxnorm_window(B, H, W, bins);
     if (!N) return EVREP_EINVAL;
     const bool normalize = (flags & EVREP_VOXNORM_NORMALIZE) != 0u;
     if (bad_ptr(grid, 16) || bad_ptr(out, 16)) return EVREP_EINVAL;
     if (normalize ? bad_ptr(scratch, 16) : stats_out != nullptr) return EVREP_EINVAL;   // statistics come with the normalisation
-    if (reinterpret_cast<uintptr_t>(stats_out) & 15u) return EVREP_EINVAL;
+    if (misaligned(stats_out, 16)) return EVREP_EINVAL;
     const uint32_t V = grid_dtype == EVREP_F64 ? 2u : 4u;
     VoxnormArgs a;
     memset(&a, 0, sizeof(a));
     voxnorm_geometry(N, V, a);
     a.grid = grid; a.out = out; a.stats = stats_out;
-    if (normalize) {
-        const size_t part = voxnorm_part_bytes(B);
-        char *sc = static_cast<char *>(scratch);
-        a.sum1 = reinterpret_cast<double *>(sc);
-        a.sum2 = reinterpret_cast<double *>(sc + part);
-        a.cnt = reinterpret_cast<uint32_t *>(sc + 2 * part);
-        a.head = reinterpret_cast<double *>(sc + 3 * part);
-    }
+    if (normalize) voxnorm_carve(scratch, B, a);
     a.HW = (uint32_t)((int64_t)H * W);
     a.bins = (uint32_t)bins;
     a.tiles = (a.HW + kTilePx - 1) / kTilePx;
     a.normalize = normalize ? 1u : 0u;
     // one 16-byte load per group where every window starts on a 16-byte boundary; the grouping, and with it every sum, is the same
     const bool vec = N % V == 0;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     if (grid_dtype == EVREP_F64) return vec ? voxnorm_launch<double, true>(a, B, stream) : voxnorm_launch<double, false>(a, B, stream);
     return vec ? voxnorm_launch<float, true>(a, B, stream) : voxnorm_launch<float, false>(a, B, stream);
 }

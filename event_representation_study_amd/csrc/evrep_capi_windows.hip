@@ -6,8 +6,6 @@
 using namespace evrep;
 using evrep_host::hip_check;
 
-static inline bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-static inline bool bad_ptr(const void *p, uintptr_t a) { return !p || misaligned(p, a); }
 
 extern "C" {
 
@@ -17,7 +15,7 @@ int evrep_time_to_index(const int64_t *t, int64_t n, const int64_t *queries, int
     if (misaligned(queries, 8) || misaligned(out_idx, 8) || (nq > 0 && (!queries || !out_idx))) return EVREP_EINVAL;
     if (nq == 0) return EVREP_OK;
     const unsigned grid = (unsigned)((nq + kWinThreads / kWave - 1) / (kWinThreads / kWave));
-    k_time_to_index<<<grid, kWinThreads, 0, static_cast<hipStream_t>(stream_)>>>(t, n, queries, nq, out_idx);
+    k_time_to_index<<<grid, kWinThreads, 0, as_stream(stream_)>>>(t, n, queries, nq, out_idx);
     LAUNCH_CHECK("k_time_to_index");
     return EVREP_OK;
 }
@@ -32,7 +30,7 @@ int evrep_windows_gather(const uint16_t *x, const uint16_t *y, const int64_t *t,
     if (bad_ptr(events_out, 16) || bad_ptr(base_out, 8) || bad_ptr(status_out, 4)) return EVREP_EINVAL;
     if (misaligned(base_in, 8) || (rebase_mode == EVREP_REBASE_GIVEN && !base_in)) return EVREP_EINVAL;
     if (B == 0) return EVREP_OK;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     if (int rc = hip_check(hipMemsetAsync(status_out, 0, (size_t)B * sizeof(uint32_t), stream), "hipMemsetAsync(status_out)")) return rc;
     k_windows_gather<<<kGatherGrid, kWinThreads, 0, stream>>>(x, y, t, p, n, i0, i1, dst_offsets, B, rebase_mode, base_in,
                                                              reinterpret_cast<int4 *>(events_out), base_out, status_out);

@@ -151,9 +151,8 @@ size_t evrep_est_backward_scratch_bytes(int64_t total_events, int32_t nseg) {
 int evrep_est_voxel_backward(const int32_t *events, const int64_t *offsets, int32_t B, int32_t H, int32_t W, const float *tnorm,
                              int32_t C, const double *segments, int32_t nseg, const uint32_t *buckets, int32_t nbucket, double lo,
                              double hi, const float *grad_out, double *grad_seg, void *scratch, void *stream_) {
-    if (!events || !offsets || !tnorm || !segments || !buckets || !grad_out || !grad_seg || !scratch) return EVREP_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(events) & 15u) || (reinterpret_cast<uintptr_t>(scratch) & 15u) ||
-        (reinterpret_cast<uintptr_t>(grad_seg) & 7u)) return EVREP_EINVAL;
+    if (!offsets || !tnorm || !segments || !buckets || !grad_out) return EVREP_EINVAL;
+    if (bad_ptr(events, 16) || bad_ptr(scratch, 16) || bad_ptr(grad_seg, 8)) return EVREP_EINVAL;
     if (B < 1 || H < 1 || W < 1 || H > EVREP_MAX_DIM || W > EVREP_MAX_DIM) return EVREP_EINVAL;
     if (C < 2 || C > kEstMaxBins || nseg < 1 || nseg > EVREP_EST_BWD_MAX_SEG || nbucket < 1 || !(hi > lo)) return EVREP_EINVAL;
     EstParams P;
@@ -169,7 +168,7 @@ int evrep_est_voxel_backward(const int32_t *events, const int64_t *offsets, int3
     a.bucket = buckets;
     a.gout = grad_out;
     a.B = B; a.H = H; a.W = W;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipStream_t stream = as_stream(stream_);
     int32_t *range = static_cast<int32_t *>(scratch);
     double *rows = reinterpret_cast<double *>(static_cast<char *>(scratch) + eb_off_rows());
     const size_t lds = (size_t)2 * nseg * sizeof(double);

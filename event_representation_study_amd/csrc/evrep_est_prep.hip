@@ -135,23 +135,24 @@ __global__ __launch_bounds__(kEpThreads) void k_est_prep_write(const float *__re
 using namespace evrep;
 using evrep_host::hip_check;
 
+// scratch: uint32 [B] keys, uint32 [1] status accumulator
+static inline size_t est_prep_scratch_bytes(int32_t B) { return ((size_t)B + 1) * sizeof(uint32_t); }
+
 extern "C" {
 
 size_t evrep_est_prepare_scratch_bytes(int64_t n, int32_t B) {
     if (n <= 0 || B <= 0 || B > kEpMaxB) return 0;
-    return up256(((size_t)B + 1) * sizeof(uint32_t));
+    return up256(est_prep_scratch_bytes(B));
 }
 
 int evrep_est_prepare(const float *events5, int64_t n, int32_t B, int32_t H, int32_t W, int32_t *rows, int64_t *offsets,
                       float *tnorm, uint32_t *status, void *scratch, void *stream_) {
-    if (!events5 || !rows || !offsets || !tnorm || !status || !scratch) return EVREP_EINVAL;
     if (n <= 0 || B <= 0 || B > kEpMaxB || H < 1 || W < 1 || H > EVREP_MAX_DIM || W > EVREP_MAX_DIM) return EVREP_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(rows) & 15u) || (reinterpret_cast<uintptr_t>(events5) & 3u) ||
-        (reinterpret_cast<uintptr_t>(offsets) & 7u) || (reinterpret_cast<uintptr_t>(tnorm) & 3u) ||
-        (reinterpret_cast<uintptr_t>(status) & 3u) || (reinterpret_cast<uintptr_t>(scratch) & 3u)) return EVREP_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (bad_ptr(events5, 4) || bad_ptr(rows, 16) || bad_ptr(offsets, 8) || bad_ptr(tnorm, 4) || bad_ptr(status, 4) || bad_ptr(scratch, 4))
+        return EVREP_EINVAL;
+    hipStream_t stream = as_stream(stream_);
     uint32_t *keys = static_cast<uint32_t *>(scratch);
-    if (int rc = hip_check(hipMemsetAsync(keys, 0, ((size_t)B + 1) * sizeof(uint32_t), stream), "hipMemsetAsync(est_prepare)")) return rc;
+    if (int rc = hip_check(hipMemsetAsync(keys, 0, est_prep_scratch_bytes(B), stream), "hipMemsetAsync(est_prepare)")) return rc;
     const int64_t want = (n + kEpThreads - 1) / kEpThreads;
     const int groups = (int)(want < kEpMaxGroups ? want : kEpMaxGroups);
     k_est_prep_scan<<<groups, kEpThreads, 0, stream>>>(events5, n, B, H, W, offsets, keys);

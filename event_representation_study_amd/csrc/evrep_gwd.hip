@@ -531,11 +531,11 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MS + M
 }
 
 // ---------------------------------------------------------------------------------------------- batched solves
-// P independent (Xs, Xt) pairs in FOUR launches in all (r03; one solve alone is four launches, three of them tiny:
-// 21.6 of 91 us).  The clouds' sizes live on the DEVICE (the harness kernels of evrep_otmi.hip produce them), so
-// nothing here depends on a host read-back: k_gwd_batch_setup derives every pair's paddings, tile count and
-// scratch pointers; the statistics / scaling grids are sized by the caller's upper bounds (surplus blocks leave at
-// once); the tile kernel is a fixed grid of workgroups striding over the concatenated tile list of all pairs.
+// P independent (Xs, Xt) pairs in SIX launches in all: setup, statistics, statistics-finish, scaling, tiles, final sums
+// (one solve alone is the last five, all but the tiles tiny: r03 measured 21.6 of 91 us).  The clouds' sizes live on the
+// DEVICE (the harness kernels of evrep_otmi.hip produce them), so nothing here depends on a host read-back:
+// k_gwd_batch_setup derives every pair's paddings, tile count and scratch pointers; the statistics, scaling and tile
+// grids are sized by the caller's upper bounds (surplus blocks leave at once; see k_gwd_tiles_batch).
 struct GwdPair {
     GwdTileArgs a;          // a.partial points at this pair's first tile sum
     const double *Xs, *Xt;

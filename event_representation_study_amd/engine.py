@@ -680,7 +680,7 @@ def _default_workspace(device):
 
 
 def gwd_padded_l1_batch(Xs, n, Xt, m, n_cap, m_cap, xs_row=None, xt_row=None, h=0.7, out=None, workspace=None):
-    """P solves of OTMI(Xs, Xt, h).solve()[1] in ONE call (five launches in all, no host synchronisation).
+    """P solves of OTMI(Xs, Xt, h).solve()[1] in ONE call (six launches in all, no host synchronisation).
     Xs: (rows, ds) float64 cuda tensor holding every source cloud, pair p = rows [xs_row[p], xs_row[p] + n[p])
     (xs_row None: p * n_cap); Xt / xt_row / m likewise.  n, m, xs_row, xt_row: int64 cuda tensors of length P (the sizes
     may come straight from the device harness).  n_cap, m_cap: host upper bounds of the sizes.  Returns (P,) float64

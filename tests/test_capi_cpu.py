@@ -97,6 +97,145 @@ def test_null_and_misaligned_pointers_are_refused_before_any_launch(lib):
     assert lib.evrep_gwd_scratch_bytes(12500, 14400) > 14 * 14400 * 4
 
 
+def test_scratch_sizes_are_the_published_ones(lib):
+    """Scratch sizes are a contract: callers size allocations they keep across library versions with them.  The table was
+    recorded by tests/golden/make_golden_scratch_sizes.py, a handful of argument tuples per function, one per edge of its
+    formula."""
+    import json
+    from event_representation_study_amd import _lib
+    with open(os.path.join(ROOT, "tests", "golden", "scratch_sizes.json")) as f:
+        table = json.load(f)
+    assert sorted(table) == sorted(name for name in _lib.SYMBOLS if name.endswith("_scratch_bytes"))
+    for name, rows in table.items():
+        assert len(rows) >= 4, name
+        for args, size in rows:
+            assert getattr(lib, name)(*args) == size, (name, args)
+
+
+# The pointer arguments of every entry point whose checks are written with the shared helpers of evrep_capi_shared.h, in
+# call order: _p(a) a required pointer aligned to a bytes (1: no alignment stated), _opt(a) an optional one (NULL allowed,
+# a misaligned one refused), _PLAN a real plan (B 1, 8 x 8, 4 events), _host(...) an int32 array the entry reads on the host,
+# _FRAME one frame descriptor read on the host; everything else is a scalar inside its stated range.  Each call is valid but
+# for its addresses, which are made up: the test runs only where there is no device.
+def _p(align=1):
+    return ("ptr", align)
+
+
+def _opt(align):
+    return ("opt", align)
+
+
+def _host(*values):
+    return ("host", values)
+
+
+_PLAN, _FRAME = ("plan",), ("frame",)
+_COMMON = [_PLAN, _p(16), _p(), _p(256)]
+_POINTER_TABLE = {
+    "evrep_bin_events": _COMMON + [None],
+    "evrep_probe_store": [_p(16), 12288, None],
+    "evrep_mdes": _COMMON + [2, _host(0, 0), _host(0, 0), _host(0, 0), 1.0, 0, _p(), None],
+    "evrep_mdes_ex": _COMMON + [2, _host(0, 0), _host(0, 0), _host(0, 0), 1.0, 0, _p(), _opt(1), _opt(1), None],
+    "evrep_optimized": _COMMON + [1.0, 0, _p(), None],
+    "evrep_mdes_sbt_windows": [_p(16), _p(), 1, 8, 8, _p(), _p(), None],
+    "evrep_event_stack": _COMMON + [4, 0, 1.0, _p(), None],
+    "evrep_time_surface": _COMMON + [2, _opt(1), 1.0, 0, 1.0, 0, _p(), None],
+    "evrep_time_surface_ftime": _COMMON + [2, _opt(1), _opt(1), 1.0, 0, 1.0, 0, _p(), None],
+    "evrep_tore": _COMMON + [2, 0, _opt(1), 1.0, _p(), None],
+    "evrep_tore_ftime": _COMMON + [2, 0, _opt(1), _opt(1), _opt(1), 1.0, _p(), None],
+    "evrep_voxel": _COMMON + [2, 0, 1.0, _p(), None],
+    "evrep_voxel_range": _COMMON + [2, 0, 1.0, _opt(1), _p(), None],
+    "evrep_voxel_tnorm": _COMMON + [_p(), 2, 1.0, _p(), None],
+    "evrep_voxel_subpixel": _COMMON + [_p(), 2, _opt(1), _p(), None],
+    "evrep_polstats": _COMMON + [_p(), 2, _host(0, 0), _host(0, 0), 0.3, _p(), None],
+    "evrep_est_voxel": _COMMON + [_p(), 2, _p(), 1, _p(), 1, 0.0, 1.0, _p(), None],
+    "evrep_est_voxel_backward": [_p(16), _p(), 1, 8, 8, _p(), 2, _p(), 1, _p(), 1, 0.0, 1.0, _p(), _p(8), _p(16), None],
+    "evrep_est_prepare": [_p(4), 10, 1, 8, 8, _p(16), _p(8), _p(4), _p(4), _p(4), None],
+    "evrep_gwd_padded_l1": [_p(), 10, 4, _p(), 10, 4, 0.7, _p(256), _p(), None],
+    "evrep_gwd_padded_l1_batch": [2, _p(), _opt(1), _p(), 4, _p(), _opt(1), _p(), 4, 10, 10, 0.7, _p(256), _p(), None],
+    "evrep_otmi_event_clouds": [_p(16), _p(), 1, 8, 8, 10, _p(), _p(), _p(), _p(16), None],
+    "evrep_otmi_rep_clouds": [_p(), 0, 1, 1, 4, 2, _p(), 10, _p(), _p(), _p(16), None],
+    "evrep_otmi_rep_clouds_bank": [_p(), _p(), 0, 1, 4, 2, 3, 0, _host(0, 1), 2, _p(), 10, _p(), _p(), _p(16), None],
+    "evrep_resize_taps": [_p(), 0, 1, 8, 8, 1, 4, 4, 1, _p(), _p(), _p(), _p(), _p(), _p(), 1.0, 0, _p(), None],
+    "evrep_entropic_gw": [_p(), 4, _p(), 4, _p(), _p(), 0, 0.1, 1, 1, 0, _p(256), _opt(1), _p(), None],
+    "evrep_filter_pixel_fsm": _COMMON + [0, 1.0, None, _p(8), _p(), None],
+    "evrep_filter_background": _COMMON + [1.0, 1, None, _p(8), _p(), None],
+    "evrep_filter_mask_gather": [_p(16), _p(), 1, 8, 8, 4, _p(), _p(), None],
+    "evrep_filter_cell_map": [_p(16), 4, 8, 8, 1, 1, _p(16), None],
+    "evrep_filter_compact": [_p(16), _p(), 1, _p(), _p(16), _p(8), _p(16), None],
+    "evrep_time_to_index": [_p(8), 4, _p(8), 2, _p(8), None],
+    "evrep_windows_gather": [_p(2), _p(2), _p(8), _p(), 4, _p(8), _p(8), _p(8), 1, 0, _opt(8), _p(16), _p(8), _p(4), None],
+    "evrep_nimg_prepare": [_p(16), _p(8), 1, _opt(8), _p(8), 1.0, 1.0, 8, 8, 0, _p(16), _p(8), _p(8), _opt(16), _p(8), _p(4), _p(16), None],
+    "evrep_dist": [_p(4), 1, 8, 8, 0.99, 3.0, _p(4), _p(16), None],
+    "evrep_dense_rank_f32": [_p(4), _p(8), 1, _p(4), _opt(4), _p(16), None],
+    "evrep_time_index": [_p(8), _p(8), 1, 0, _p(8), _p(4), _p(16), None],
+    "evrep_sort_image": [_p(4), 1, 8, 8, 1, 0, _host(1, 2), 2, _p(4), _p(4), _p(16), None],
+    "evrep_nimg_study_rows": [_p(16), _p(8), _p(16), _p(8), 1, 8, 8, 7, _p(16), _p(16), _p(16), _p(8), _p(4), _p(16), None],
+    "evrep_detector_input": [_p(8), 0, 1, 8, 8, 1, 4, 4, 1, _p(4), _p(4), _p(8), _p(4), _p(4), _p(8), 8, 0, 0, _p(8), _opt(4), _opt(4),
+                             1.0, _p(4), None],
+    "evrep_resize_tap_tables": [_p(4), 1, 8, _p(4), _p(4), _p(8), 16, 16, None],
+    "evrep_detector_input_frames": [_FRAME, 1, 0, 1, 8, _p(4), _p(4), _p(8), 64, 64, _p(8), _opt(4), 1.0, _p(8), _p(4), None],
+    "evrep_voxel_normalize": [_p(16), 0, 1, 8, 8, 2, 1, _p(16), _opt(16), _p(16), None],
+    "evrep_decode_state_init": [_p(8), None],
+    "evrep_decode_dat": [_p(16), 4, 8, 0, 8, 8, 0, _p(16), _p(16), _p(16), _p(16), 10, _p(8), _opt(256), None],
+    "evrep_decode_bin5": [_p(16), 4, 0, 8, 8, 0, _p(16), _p(16), _p(16), _p(16), 10, _p(8), _opt(256), None],
+    "evrep_dat_seek_time": [_p(8), 4, _p(8), 2, 1, _p(8), None],
+}
+
+
+def _pointer_cases():
+    cases = [(name, -1, "valid") for name in _POINTER_TABLE]
+    for name, spec in _POINTER_TABLE.items():
+        for i, a in enumerate(spec):
+            if not isinstance(a, tuple):
+                continue
+            if a[0] != "opt":
+                cases.append((name, i, "null"))
+            if a[0] in ("ptr", "opt") and a[1] > 1:
+                cases.append((name, i, "misaligned"))
+    return cases
+
+
+@pytest.mark.parametrize("name,index,fault", _pointer_cases(), ids=lambda v: str(v))
+def test_every_pointer_check_refuses_before_any_launch(lib, name, index, fault):
+    """One call per pointer argument and fault: a required pointer NULL, a pointer with a stated alignment off by half of it.
+    Each is EVREP_EINVAL; the call with no fault gets past the argument checks (and fails in HIP: there is no device)."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present: made-up addresses must never be able to reach a launch")
+    from event_representation_study_amd._lib import DetinFrame, Plan, EVREP_EINVAL
+    fn = getattr(lib, name)
+    keep, args = [], []
+    for i, (a, ctype) in enumerate(zip(_POINTER_TABLE[name], fn.argtypes)):
+        if not isinstance(a, tuple):
+            args.append(a)
+            continue
+        if i == index and fault == "null":
+            args.append(None)
+            continue
+        if a[0] == "plan":
+            keep.append(Plan())
+            assert lib.evrep_plan_init(ctypes.byref(keep[-1]), 1, 8, 8, 4, 4) == 0
+            address = ctypes.addressof(keep[-1])
+        elif a[0] == "host":
+            keep.append((ctypes.c_int32 * len(a[1]))(*a[1]))
+            address = ctypes.addressof(keep[-1])
+        elif a[0] == "frame":
+            keep.append(DetinFrame(src=0x7000000, H=8, W=8, rh=4, rw=4, T1=1, nh=4, nw=4))
+            address = ctypes.addressof(keep[-1])
+        elif a[0] == "opt" and i != index:
+            address = None
+        else:
+            address = 0x10000000 + 0x100000 * i + (a[1] // 2 if i == index else 0)
+        args.append(None if address is None else ctypes.cast(ctypes.c_void_p(address), ctype))
+    assert len(args) == len(fn.argtypes)
+    rc = fn(*args)
+    if fault == "valid":
+        assert rc != EVREP_EINVAL
+    else:
+        assert rc == EVREP_EINVAL
+
+
 def test_no_cpu_fallback():
     """Without a GPU the product path must fail loudly (never route through the oracle)."""
     import torch
