@@ -187,7 +187,7 @@ int evrep_gwd_padded_l1(const double *Xs, int64_t n, int32_t ds, const double *X
     k_gwd_stats<<<dim3(kStatBlocks, 2), kThreads, 0, stream>>>(Xs, n, ds, Xt, m, dt, w.stat);
     LAUNCH_CHECK("k_gwd_stats");
     const int sblocks = (int)((npad + kThreads - 1) / kThreads), tblocks = (int)((mpad + kThreads - 1) / kThreads);
-    k_gwd_stats_finish<<<2, 64, 0, stream>>>(w.stat, n, ds, m, dt, h, fin);
+    k_gwd_stats_finish<<<2, 64, 0, stream>>>(Xs, Xt, w.stat, n, ds, m, dt, h, fin);
     LAUNCH_CHECK("k_gwd_stats_finish");
     // the split form spreads a point's chunks over blockIdx.z
     const int prep_z = gwd_use_split(ds, dt) ? 2 * gwd_split_steps(ds > dt ? ds : dt) : 1;

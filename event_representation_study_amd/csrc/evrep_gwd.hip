@@ -19,9 +19,12 @@ constexpr int kTile = 128;  // tile edge; 4 waves, each a 32-row strip of four 3
 constexpr int kStatBlocks = 64;  // partial-sum blocks per cloud
 
 
-// Block `blk` of kStatBlocks sums x and x^2 per dimension over its slice of one cloud
-// (float64, one pass; the clouds hold O(1e4) points of magnitude <= 255, so sum(x^2)/N - mean^2
-// keeps ~1e-11 relative accuracy, far inside the 1e-5 budget).  dst: this cloud's [kStatBlocks][2*kGwdMaxD].
+// Block `blk` of kStatBlocks sums u and u^2 per dimension over its slice of one cloud, u = x - pivot, the pivot being the
+// cloud's row 0 (float64, one pass).  The variance sum(u^2)/N - (sum(u)/N)^2 then does not depend on where the cloud sits:
+// sum(x^2)/N - mean^2 on the raw coordinates lost it to cancellation once |mean| >> sigma (timestamps in microseconds:
+// 4e-3 relative cost error at an offset of 1e6 sigma, NaN beyond 1e8).  The pivot is a point of the cloud, so
+// (mean - pivot)^2 <= N var whatever row 0 is (an outlier included), and the cancellation costs at most ~N ulps of the
+// variance: 1e-12 for O(1e4) points.  A constant dimension gives u = 0 exactly.  dst: this cloud's [kStatBlocks][2*kGwdMaxD].
 __device__ __forceinline__ void gwd_stats_body(const double *__restrict__ X, int64_t N, int d, int blk, double *__restrict__ dst,
                                       double (*red)[2 * kGwdMaxD]) {
     const int64_t per = (N + kStatBlocks - 1) / kStatBlocks;
@@ -33,7 +36,7 @@ __device__ __forceinline__ void gwd_stats_body(const double *__restrict__ X, int
         const double *row = X + i * d;
 #pragma unroll
         for (int k = 0; k < kGwdMaxD; ++k)
-            if (k < d) { const double v = gload_f64(row + k); s[k] += v; q[k] += v * v; }
+            if (k < d) { const double v = gload_f64(row + k) - gload_f64(X + k); s[k] += v; q[k] += v * v; }
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -155,30 +158,33 @@ __device__ inline void gwd_split_chunk(const double *__restrict__ xrow, const do
 
 // The cloud statistics from the 64 partial sums, once per cloud (r03: every block of the scaling pass used to redo this
 // chain of 128 dependent loads): fin[k] = mean of dimension k, fin[kGwdMaxD] = sqrt(log2(e) / (2 h^2 sigma^2)).
-// sigma^2 = mean ||a - abar||^2 = sum_k (E[x_k^2] - E[x_k]^2).  One wave.
-__device__ __forceinline__ void gwd_stats_finish_body(const double *__restrict__ stat_cloud, int64_t N, int d, double h,
-                                             double *__restrict__ fin) {
+// sigma^2 = mean ||a - abar||^2 = sum_k (E[u_k^2] - E[u_k]^2), u = x - X[0] as gwd_stats_body sums it; mean_k = X[0][k] + E[u_k].
+// One wave.
+__device__ __forceinline__ void gwd_stats_finish_body(const double *__restrict__ X, const double *__restrict__ stat_cloud, int64_t N,
+                                             int d, double h, double *__restrict__ fin) {
     const int k = threadIdx.x;
     if (k >= 32) return;
-    double sx = 0.0, sq = 0.0;
+    double sx = 0.0, sq = 0.0, pivot = 0.0;
     if (k < d) {
         const double *p = stat_cloud + 2 * k;
 #pragma unroll 16
         for (int j = 0; j < kStatBlocks; ++j) { sx += gload_f64(p + (size_t)j * (2 * kGwdMaxD)); sq += gload_f64(p + (size_t)j * (2 * kGwdMaxD) + 1); }
+        pivot = gload_f64(X + k);
     }
-    const double mean = sx / (double)N;
-    double var = (k < d) ? sq / (double)N - mean * mean : 0.0;
+    const double mu = sx / (double)N;   // the mean of u
+    double var = (k < d) ? sq / (double)N - mu * mu : 0.0;
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) var += __shfl_xor(var, o, 64);
-    gstore_f64(fin + k, mean);
+    gstore_f64(fin + k, pivot + mu);
     if (k == 0) gstore_f64(fin + kGwdMaxD, sqrt(1.4426950408889634 / (2.0 * h * h * var)));
 }
 constexpr int kGwdFin = kGwdMaxD + 1;   // doubles per cloud behind the partial sums
 // grid (2), 64 threads
-__global__ __launch_bounds__(64) void k_gwd_stats_finish(const double *__restrict__ stat_partial, int64_t n, int ds, int64_t m, int dt,
+__global__ __launch_bounds__(64) void k_gwd_stats_finish(const double *__restrict__ Xs, const double *__restrict__ Xt,
+                                                        const double *__restrict__ stat_partial, int64_t n, int ds, int64_t m, int dt,
                                                         double h, double *__restrict__ fin) {
     const int c = blockIdx.x;
-    gwd_stats_finish_body(stat_partial + (size_t)c * kStatBlocks * (2 * kGwdMaxD), c ? m : n, c ? dt : ds, h, fin + c * kGwdFin);
+    gwd_stats_finish_body(c ? Xt : Xs, stat_partial + (size_t)c * kStatBlocks * (2 * kGwdMaxD), c ? m : n, c ? dt : ds, h, fin + c * kGwdFin);
 }
 
 // One block of the scaling pass of ONE cloud (blk = its index among the cloud's ceil(Npad / 256) blocks): centres /
@@ -648,7 +654,7 @@ __global__ __launch_bounds__(64) void k_gwd_stats_finish_batch(const GwdPair *__
     const GwdPair &q = pairs[blockIdx.y];
     if (q.a.ntiles == 0) return;
     const int c = blockIdx.x;
-    gwd_stats_finish_body(q.stat + (size_t)c * kStatBlocks * (2 * kGwdMaxD), c ? q.a.m : q.a.n, c ? dt : ds, h,
+    gwd_stats_finish_body(c ? q.Xt : q.Xs, q.stat + (size_t)c * kStatBlocks * (2 * kGwdMaxD), c ? q.a.m : q.a.n, c ? dt : ds, h,
                           q.stat + (size_t)2 * kStatBlocks * (2 * kGwdMaxD) + c * kGwdFin);
 }
 

@@ -369,9 +369,13 @@ int evrep_probe_store(void *out, size_t bytes, void *stream);
  * POT's max_iter=0 path: mean over the LxL zero-padded grid of |Ks - Kt|.
  * Xs DEVICE double [n,ds], Xt DEVICE double [m,dt] (ds, dt <= 32); scratch DEVICE of
  * evrep_gwd_scratch_bytes(n, m), 256-byte aligned; cost DEVICE double [1].
- * Arithmetic: float64 statistics; the pairwise exponents in float32 accuracy on the matrix cores -- clouds of <= 15
+ * Arithmetic: float64 statistics (mean and variance per dimension from the sums of x - row 0 and its square, so the score
+ * does not depend on where a cloud sits: timestamps in microseconds need no rebasing; a cloud of one point or of equal points has
+ * sigma = 0 and costs NaN, as in the reference); the pairwise exponents in float32 accuracy on the matrix cores -- clouds of <= 15
  * dimensions (both) as exact three-way bfloat16 splits of the float32 operands (v_mfma_f32_32x32x16_bf16), wider ones as
- * float32 MFMA chains; exponentials in float32; sums in float64.  Measured 5e-9 relative against the float64 value, the
+ * float32 MFMA chains; exponentials in float32; sums in float64.  Measured against the float64 value: 5e-9 relative on
+ * uniform clouds of 1e4 points at h = 0.7; up to 9e-7 on clouds of two or three points; 6.8e-6 at worst (the split form at
+ * h = 0.2 on a cloud a quarter of whose points agree in 12 of 14 columns; tests/test_gpu_gwd_edges.py, NOTES.md).  The
  * reference's budget is 1e-5. */
 size_t evrep_gwd_scratch_bytes(int64_t n, int64_t m);
 int evrep_gwd_padded_l1(const double *Xs, int64_t n, int32_t ds, const double *Xt, int64_t m, int32_t dt,

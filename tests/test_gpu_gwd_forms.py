@@ -4,6 +4,10 @@ Clouds of up to 15 dimensions take the split form (each float32 coordinate as th
 pipe, r03); wider ones keep the float32 MFMA chain.  Both must hold the 1e-5 budget with a wide margin (1e-7 asserted here;
 5e-9-class measured) for every instantiation, for ragged sizes around the 128-point tile edge, and for either cloud being
 the larger one (the tiles behind the smaller cloud take the one-sided path).
+
+Reached here, single solves only: split <2,2> <2,6> <6,2> <6,6>, float32 <3,17> <17,3> <17,17> <17,8>.  The rest -- float32
+<8,17>, every batched form, exact tile edges, structured clouds, other bandwidths, translated and degenerate clouds -- is in
+test_gpu_gwd_edges.py.
 """
 import numpy as np
 import pytest
