@@ -400,6 +400,17 @@ int evrep_gwd_padded_l1_batch(int32_t P, const double *Xs, const int64_t *xs_row
  *   float32 x / ((W-1)//2), y / ((H-1)//2), (t - t0) / (t1 - t0), (p - pmin) / (pmax - pmin), rows with
  *   x < (W-1)//2 and y < (H-1)//2 kept, :164-173): Xs DEVICE double [B][3][cap][4], n_out DEVICE int64 [B][3],
  *   quad_out DEVICE int32 [B][3] (which quadrant each slot holds).  cap >= the longest window.
+ *   Held to the reference's arithmetic at its edges (tests/test_gpu_otmi_edges.py):
+ *   - an event outside the frame (x < 0, x >= W, y < 0, y >= H, any int32) belongs to no quadrant; the column x = W/2 - 1
+ *     is the last one on the left, so with an odd W the middle column is on the right (likewise rows);
+ *   - among equally populated quadrants the FIRST one is skipped (all four of an empty window: quadrant 0);
+ *   - a scored quadrant without an event gives n_out = 0 and the rows of its slot are not written (the reference raises
+ *     there; a cost formed from such a slot is NaN);
+ *   - t0 and t1 are the quadrant's first and last member in ARRAY order and the differences are taken in int64 before
+ *     the float32 rounding, so any int32 timestamps and polarities, descending or unsorted ones included, divide as in
+ *     the reference: a quadrant of one timestamp (or one event) has NaN in the t column, one of a single polarity NaN in
+ *     the p column (0 / 0), and with t0 == t1 among other timestamps the column holds +inf, -inf and NaN;
+ *   - H = 2 or W = 2 keeps no row ((W-1)//2 = 0): n_out = 0 in all three slots.
  * evrep_otmi_rep_clouds: rep DEVICE (items, S, S, C) letterboxed representations, item i belongs to window i % B ->
  *   for slot k the cut of quadrant quad[i % B][k] (:150-155,177-179), two positional channels (:181-198), rows with
  *   sum |feat| > 0 (:200-202): Xt DEVICE double [items][3][m_cap][C+2], m_out DEVICE int64 [items][3];

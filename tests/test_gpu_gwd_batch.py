@@ -3,7 +3,8 @@
 * evrep_gwd_padded_l1_batch: costs equal the single-solve entry point BIT FOR BIT (same tile sums, same summation order),
   for ragged pairs, pairs sharing a cloud, and against the oracle's closed form within 1e-5.
 * evrep_otmi_event_clouds / evrep_otmi_rep_clouds: the device point clouds equal the host ones
-  (compute_otmi.otmi_point_clouds, itself pinned to the reference-derived oracle in tests/test_host_logic_cpu.py) bit for bit.
+  (compute_otmi.otmi_point_clouds, itself pinned to the reference-derived oracle over the edge case lists in
+  tests/test_otmi_ref_cpu.py) bit for bit; the device clouds at those edges: tests/test_gpu_otmi_edges.py.
 * otmi_batch: the reference's golden otmi() cost within 1e-5.
 """
 import numpy as np
