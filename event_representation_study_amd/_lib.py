@@ -129,7 +129,12 @@ SYMBOLS = {
     "evrep_decode_dat": _st([_vp, _i64, _i32, _i64, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "evrep_decode_bin5": _st([_vp, _i64, _i64, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "evrep_dat_seek_time": _st([_vp, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "evrep_render_state": _st([_PP, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp]),
+    "evrep_render_compose": _st([_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp]),
 }
+# evrep_render_compose: RenderingType's values, the flag of cast=False
+RENDER_RED_BLUE_OVERLAP, RENDER_RED_BLUE_NO_OVERLAP, RENDER_BLACK_WHITE_NO_OVERLAP, RENDER_TIME_SURFACE, RENDER_EVENT_FRAME = 1, 2, 3, 4, 5
+RENDER_JITTER = 1
 # evrep_decode_dat / evrep_decode_bin5: modes, the overrun bit of the state's n_in, the fields of the state, the largest n
 DECODE_STRICT, DECODE_DROP_OOB = 0, 1
 DECODE_N_IN_OVERRUN = 1 << 62

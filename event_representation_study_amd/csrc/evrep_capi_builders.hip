@@ -1,8 +1,9 @@
 // evrep_capi_builders.hip -- the extern "C" surface, part 3: EventStack, TimeSurface, TORE, the voxel grids, the n_imagenet
-// accumulators, EST, the resize taps and the store probe.
+// accumulators, EST, the resize taps, the store probe and the renderings (evrep_render.hip).
 #define EVREP_TU_BUILDERS 1
 #include <cstdlib>
 #include "evrep_capi_builders.h"
+#include "evrep_render.hip"
 
 // LDS padding of a stream launch on SPARSE windows (kSparseMaxPerUnit).  EventStack's and TORE's streams are bound by
 // their HBM stores there, and two workgroups fewer per CU leave them FASTER -- the store-pacing effect of DESIGN.md 3.2, found again
@@ -381,6 +382,57 @@ int evrep_probe_store(void *out, size_t bytes, void *stream_) {
     if (tiles == 0 || tiles > 0x7fffffffu) return EVREP_EINVAL;
     k_store_probe<<<(unsigned)tiles, kWave, 8320, as_stream(stream_)>>>(static_cast<float *>(out), (int)tiles);
     LAUNCH_CHECK("k_store_probe");
+    return EVREP_OK;
+}
+
+int evrep_render_state(const evrep_plan *plan, const int32_t *events, const int64_t *offsets, void *workspace,
+                       uint8_t *state, int32_t *net, float *surface, double tau, void *stream_) {
+    int rc = check_common(plan, events, offsets, workspace);
+    if (rc) return rc;
+    if (bad_ptr(state, 4) || misaligned(net, 4) || misaligned(surface, 4)) return EVREP_EINVAL;
+    if (surface && !(tau > 0.0)) return EVREP_EINVAL;
+    if ((int64_t)plan->H * plan->W * 4 >= (int64_t)1 << 31) return EVREP_EINVAL;
+    hipStream_t stream = as_stream(stream_);
+    // one launch under every binning pass: after the key-sorted pass the unit's records come through stream_unit_records whatever the
+    // unit holds (no hot list), after the others they are the unit's segment of the pixel-sorted stream
+    const UnitCfg us = stream_cfg(plan, unit_cfg(plan, 4, 0, true, false));
+    constexpr int kRB = 4;
+    k_render_state<kRB><<<unit_grid(plan, us), kWave, render_state_lds_bytes(kChunkPx, kRB), stream>>>(
+        bin_view(plan, events, workspace, true), offsets, plan->H, plan->W, plan->nchunk, us, tau, WS(WindowMeta, off_meta), state, net, surface);
+    LAUNCH_CHECK("k_render_state");
+    return EVREP_OK;
+}
+
+int evrep_render_compose(const uint8_t *state, const int32_t *net, const float *surface, const double *lut,
+                         const uint8_t *canvas, int32_t canvas_is_batched, int32_t B, int32_t H, int32_t W, int32_t type,
+                         uint32_t flags, void *out, void *stream_) {
+    if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || (int64_t)H * W * 4 >= (int64_t)1 << 31) return EVREP_EINVAL;
+    if (type < EVREP_RENDER_RED_BLUE_OVERLAP || type > EVREP_RENDER_EVENT_FRAME || (flags & ~EVREP_RENDER_JITTER)) return EVREP_EINVAL;
+    const bool colour = type <= EVREP_RENDER_BLACK_WHITE_NO_OVERLAP, jitter = flags & EVREP_RENDER_JITTER;
+    if (jitter && !colour) return EVREP_EINVAL;
+    if (bad_ptr(state, 4) || bad_ptr(out, 16) || misaligned(net, 4) || misaligned(surface, 4) || misaligned(lut, 8)) return EVREP_EINVAL;
+    if (type == EVREP_RENDER_EVENT_FRAME && !net) return EVREP_EINVAL;
+    if (type == EVREP_RENDER_TIME_SURFACE && (!surface || !lut)) return EVREP_EINVAL;
+    if (canvas_is_batched != 0 && canvas_is_batched != 1) return EVREP_EINVAL;
+    const size_t npx = (size_t)H * W;
+    if (canvas && colour) {   // out never aliases canvas: a pixel without events is read from the one and written to the other
+        const uintptr_t c0 = reinterpret_cast<uintptr_t>(canvas), c1 = c0 + (canvas_is_batched ? (size_t)B : 1) * npx * 3;
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + (size_t)B * npx * 3;
+        if (c0 < o1 && o0 < c1) return EVREP_EINVAL;
+    }
+    hipStream_t stream = as_stream(stream_);
+    const dim3 grid((unsigned)(((npx + 3) / 4 + 1 + kRcThreads - 1) / kRcThreads), (unsigned)B);
+#define RENDER_LAUNCH(TYPE, JIT, LDS) \
+    k_render_compose<TYPE, JIT><<<grid, kRcThreads, LDS, stream>>>(state, net, surface, lut, canvas, canvas_is_batched, B, H, W, out)
+    switch (type) {
+    case EVREP_RENDER_RED_BLUE_OVERLAP: if (jitter) RENDER_LAUNCH(EVREP_RENDER_RED_BLUE_OVERLAP, true, 0); else RENDER_LAUNCH(EVREP_RENDER_RED_BLUE_OVERLAP, false, 0); break;
+    case EVREP_RENDER_RED_BLUE_NO_OVERLAP: if (jitter) RENDER_LAUNCH(EVREP_RENDER_RED_BLUE_NO_OVERLAP, true, 0); else RENDER_LAUNCH(EVREP_RENDER_RED_BLUE_NO_OVERLAP, false, 0); break;
+    case EVREP_RENDER_BLACK_WHITE_NO_OVERLAP: if (jitter) RENDER_LAUNCH(EVREP_RENDER_BLACK_WHITE_NO_OVERLAP, true, 0); else RENDER_LAUNCH(EVREP_RENDER_BLACK_WHITE_NO_OVERLAP, false, 0); break;
+    case EVREP_RENDER_TIME_SURFACE: RENDER_LAUNCH(EVREP_RENDER_TIME_SURFACE, false, 1024 * sizeof(double)); break;
+    default: RENDER_LAUNCH(EVREP_RENDER_EVENT_FRAME, false, 0); break;
+    }
+#undef RENDER_LAUNCH
+    LAUNCH_CHECK("k_render_compose");
     return EVREP_OK;
 }
 

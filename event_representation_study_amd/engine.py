@@ -444,6 +444,18 @@ class EventBatch:
                                                   int(self.plan.max_events_per_window), _ptr(m), _ptr(keep), self._sp())
         return keep, m
 
+    def render(self, rendering_type=1, cast=True, rendering=None, check=True, out=None):
+        """ev-licious' Events.render for every window -> (B, H, W, 3) uint8 frames, colours in the reference's channel order as
+        stored; RenderingType.TIME_SURFACE: (B, H, W, 4) float64 RGBA, a window of <= 2 events an all-zero slot (alpha included).
+        rendering_type: evlicious_render.RenderingType (default RED_BLUE_OVERLAP).  cast=False: the 2 x 2 jitter of the three
+        colour types (EVENT_FRAME and TIME_SURFACE ignore it, as the reference).  rendering: the canvas the colour types draw
+        onto, a device or host uint8 (H, W, 3) or (B, H, W, 3); None: white; anything else ``ValueError``.
+        check=True reads the status words once and raises ``ValueError`` naming the first window with rows outside the frame (the
+        Events constructor refuses them); check=False reads nothing back and returns (images, status), status a (B,) uint32
+        device tensor of _lib.ST_* bits: such a window is drawn from its in-frame events."""
+        from . import evlicious_render
+        return evlicious_render.render_batch(self, rendering_type, cast=cast, rendering=rendering, check=check, out=out)
+
     def pixel_counts(self):
         """Events per pixel -> (B, H, W) float32 (the COUNT accumulator of evrep_polstats; HotPixel.calibrate's np.add.at)."""
         tn = torch.zeros(self.total, dtype=torch.float64, device=self.device)

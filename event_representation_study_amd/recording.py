@@ -515,6 +515,14 @@ class DeviceRecording:
         for k in range(0, len(a), int(batch_size)):
             yield self.windows(a[k:k + batch_size], e[k:k + batch_size], rebase="first")
 
+    def render_iterator(self, step_size, window, step_size_unit, window_unit, rendering_type=2, batch_size=32, cast=True):
+        """The frames ``Visualizer.update(step, put_text=False)`` renders before its resize (io/utils/visualization.py:162-165),
+        in batches: ``EventBatch.render`` of every batch of ``iterator`` -> (b, H, W, 3) uint8 device tensors ((b, H, W, 4) float64
+        for TIME_SURFACE; ``evlicious_render.video_frames`` makes them ``convert_to_video``'s uint8 frames).  rendering_type:
+        evlicious_render.RenderingType, by default the Visualizer's own RED_BLUE_NO_OVERLAP."""
+        for batch in self.iterator(step_size, window, step_size_unit, window_unit, batch_size=batch_size):
+            yield batch.render(rendering_type, cast=cast)
+
 
 class DatDeviceRecording(DeviceRecording):
     """What ``DeviceRecording.from_dat`` returns: the recording of a DAT file with ``DatEventHandle``'s semantics

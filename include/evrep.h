@@ -857,6 +857,54 @@ int evrep_detector_input_frames(const evrep_detin_frame *frames, int32_t B, int3
                                 const int32_t *start, const int32_t *count, const double *weights, int64_t n_rows, int64_t n_wt,
                                 const double *pad, const int32_t *warp, float scale, void *frames_dev, float *out, void *stream);
 
+/* ev-licious' Events.render (ev-licious/src/evlicious/io/utils/render.py:9-141) for B windows of integer coordinates: two calls,
+ * one stream builder over the binned records and one streaming launch.  Neither allocates, waits for the device or reads a
+ * size on the host: both may be captured into a graph.  Limits: B <= 65535, H * W * 4 < 2^31.
+ *
+ * evrep_render_state: requires evrep_bin_events on the same plan and workspace, as every builder.  `state` is a caller-owned
+ *   tensor with this meaning (as `prim` is between evrep_polstats and evrep_dist), one byte per pixel:
+ *     bit 0  some event of the pixel has p > 0          bit 1  some event has p <= 0
+ *     bit 2  the pixel's LAST event in array order has p > 0 (the reversed first-visit loop of _render_no_overlap_numba)
+ *     bit 3  set on every pixel of a window of <= 2 rows: _render_timesurface returns zeros for such a window
+ *   net (or NULL): #positive - #negative events of the pixel (_render_event_frame's np.add.at of p in {-1, +1}).
+ *   surface (or NULL): the image of _render_timesurface before the colour map: per event in array order
+ *     img = fl32(double(img) + v),  v = exp(-(t[-1] - t) / tau) in float64 (a division, an exponential, nothing fused), t[-1]
+ *     the t of the window's last ROW; tau > 0 (3e4 in the reference), only read with surface.  One lane per pixel adds at a
+ *     time, elected in array order: no floating-point atomic.
+ *   Every element of every given tensor is written exactly once, 0 where no event fell.  Only array order matters: timestamps
+ *   need not ascend.  A window with out-of-frame rows (x + y * W outside [0, H * W), as for every builder) keeps EVREP_ST_OOB in
+ *   its status word and contributes its in-frame events.
+ *   After the call the window statistics of the workspace (what evrep_read_status copies) are merged on the device under every
+ *   binning pass.  state, net, surface DEVICE [B,H,W], 4-byte aligned.
+ * evrep_render_compose: state (+ net / surface + canvas) -> frames, `type` one of EVREP_RENDER_*  (RenderingType's values).
+ *     RED_BLUE_OVERLAP         a pixel with events: (255 if bit 1, 0, 255 if bit 0)
+ *     RED_BLUE_NO_OVERLAP      a pixel with events: (0, 0, 255) if bit 2 else (255, 0, 0)
+ *     BLACK_WHITE_NO_OVERLAP   a pixel with events: 255 x 3 if bit 2 else 0 x 3
+ *       a pixel without events: the canvas' pixel; canvas DEVICE uint8 [B,H,W,3] (canvas_is_batched 1) or [H,W,3] for every
+ *       window (0), or NULL = white.  out never aliases canvas.
+ *       flags EVREP_RENDER_JITTER (cast=False, _jitter_events: every event also at (x, y+1), (x+1, y), (x+1, y+1), clipped to the
+ *       frame, the four copies concatenated): a 2 x 2 stencil over the state; for output pixel (y, x) the sources are, latest
+ *       copy first, (y-1, x-1), (y, x-1), (y-1, x), (y, x): OVERLAP takes the union of their bits 0 and 1, the NO_OVERLAP types
+ *       bit 2 of the first source that has an event.
+ *     EVENT_FRAME              needs net: uint8(clip(20 * net + 128, 0, 255)) on three channels; canvas is ignored
+ *     TIME_SURFACE             needs surface and lut (DEVICE double [256][4], 8-byte aligned): out = lut[min(int(img * 256), 255)],
+ *       the product in float32 (matplotlib's Colormap.__call__ on a float image); a window of <= 2 rows (bit 3): zeros, alpha
+ *       included; canvas is ignored
+ *   out DEVICE, 16-byte aligned: uint8 [B,H,W,3], colours in the reference's channel order as stored; TIME_SURFACE: double
+ *   [B,H,W,4].  EVREP_RENDER_JITTER with EVENT_FRAME or TIME_SURFACE is EVREP_EINVAL (the reference ignores cast there: pass
+ *   0).  Every violation of the above is EVREP_EINVAL before any launch. */
+#define EVREP_RENDER_RED_BLUE_OVERLAP 1
+#define EVREP_RENDER_RED_BLUE_NO_OVERLAP 2
+#define EVREP_RENDER_BLACK_WHITE_NO_OVERLAP 3
+#define EVREP_RENDER_TIME_SURFACE 4
+#define EVREP_RENDER_EVENT_FRAME 5
+#define EVREP_RENDER_JITTER 1u
+int evrep_render_state(const evrep_plan *plan, const int32_t *events, const int64_t *offsets, void *workspace,
+                       uint8_t *state, int32_t *net, float *surface, double tau, void *stream);
+int evrep_render_compose(const uint8_t *state, const int32_t *net, const float *surface, const double *lut,
+                         const uint8_t *canvas, int32_t canvas_is_batched, int32_t B, int32_t H, int32_t W, int32_t type,
+                         uint32_t flags, void *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
