@@ -15,13 +15,17 @@ from . import _lib
 from ._lib import ptr, stream_ptr
 
 LOSSES = {"square_loss": 0, "kl_loss": 1}
+PRECISIONS = {"f64": _lib.F64, "f32": _lib.F32}
 
 
 def entropic_gromov_wasserstein(C1, C2, p=None, q=None, loss_fun="square_loss", epsilon=0.1, outer_iters=10,
                                 sinkhorn_iters=100, precision="f64", return_plan=True, device=None):
     """C1 (n, n), C2 (m, m) structure matrices (array-likes or CUDA tensors), p, q marginals (default uniform).
     Returns (T, gw): the (n, m) float64 plan (CUDA tensor, or None when return_plan is False) and the 0-dim
-    float64 loss, both left on the device (no host synchronisation)."""
+    float64 loss, both left on the device (no host synchronisation).  precision "f64" or "f32" (the GEMMs, the plan and the
+    Gibbs kernel; the Sinkhorn scalings and the outputs stay float64)."""
+    if precision not in PRECISIONS:                      # before anything is allocated or copied
+        raise ValueError("precision must be 'f64' or 'f32', not %r" % (precision,))
     if not torch.cuda.is_available():
         raise _lib.EvrepError("no HIP device visible: the solver runs on an MI355X only (no CPU fallback)")
     api = _lib.api()
@@ -38,7 +42,7 @@ def entropic_gromov_wasserstein(C1, C2, p=None, q=None, loss_fun="square_loss", 
         raise ValueError("p / q do not match C1 / C2")
     if loss_fun not in LOSSES:
         raise ValueError("loss_fun must be 'square_loss' or 'kl_loss'")
-    prec = {"f64": _lib.F64, "f32": _lib.F32}[precision]
+    prec = PRECISIONS[precision]
     scratch = _lib.scratch(api.evrep_gw_scratch_bytes(n, m, prec), dev)
     T = torch.empty((n, m), dtype=torch.float64, device=dev) if return_plan else None
     gw = torch.empty((), dtype=torch.float64, device=dev)

@@ -460,7 +460,13 @@ int evrep_resize_taps(const void *in, int32_t in_dtype, int32_t B, int32_t H, in
  * C1 DEVICE double [n,n], C2 DEVICE double [m,m], p DEVICE double [n], q DEVICE double [m];
  * loss 0 = "square_loss", 1 = "kl_loss"; precision EVREP_F64 (v_mfma_f64_16x16x4_f64) or EVREP_F32
  * (v_mfma_f32_16x16x4_f32; plan and Gibbs kernel in float32, Sinkhorn scalings in float64);
- * scratch DEVICE of evrep_gw_scratch_bytes(n, m, precision); T_out DEVICE double [n,m] or NULL; gw_out DEVICE double [1]. */
+ * scratch DEVICE of evrep_gw_scratch_bytes(n, m, precision); T_out DEVICE double [n,m] or NULL; gw_out DEVICE double [1].
+ * C1 and C2 need not be symmetric: C1[i][k] and C2[j][l] are read row-major as given, and T_out[i][j] couples point i of the
+ * first space with point j of the second.  A point of zero mass (p[i] == 0 or q[j] == 0) gives a row or column of T_out that
+ * is exactly 0 and does not influence gw or the rest of the plan: both equal those of the problem without the point.  With
+ * zeros in BOTH marginals POT's published recurrence yields NaN (it forms (1 / p) * K, a row of inf, and multiplies it by the
+ * zero scaling of a zero-mass column); this solver computes u = p / (K v) and stays finite, with the same zero rows and columns.
+ * outer_iters == 0 is accepted: T_out is then p q^T and gw the loss of that product plan. */
 size_t evrep_gw_scratch_bytes(int64_t n, int64_t m, int32_t precision);
 int evrep_entropic_gw(const double *C1, int64_t n, const double *C2, int64_t m, const double *p, const double *q,
                       int32_t loss, double epsilon, int32_t outer_iters, int32_t sinkhorn_iters, int32_t precision,
