@@ -122,6 +122,7 @@ SYMBOLS = {
     "evrep_resize_tap_tables": _st([_vp, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp]),
     "evrep_detector_input_frames_scratch_bytes": (ctypes.c_size_t, [_i32]),
     "evrep_detector_input_frames": _st([_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _f32, _vp, _vp, _vp]),
+    "evrep_nms": _st([_vp, _i32, _i32, _i32, _f32, _f64, ctypes.c_uint32, _I32P, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "evrep_voxel_normalize_scratch_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32]),
     "evrep_voxel_normalize": _st([_vp, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
     "evrep_decode_scratch_bytes": (ctypes.c_size_t, [_i64]),
@@ -157,6 +158,9 @@ EST_PREP_DESCENDING, EST_PREP_BAD_INDEX, EST_PREP_BAD_POLARITY, EST_PREP_OUT_OF_
 EST_PREP_MAX_B = 65535
 # evrep_detector_input: per-sample flags
 DETIN_WARP, DETIN_FLIPUD, DETIN_FLIPLR = 1, 2, 4
+# evrep_nms: flags, limits
+NMS_MULTI_LABEL, NMS_AGNOSTIC = 1, 2
+NMS_MAX_DET, NMS_MAX_CLASSES, NMS_MAX_ROWS = 1024, 4096, 1 << 24
 # evrep_resize_tap_tables: interpolation codes; the columns of an axis descriptor
 TAPS_LINEAR, TAPS_AREA, TAPS_IDENTITY = 0, 1, 2
 TAPS_AXIS_FIELDS = 6

@@ -1,10 +1,12 @@
-// evrep_capi_detin.hip -- the extern "C" surface, part 10: the detector's input batch (evrep_detin.hip) and its form for frames
-// of different sizes with the tap tables made on the device (evrep_detin_frames.hip): argument checks and one launch per entry
-// point.  No plan, no workspace, no allocation, no wait for the device.
+// evrep_capi_detin.hip -- the extern "C" surface, part 10: the detector's input batch (evrep_detin.hip), its form for frames
+// of different sizes with the tap tables made on the device (evrep_detin_frames.hip), and the detector's output, the batched
+// non_max_suppression (evrep_nms.hip): argument checks and one launch per entry point.  No plan, no workspace, no allocation,
+// no wait for the device.
 #include <limits.h>
 
 #include "evrep_capi_shared.h"
 #include "evrep_detin_frames.hip"
+#include "evrep_nms.hip"
 
 using namespace evrep;
 using evrep_host::hip_check;
@@ -126,6 +128,40 @@ int evrep_detector_input_frames(const evrep_detin_frame *frames, int32_t B, int3
         k_detector_input_frames<float><<<grid, kThreads, 0, stream>>>(a);
     }
     LAUNCH_CHECK("k_detector_input_frames");
+    return EVREP_OK;
+}
+
+// the rows an image can have, every box a candidate under every class
+static inline int64_t nms_rows(int32_t N, int32_t C, uint32_t flags) {
+    return ((flags & EVREP_NMS_MULTI_LABEL) && C > 1) ? (int64_t)N * C : (int64_t)N;
+}
+
+int evrep_nms(const float *pred, int32_t B, int32_t N, int32_t C, float conf_thres, double iou_thres, uint32_t flags,
+              const int32_t *classes_host, int32_t n_classes, int32_t max_nms, int32_t max_det, float *det, int32_t *count,
+              void *scratch, void *stream_) {
+    if (B < 1 || B > 65535 || N < 1 || C < 1 || C > EVREP_NMS_MAX_CLASSES || (int64_t)N * C > EVREP_NMS_MAX_ROWS) return EVREP_EINVAL;
+    if (max_det < 1 || max_det > EVREP_NMS_MAX_DET || max_nms < 1) return EVREP_EINVAL;
+    if (!(conf_thres >= 0.0f && conf_thres <= 1.0f) || !(iou_thres >= 0.0 && iou_thres <= 1.0)) return EVREP_EINVAL;   // (NaN fails)
+    if (flags & ~(uint32_t)(EVREP_NMS_MULTI_LABEL | EVREP_NMS_AGNOSTIC)) return EVREP_EINVAL;
+    if (n_classes < -1 || n_classes > EVREP_NMS_MAX_ROWS || (n_classes > 0 && bad_ptr(classes_host, 4))) return EVREP_EINVAL;
+    if (bad_ptr(pred, 4) || bad_ptr(det, 4) || bad_ptr(count, 4) || bad_ptr(scratch, 16)) return EVREP_EINVAL;
+    const int64_t R = nms_rows(N, C, flags);
+    if (5 * (((int64_t)B * R + 3) / 4) > EVREP_RANK_MAX_TOTAL) return EVREP_EINVAL;
+    NmsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pred = pred; a.det = det; a.count = count; a.scratch = static_cast<uint32_t *>(scratch);
+    a.iou_thres = iou_thres; a.R = R; a.ct = conf_thres;
+    a.B = B; a.N = N; a.C = C;
+    a.multi = ((flags & EVREP_NMS_MULTI_LABEL) && C > 1) ? 1 : 0;
+    a.agnostic = (flags & EVREP_NMS_AGNOSTIC) ? 1 : 0;
+    a.use_classes = n_classes >= 0 ? 1 : 0;
+    a.max_nms = max_nms; a.max_det = max_det;
+    for (int32_t k = 0; k < n_classes; ++k) {
+        const int32_t c = classes_host[k];
+        if (c >= 0 && c < C) a.class_mask[c >> 5] |= 1u << (c & 31);
+    }
+    k_nms<<<(unsigned)B, kDistThreads, 0, as_stream(stream_)>>>(a);
+    LAUNCH_CHECK("k_nms");
     return EVREP_OK;
 }
 

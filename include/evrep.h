@@ -863,6 +863,45 @@ int evrep_detector_input_frames(const evrep_detin_frame *frames, int32_t B, int3
                                 const int32_t *start, const int32_t *count, const double *weights, int64_t n_rows, int64_t n_wt,
                                 const double *pad, const int32_t *warp, float scale, void *frames_dev, float *out, void *stream);
 
+/* The detector's output in ONE launch: ev-YOLOv6's non_max_suppression (yolov6/utils/nms.py:59-129) with the CPU kernel of
+ * torchvision.ops.nms behind it, for the B images of a batch, one workgroup per image.  pred[b] is (N, 5 + C) float32, a row
+ * [cx, cy, w, h, obj, cls_0 .. cls_{C-1}]; every statement below is one float32 operation, none fused with another:
+ *   candidates  ct = conf_thres (a float: torch compares a float32 tensor with a Python scalar in float32).  A box is a
+ *               candidate iff obj > ct and max_c cls_c > ct; a NaN obj or a NaN among the classes fails.
+ *   rows        conf_c = cls_c * obj; corners x1 = cx - w / 2, x2 = cx + w / 2, y likewise.  EVREP_NMS_MULTI_LABEL and C > 1: one
+ *               row per (box i, class c) with conf_c > ct; otherwise one row per candidate with c the FIRST maximum of conf_c,
+ *               kept iff conf_c > ct.  A row's number is i * C + c.  n_classes >= 0: a row survives iff its class is among
+ *               classes_host[0 .. n_classes) (HOST int32; values outside [0, C) match nothing; n_classes = 0 drops every row);
+ *               n_classes = -1: no filter, classes_host is not read.
+ *   order       conf descending, equal conf by row number ascending (torchvision's stable sort).  More than max_nms rows: the
+ *               first max_nms of that order (the reference's unstable argsort leaves ties at the cut open: here the lower
+ *               row number goes first).
+ *   greedy      o = cls * 4096, or cls * 0 with EVREP_NMS_AGNOSTIC; every corner is c' = c + o (this addition rounds: at 8192
+ *               an ulp is 2^-10); area = (x2' - x1') * (y2' - y1').  A row is kept iff no EARLIER KEPT row i suppresses it:
+ *               w = max(0, min(x2'_i, x2'_j) - max(x1'_i, x1'_j)), h likewise, inter = w * h,
+ *               ovr = inter / ((area_i + area_j) - inter), suppressed iff (double)ovr > iou_thres.  NaN suppresses nothing.
+ *   output      det[b]: the first max_det kept rows as the UN-offset [x1, y1, x2, y2, conf, (float)c], zeros behind them;
+ *               count[b]: how many.  Every byte of det and count is written on every call.
+ * Not mirrored: the reference's 10 s time limit, half-precision input.
+ * pred DEVICE float [B,N,5+C]; det DEVICE float [B,max_det,6]; count DEVICE int32 [B]; all 4-byte aligned.
+ * scratch DEVICE, 16-byte aligned: five arrays of B * R uint32 (the four of the pair sort and the row numbers), R the rows an
+ *   image can have at the worst, every row of every image a candidate: R = N * C with EVREP_NMS_MULTI_LABEL and C > 1, R = N
+ *   otherwise.  Its size is evrep_dense_rank_scratch_bytes(B, 5 * ceil(B * R / 4)) -- four arrays of that total are the five
+ *   of B * R.  Needs no initialisation.
+ * 1 <= B <= 65535, N >= 1, 1 <= C <= EVREP_NMS_MAX_CLASSES, N * C <= EVREP_NMS_MAX_ROWS, 1 <= max_det <= EVREP_NMS_MAX_DET,
+ * max_nms >= 1, conf_thres and iou_thres in [0, 1], -1 <= n_classes <= EVREP_NMS_MAX_ROWS, the total above at most
+ * EVREP_RANK_MAX_TOTAL; anything else, an unknown flag, a
+ * NULL or misaligned pointer is EVREP_EINVAL before any launch.  Does not allocate, does not wait for the device, reads nothing
+ * back: the call may be captured into a graph. */
+#define EVREP_NMS_MULTI_LABEL 1u
+#define EVREP_NMS_AGNOSTIC 2u
+#define EVREP_NMS_MAX_DET 1024
+#define EVREP_NMS_MAX_CLASSES 4096
+#define EVREP_NMS_MAX_ROWS (1 << 24)
+int evrep_nms(const float *pred, int32_t B, int32_t N, int32_t C, float conf_thres, double iou_thres, uint32_t flags,
+              const int32_t *classes_host, int32_t n_classes, int32_t max_nms, int32_t max_det, float *det, int32_t *count,
+              void *scratch, void *stream);
+
 /* ev-licious' Events.render (ev-licious/src/evlicious/io/utils/render.py:9-141) for B windows of integer coordinates: two calls,
  * one stream builder over the binned records and one streaming launch.  Neither allocates, waits for the device or reads a
  * size on the host: both may be captured into a graph.  Limits: B <= 65535, H * W * 4 < 2^31.
