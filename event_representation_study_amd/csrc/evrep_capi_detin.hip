@@ -1,12 +1,13 @@
 // evrep_capi_detin.hip -- the extern "C" surface, part 10: the detector's input batch (evrep_detin.hip), its form for frames
 // of different sizes with the tap tables made on the device (evrep_detin_frames.hip), and the detector's output, the batched
-// non_max_suppression (evrep_nms.hip): argument checks and one launch per entry point.  No plan, no workspace, no allocation,
-// no wait for the device.
+// non_max_suppression (evrep_nms.hip), and the scoring of its detections against the labels (evrep_deteval.hip): argument checks
+// and one launch per entry point.  No plan, no workspace, no allocation, no wait for the device.
 #include <limits.h>
 
 #include "evrep_capi_shared.h"
 #include "evrep_detin_frames.hip"
 #include "evrep_nms.hip"
+#include "evrep_deteval.hip"
 
 using namespace evrep;
 using evrep_host::hip_check;
@@ -162,6 +163,40 @@ int evrep_nms(const float *pred, int32_t B, int32_t N, int32_t C, float conf_thr
     }
     k_nms<<<(unsigned)B, kDistThreads, 0, as_stream(stream_)>>>(a);
     LAUNCH_CHECK("k_nms");
+    return EVREP_OK;
+}
+
+int evrep_det_match(const float *det, const int32_t *count, int32_t B, int32_t max_det, const float *targets, int64_t n_t,
+                    const float *geom, int32_t img_h, int32_t img_w, const float *iouv_host, int32_t T, uint32_t flags,
+                    int64_t *matrix, int32_t nc, float conf, float iou_thres, uint8_t *correct, float *detn, float *tbox,
+                    int32_t *n_labels, uint32_t *status, void *stream_) {
+    if (B < 1 || B > 65535 || max_det < 1 || max_det > EVREP_NMS_MAX_DET) return EVREP_EINVAL;
+    if (n_t < 0 || n_t > EVREP_DETEVAL_MAX_TARGETS || T < 1 || T > EVREP_DETEVAL_MAX_T) return EVREP_EINVAL;
+    if (flags & ~(uint32_t)(EVREP_DETEVAL_NATIVE | EVREP_DETEVAL_SKIP_EMPTY)) return EVREP_EINVAL;
+    if (bad_ptr(det, 4) || bad_ptr(count, 4) || bad_ptr(iouv_host, 4) || bad_ptr(correct, 1) || bad_ptr(n_labels, 4) || bad_ptr(status, 4))
+        return EVREP_EINVAL;
+    if (n_t > 0 ? bad_ptr(targets, 4) : misaligned(targets, 4)) return EVREP_EINVAL;
+    if (misaligned(detn, 4) || misaligned(tbox, 4) || misaligned(matrix, 8)) return EVREP_EINVAL;
+    const bool native = (flags & EVREP_DETEVAL_NATIVE) != 0u;
+    if (native ? misaligned(geom, 4) : bad_ptr(geom, 4)) return EVREP_EINVAL;
+    if (!native && (img_h < 1 || img_w < 1 || img_h > EVREP_MAX_DIM || img_w > EVREP_MAX_DIM)) return EVREP_EINVAL;
+    if (matrix && (nc < 1 || nc > EVREP_NMS_MAX_CLASSES || !(conf == conf) || !(iou_thres == iou_thres))) return EVREP_EINVAL;
+    DetevalArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int32_t i = 0; i < T; ++i) {
+        if (!(iouv_host[i] == iouv_host[i])) return EVREP_EINVAL;   // NaN
+        a.iouv[i] = iouv_host[i];
+    }
+    a.det = det; a.count = count; a.targets = targets; a.geom = geom;
+    a.matrix = reinterpret_cast<unsigned long long *>(matrix);
+    a.correct = correct; a.detn = detn; a.tbox = tbox; a.n_labels = n_labels; a.status = status;
+    a.n_t = n_t;
+    a.img_h = (float)img_h; a.img_w = (float)img_w; a.conf = conf; a.iou_thres = iou_thres;
+    a.B = B; a.max_det = max_det; a.T = T; a.nc = matrix ? nc : 0;
+    a.native = native ? 1 : 0;
+    a.skip_empty = (flags & EVREP_DETEVAL_SKIP_EMPTY) ? 1 : 0;
+    k_det_match<<<(unsigned)B, kDistThreads, 0, as_stream(stream_)>>>(a);
+    LAUNCH_CHECK("k_det_match");
     return EVREP_OK;
 }
 

@@ -902,6 +902,65 @@ int evrep_nms(const float *pred, int32_t B, int32_t N, int32_t C, float conf_thr
               const int32_t *classes_host, int32_t n_classes, int32_t max_nms, int32_t max_det, float *det, int32_t *count,
               void *scratch, void *stream);
 
+/* Scoring the detections in ONE launch: the statistics step of ev-YOLOv6's validation loop (yolov6/core/evaler.py:206-258) with
+ * yolov6/utils/metrics.py's process_batch and ConfusionMatrix.process_batch behind it, for the B images of a batch, one
+ * workgroup per image.  Per image b the detections are rows j = 0 .. count[b]-1 of det[b], [x1, y1, x2, y2, conf, cls] in NMS
+ * order (what evrep_nms wrote); the labels are the rows of `targets` whose column 0 equals b (float equality), in array order
+ * k = 0 .. M-1, [image, cls, cx, cy, w, h].  Every statement below is one float32 operation, none fused with another (the library
+ * is built with -ffp-contract=off and the kernel file repeats it as a pragma):
+ *   geometry    (normalised mode, evaler.py:228-249)  detections: scale_coords with ratio_pad given and scale_exact false, with
+ *               geom[b] = [pad_x, pad_y, gain, w0, h0] the float32 pad, gain[0] and source frame: x = (x - pad_x) / gain clamped
+ *               to [0, w0], y = (y - pad_y) / gain clamped to [0, h0] (clamp: v < 0 ? 0 : v > hi ? hi : v, a NaN stays).
+ *               labels, in this order: xywh2xyxy (x1 = cx - w / 2, x2 = cx + w / 2, y likewise), x *= img_w, y *= img_h of the
+ *               letterboxed image, then the same scale_coords.
+ *   native      EVREP_DETEVAL_NATIVE: labels are [image, cls, x1, y1, x2, y2] and both sides are taken as they are (what
+ *               process_batch(detections, labels, iouv) receives); geom, img_h and img_w are not read.
+ *   iou         general.box_iou(labels, detections): area = (x2 - x1) * (y2 - y1) for each side,
+ *               w = clamp(min(x2l, x2d) - max(x1l, x1d), 0), h likewise, inter = w * h, iou = inter / ((area_l + area_d) - inter).
+ *               0 / 0 is NaN, and a NaN matches nothing.
+ *   correct     (process_batch) for detection j let k*(j) be the label with cls_k == cls_j (float equality) of greatest
+ *               iou(k, j) and iou*(j) that value.  correct[j, i] iff iou*(j) >= iouv[i] (float32, not strict) and no j' < j has
+ *               k*(j') == k*(j) and iou*(j') >= iouv[i].  This equals the reference's sort / unique / unique for every threshold.
+ *               TIE: among labels of equal greatest IoU the LOWEST label index wins.  The reference's argsort()[::-1] is numpy's
+ *               unstable sort and leaves this open: its outcome depends on numpy's build and the CPU (as the ties at evrep_nms's
+ *               max_nms cut are).
+ *   confusion   (ConfusionMatrix.process_batch; only with matrix != NULL)  only detections with conf > `conf` take part.  For
+ *               detection j the best label over ALL classes with iou > iou_thres (strict); for label k the detection of greatest
+ *               IoU among those whose best label is k.  Ties: lowest label index, then lowest detection index (open in the
+ *               reference for the same reason).  A matched label adds 1 at [int(cls_det), int(cls_label)]; an unmatched label
+ *               adds 1 at [nc, int(cls_label)]; detections that won no label add 1 at [int(cls_det), nc], but only if the image
+ *               has at least one match.  matrix is DEVICE int64 [(nc+1) * (nc+1)], row-major, accumulated with integer atomics
+ *               across images and calls; the caller zeroes it once.  A class outside [0, nc) sets EVREP_DETEVAL_ST_BAD_CLASS and
+ *               that update is skipped (the reference raises or wraps).  EVREP_DETEVAL_SKIP_EMPTY is the evaler's guard
+ *               (evaler.py:215-225): an image with count[b] == 0 contributes nothing to the matrix.
+ *   limits      an image with more than EVREP_DETEVAL_MAX_LABELS labels sets EVREP_DETEVAL_ST_LABEL_OVERFLOW, gets all-false
+ *               rows and adds nothing to the matrix (the cap lets the label boxes and the (label, threshold) table of one image
+ *               live in LDS); a count[b] outside [0, max_det] is clamped and sets EVREP_DETEVAL_ST_BAD_COUNT.
+ *   outputs     correct DEVICE uint8 [B,max_det,T], rows at or beyond count[b] are 0, every byte written on every call;
+ *               detn (or NULL) DEVICE float [B,max_det,6]: the native-space detections, zeros beyond count[b], every byte
+ *               written; tbox (or NULL) DEVICE float [n_t,4]: the native-space box of every target row, zeros for a row whose
+ *               column 0 is no integer in [0, B), every byte written; n_labels DEVICE int32 [B]: the labels of each image (the
+ *               true number, also above the cap); status DEVICE uint32 [B]: the bits above, 0 when all is well.
+ * det DEVICE float [B,max_det,6]; count DEVICE int32 [B]; targets DEVICE float [n_t,6] (NULL allowed when n_t == 0); geom DEVICE
+ * float [B,5] (NULL allowed in native mode); iouv_host HOST float [T], read during the call; pointers 4-byte aligned, matrix
+ * 8-byte aligned.  1 <= B <= 65535, 1 <= max_det <= EVREP_NMS_MAX_DET, 0 <= n_t <= EVREP_DETEVAL_MAX_TARGETS,
+ * 1 <= T <= EVREP_DETEVAL_MAX_T and no threshold NaN, img_h and img_w in 1..EVREP_MAX_DIM in normalised mode, with a matrix
+ * 1 <= nc <= EVREP_NMS_MAX_CLASSES and conf, iou_thres not NaN; anything else, an unknown flag, a NULL or misaligned pointer is
+ * EVREP_EINVAL before any launch.  Needs no scratch.  Does not allocate, does not wait for the device, reads nothing back: the
+ * call may be captured into a graph. */
+#define EVREP_DETEVAL_NATIVE 1u
+#define EVREP_DETEVAL_SKIP_EMPTY 2u
+#define EVREP_DETEVAL_MAX_LABELS 1024
+#define EVREP_DETEVAL_MAX_T 16
+#define EVREP_DETEVAL_MAX_TARGETS (1 << 24)
+#define EVREP_DETEVAL_ST_LABEL_OVERFLOW 1u
+#define EVREP_DETEVAL_ST_BAD_CLASS 2u
+#define EVREP_DETEVAL_ST_BAD_COUNT 4u
+int evrep_det_match(const float *det, const int32_t *count, int32_t B, int32_t max_det, const float *targets, int64_t n_t,
+                    const float *geom, int32_t img_h, int32_t img_w, const float *iouv_host, int32_t T, uint32_t flags,
+                    int64_t *matrix, int32_t nc, float conf, float iou_thres, uint8_t *correct, float *detn, float *tbox,
+                    int32_t *n_labels, uint32_t *status, void *stream);
+
 /* ev-licious' Events.render (ev-licious/src/evlicious/io/utils/render.py:9-141) for B windows of integer coordinates: two calls,
  * one stream builder over the binned records and one streaming launch.  Neither allocates, waits for the device or reads a
  * size on the host: both may be captured into a graph.  Limits: B <= 65535, H * W * 4 < 2^31.
