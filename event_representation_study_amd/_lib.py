@@ -125,6 +125,10 @@ SYMBOLS = {
     "evrep_nms": _st([_vp, _i32, _i32, _i32, _f32, _f64, ctypes.c_uint32, _I32P, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "evrep_det_match": _st([_vp, _vp, _i32, _i32, _vp, _i64, _vp, _i32, _i32, ctypes.POINTER(ctypes.c_float), _i32, ctypes.c_uint32, _vp, _i32,
                             _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "evrep_det_targets_pad": _st([_vp, _i64, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
+    "evrep_tal_workspace_bytes": (ctypes.c_size_t, [_i32, _i32, _i32]),
+    "evrep_tal_assign": _st([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _vp]),
     "evrep_voxel_normalize_scratch_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32]),
     "evrep_voxel_normalize": _st([_vp, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
     "evrep_decode_scratch_bytes": (ctypes.c_size_t, [_i64]),
@@ -167,6 +171,10 @@ NMS_MAX_DET, NMS_MAX_CLASSES, NMS_MAX_ROWS = 1024, 4096, 1 << 24
 DETEVAL_NATIVE, DETEVAL_SKIP_EMPTY = 1, 2
 DETEVAL_MAX_LABELS, DETEVAL_MAX_T, DETEVAL_MAX_TARGETS = 1024, 16, 1 << 24
 DETEVAL_ST_LABEL_OVERFLOW, DETEVAL_ST_BAD_CLASS, DETEVAL_ST_BAD_COUNT = 1, 2, 4
+# evrep_det_targets_pad / evrep_tal_assign: flag, limits, per-image status bits
+TAL_F32_OUT = 1
+TAL_MAX_TOPK, TAL_MAX_LABELS, TAL_MAX_CLASSES, TAL_MAX_ANCHORS, TAL_MAX_POWER = 64, 1024, 4096, 1 << 24, 16
+TAL_ST_LABEL_OVERFLOW, TAL_ST_BAD_CLASS, TAL_ST_NONFINITE = 1, 2, 4
 # evrep_resize_tap_tables: interpolation codes; the columns of an axis descriptor
 TAPS_LINEAR, TAPS_AREA, TAPS_IDENTITY = 0, 1, 2
 TAPS_AXIS_FIELDS = 6

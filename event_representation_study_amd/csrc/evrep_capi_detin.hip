@@ -1,13 +1,15 @@
 // evrep_capi_detin.hip -- the extern "C" surface, part 10: the detector's input batch (evrep_detin.hip), its form for frames
 // of different sizes with the tap tables made on the device (evrep_detin_frames.hip), and the detector's output, the batched
-// non_max_suppression (evrep_nms.hip), and the scoring of its detections against the labels (evrep_deteval.hip): argument checks
-// and one launch per entry point.  No plan, no workspace, no allocation, no wait for the device.
+// non_max_suppression (evrep_nms.hip), the scoring of its detections against the labels (evrep_deteval.hip), and the training
+// targets, label padding and the task-aligned assigner (evrep_assign.hip): argument checks and the launches of each entry
+// point.  No plan, no workspace, no allocation, no wait for the device.
 #include <limits.h>
 
 #include "evrep_capi_shared.h"
 #include "evrep_detin_frames.hip"
 #include "evrep_nms.hip"
 #include "evrep_deteval.hip"
+#include "evrep_assign.hip"
 
 using namespace evrep;
 using evrep_host::hip_check;
@@ -197,6 +199,85 @@ int evrep_det_match(const float *det, const int32_t *count, int32_t B, int32_t m
     a.skip_empty = (flags & EVREP_DETEVAL_SKIP_EMPTY) ? 1 : 0;
     k_det_match<<<(unsigned)B, kDistThreads, 0, as_stream(stream_)>>>(a);
     LAUNCH_CHECK("k_det_match");
+    return EVREP_OK;
+}
+
+int evrep_det_targets_pad(const float *targets, int64_t n_t, int32_t B, int32_t M, float width, float height, double *gt,
+                          int32_t *n_labels, uint32_t *status, void *stream_) {
+    if (B < 1 || B > 65535 || M < 0 || M > EVREP_TAL_MAX_LABELS || n_t < 0 || n_t > EVREP_DETEVAL_MAX_TARGETS) return EVREP_EINVAL;
+    if (!(width - width == 0.0f) || !(height - height == 0.0f)) return EVREP_EINVAL;   // NaN, inf
+    if (n_t > 0 ? bad_ptr(targets, 4) : misaligned(targets, 4)) return EVREP_EINVAL;
+    if (M > 0 ? bad_ptr(gt, 8) : misaligned(gt, 8)) return EVREP_EINVAL;
+    if (bad_ptr(n_labels, 4) || bad_ptr(status, 4)) return EVREP_EINVAL;
+    TalPadArgs a;
+    a.targets = targets; a.gt = gt; a.n_labels = n_labels; a.status = status;
+    a.n_t = n_t; a.W = (double)width; a.H = (double)height; a.B = B; a.M = M;
+    k_det_targets_pad<<<(unsigned)B, kDistThreads, 0, as_stream(stream_)>>>(a);
+    LAUNCH_CHECK("k_det_targets_pad");
+    return EVREP_OK;
+}
+
+static inline bool tal_shape_ok(int32_t B, int32_t M, int32_t A) {
+    return B >= 1 && B <= 65535 && M >= 0 && M <= EVREP_TAL_MAX_LABELS && A >= 1 && A <= EVREP_TAL_MAX_ANCHORS;
+}
+
+// the scratch of evrep_tal_assign: per (image, anchor) cnt, first, row and the metric; per (image, row) the two maxima
+static size_t tal_layout(void *scratch, int32_t B, int32_t M, int32_t A, TalArgs *t) {
+    Carver c(scratch);
+    const size_t ba = (size_t)B * (size_t)A, bm = (size_t)B * (size_t)M;
+    uint32_t *cnt = c.take<uint32_t>(ba * 4);
+    uint32_t *first = c.take<uint32_t>(ba * 4);
+    int32_t *row = c.take<int32_t>(ba * 4);
+    double *alv = c.take<double>(ba * 8);
+    unsigned long long *pos_al = c.take<unsigned long long>(bm * 8);
+    unsigned long long *pos_ov = c.take<unsigned long long>(bm * 8);
+    if (t) {
+        t->cnt = cnt; t->first = first; t->row = row; t->alv = alv; t->pos_al = pos_al; t->pos_ov = pos_ov;
+    }
+    return c.off;
+}
+
+size_t evrep_tal_workspace_bytes(int32_t B, int32_t M, int32_t A) {
+    return tal_shape_ok(B, M, A) ? tal_layout(nullptr, B, M, A, nullptr) : 0;
+}
+
+int evrep_tal_assign(const float *pd_scores, const float *pd_bboxes, const float *anc_points, const double *gt, int32_t B,
+                     int32_t M, int32_t A, int32_t nc, int32_t topk, int32_t alpha, int32_t beta, uint32_t flags,
+                     int64_t *target_labels, void *target_bboxes, void *target_scores, uint8_t *fg, uint32_t *status,
+                     void *scratch, void *stream_) {
+    if (!tal_shape_ok(B, M, A) || nc < 1 || nc > EVREP_TAL_MAX_CLASSES || (int64_t)A * nc > INT32_MAX) return EVREP_EINVAL;
+    if (topk < 1 || topk > EVREP_TAL_MAX_TOPK || alpha < 0 || alpha > EVREP_TAL_MAX_POWER || beta < 0 || beta > EVREP_TAL_MAX_POWER)
+        return EVREP_EINVAL;
+    if (flags & ~(uint32_t)EVREP_TAL_F32_OUT) return EVREP_EINVAL;
+    const uintptr_t elem = (flags & EVREP_TAL_F32_OUT) ? 4 : 8;
+    if (bad_ptr(pd_scores, 4) || bad_ptr(pd_bboxes, 4) || bad_ptr(anc_points, 4)) return EVREP_EINVAL;
+    if (M > 0 ? bad_ptr(gt, 8) : misaligned(gt, 8)) return EVREP_EINVAL;
+    if (bad_ptr(target_labels, 8) || bad_ptr(target_bboxes, elem) || bad_ptr(target_scores, elem) || bad_ptr(fg, 1)) return EVREP_EINVAL;
+    if (bad_ptr(status, 4) || bad_ptr(scratch, 256)) return EVREP_EINVAL;
+    TalArgs t;
+    memset(&t, 0, sizeof(t));
+    t.pd_scores = pd_scores; t.pd_bboxes = pd_bboxes; t.anc = anc_points; t.gt = gt;
+    t.labels = target_labels; t.boxes = target_bboxes; t.scores = target_scores; t.fg = fg; t.status = status;
+    t.B = B; t.M = M; t.A = A; t.nc = nc; t.topk = topk; t.alpha = alpha; t.beta = beta;
+    t.f32_out = (flags & EVREP_TAL_F32_OUT) ? 1 : 0;
+    tal_layout(scratch, B, M, A, &t);
+    hipStream_t stream = as_stream(stream_);
+    int rc = hip_check(hipMemsetAsync(status, 0, (size_t)B * 4u, stream), "hipMemsetAsync(status)");
+    if (rc != EVREP_OK) return rc;
+    const auto spread = [&](size_t work) {                              // workgroups per image: B * G about 2048
+        const size_t need = (work + kThreads - 1) / kThreads, cap = (2048 + (size_t)B - 1) / (size_t)B;
+        return (unsigned)(need < 1 ? 1 : (need < cap ? need : cap));
+    };
+    if (M > 0) {
+        k_tal_prepare<<<dim3(spread((size_t)A * nc), (unsigned)B), kThreads, 0, stream>>>(t);
+        LAUNCH_CHECK("k_tal_prepare");
+        k_tal_select<<<dim3((unsigned)M, (unsigned)B), kTalSelectThreads, 0, stream>>>(t);
+        LAUNCH_CHECK("k_tal_select");
+    }
+    k_tal_resolve<<<dim3((unsigned)((A + kThreads - 1) / kThreads), (unsigned)B), kThreads, 0, stream>>>(t);
+    LAUNCH_CHECK("k_tal_resolve");
+    k_tal_scores<<<dim3(spread((size_t)A * nc), (unsigned)B), kThreads, 0, stream>>>(t);
+    LAUNCH_CHECK("k_tal_scores");
     return EVREP_OK;
 }
 

@@ -961,6 +961,79 @@ int evrep_det_match(const float *det, const int32_t *count, int32_t B, int32_t m
                     int64_t *matrix, int32_t nc, float conf, float iou_thres, uint8_t *correct, float *detn, float *tbox,
                     int32_t *n_labels, uint32_t *status, void *stream);
 
+/* The training targets: what ev-YOLOv6's ComputeLoss.__call__ does between the head's output and the loss terms
+ * (yolov6/models/losses/loss.py:73-111) for the B images of a batch, with no (B, M, A) array in memory.
+ *
+ * evrep_det_targets_pad is ComputeLoss.preprocess (loss.py:219-236).  The labels of image b are the rows of `targets` whose
+ *   column 0 equals b (float equality), in array order, [image, cls, cx, cy, w, h] float32.  Every value is widened exactly to
+ *   float64, as are width and height; then, one float64 operation per statement, bx = cx * width, by = cy * height,
+ *   bw = w * width, bh = h * height, x1 = bx - bw * 0.5, y1 = by - bh * 0.5, x2 = x1 + bw, y2 = y1 + bh (the updated x1, y1: the
+ *   in-place xywh2xyxy of yolov6/utils/general.py:58-64).  gt[b, m] = [cls, x1, y1, x2, y2] for the image's m-th label, m < M;
+ *   the rows behind the last label are [-1, 0, 0, 0, 0].  An image with more than M labels keeps its first M and sets
+ *   EVREP_TAL_ST_LABEL_OVERFLOW.  n_labels[b] is the true number.  Every byte of gt, n_labels and status is written.
+ *   targets DEVICE float [n_t,6] (NULL allowed when n_t == 0); gt DEVICE double [B,M,5] (NULL allowed when M == 0); n_labels
+ *   DEVICE int32 [B]; status DEVICE uint32 [B].  1 <= B <= 65535, 0 <= M <= EVREP_TAL_MAX_LABELS, 0 <= n_t <=
+ *   EVREP_DETEVAL_MAX_TARGETS, width and height finite.  One launch, no scratch.
+ *
+ * evrep_tal_assign is TaskAlignedAssigner.forward (yolov6/assigners/tal_assigner.py, assigner_utils.py) on such a gt.  The
+ *   reference's route is float64 (preprocess builds its tensor from Python floats) but for ONE float32 quantity, the predicted
+ *   box's own area; each statement below is one operation of the stated type, none fused with another (-ffp-contract=off, and the
+ *   kernel file repeats it as a pragma).  max(a, b) is a > b ? a : b, min(a, b) is a < b ? a : b.  pd_scores, pd_bboxes and
+ *   anc_points are float32 and widened where they meet a float64 value.
+ *   row         row m of image b is VALID iff ((x1 + y1) + x2) + y2 > 0 (mask_gt), its class lies in [0, nc) and the image is
+ *               finite (below).  A valid-box row whose class lies outside [0, nc) sets EVREP_TAL_ST_BAD_CLASS and is treated as
+ *               padding (the reference raises or wraps).
+ *   in-gt       d = min(min(ax - x1, ay - y1), min(x2 - ax, y2 - ay)); in_gt = d > 1e-9: a centre on an edge is outside.
+ *   iou         ix1 = max(x1, px1), ix2 = min(x2, px2), y likewise; ov = max(ix2 - ix1, 0) * max(iy2 - iy1, 0);
+ *               a1 = max(x2 - x1, 0) * max(y2 - y1, 0); a2 = max(px2 - px1, 0f) * max(py2 - py1, 0f) in FLOAT32, then widened;
+ *               iou = ov / (((a1 + a2) - ov) + 1e-9).
+ *   metric      al = score^alpha * iou^beta, score = pd_scores[b, a, long(cls)]; x^0 = 1, x^1 = x, x^n is n - 1 successive
+ *               multiplications by x, left to right.  The reference uses alpha = 1, beta = 6.
+ *   key         al if in_gt and al > 0, else +0.
+ *   top-k       per valid row the first `topk` anchors of the TOTAL order (key descending, anchor index ascending) over all A
+ *               anchors (all of them when topk > A); a selected anchor is a CANDIDATE of the row iff it is in_gt.  Zero keys are
+ *               therefore chosen by lowest index, inside the box or not: one of the outcomes the reference's torch.topk may
+ *               produce, made definite (as evrep_nms settles its max_nms ties).  Rows that are not valid have no candidates.
+ *   anchor      c = the rows it is a candidate of.  c == 0: background, row 0.  c == 1: that row.  c > 1: the FIRST row of greatest
+ *               iou over ALL M rows -- padding and rows it is no candidate of included (select_highest_overlaps, reproduced).
+ *               fg = c > 0; target_labels = long(cls) of the row when that lies in [0, nc), else 0; target_bboxes = the row's
+ *               box.  Background anchors carry row 0's label and box, as the reference returns them.
+ *   scores      pos_al[m] / pos_ov[m] = the greatest al / iou over the anchors assigned to row m, 0 when there is none (al is the
+ *               metric, not the key; only values > 0 take part; a row whose class lies outside [0, nc) has al = 0).
+ *               target_scores[b, a, :] is zero but at a foreground anchor's label, where it is (al * pos_ov) / (pos_al + 1e-9).
+ *   shapes      M == 0 is the reference's early return: labels nc, everything else zero, status 0.
+ *   status      EVREP_TAL_ST_BAD_CLASS as above; EVREP_TAL_ST_NONFINITE: an inf or NaN among pd_scores[b], pd_bboxes[b] or gt[b] --
+ *               the whole image is written as if it had no valid row.  (anc_points must be finite; products of finite inputs that
+ *               overflow are outside the contract.)
+ *   outputs     target_labels DEVICE int64 [B,A]; target_bboxes [B,A,4] and target_scores [B,A,nc] DEVICE double -- the
+ *               reference's dtype -- or, with EVREP_TAL_F32_OUT, float: the same float64 values rounded once at the store;
+ *               fg DEVICE uint8 [B,A]; status DEVICE uint32 [B].  Every byte of each is written on every call.
+ *   scratch     DEVICE, 256-byte aligned, evrep_tal_workspace_bytes(B, M, A) bytes (0 for a refused shape): per (image, anchor)
+ *               three 32-bit words and one double, per (image, row) two 64-bit words, each array rounded up to 256 bytes.  Needs
+ *               no initialisation: the call clears what it reads.
+ * pd_scores DEVICE float [B,A,nc]; pd_bboxes DEVICE float [B,A,4] xyxy; anc_points DEVICE float [A,2]; gt DEVICE double [B,M,5]
+ * (NULL allowed when M == 0).  1 <= B <= 65535, 0 <= M <= EVREP_TAL_MAX_LABELS, 1 <= A <= EVREP_TAL_MAX_ANCHORS,
+ * 1 <= nc <= EVREP_TAL_MAX_CLASSES, A * nc < 2^31, 1 <= topk <= EVREP_TAL_MAX_TOPK, alpha and beta in 0..EVREP_TAL_MAX_POWER;
+ * anything else, an unknown flag, a NULL or misaligned pointer is EVREP_EINVAL before any launch.  Integer atomics only: two
+ * calls give equal bits.  One async memset of status and up to four launches; does not allocate, does not wait for the
+ * device, reads nothing back: the call may be captured into a graph. */
+#define EVREP_TAL_F32_OUT 1u
+#define EVREP_TAL_MAX_TOPK 64
+#define EVREP_TAL_MAX_LABELS 1024
+#define EVREP_TAL_MAX_CLASSES 4096
+#define EVREP_TAL_MAX_ANCHORS (1 << 24)
+#define EVREP_TAL_MAX_POWER 16
+#define EVREP_TAL_ST_LABEL_OVERFLOW 1u
+#define EVREP_TAL_ST_BAD_CLASS 2u
+#define EVREP_TAL_ST_NONFINITE 4u
+int evrep_det_targets_pad(const float *targets, int64_t n_t, int32_t B, int32_t M, float width, float height, double *gt,
+                          int32_t *n_labels, uint32_t *status, void *stream);
+size_t evrep_tal_workspace_bytes(int32_t B, int32_t M, int32_t A);
+int evrep_tal_assign(const float *pd_scores, const float *pd_bboxes, const float *anc_points, const double *gt, int32_t B,
+                     int32_t M, int32_t A, int32_t nc, int32_t topk, int32_t alpha, int32_t beta, uint32_t flags,
+                     int64_t *target_labels, void *target_bboxes, void *target_scores, uint8_t *fg, uint32_t *status,
+                     void *scratch, void *stream);
+
 /* ev-licious' Events.render (ev-licious/src/evlicious/io/utils/render.py:9-141) for B windows of integer coordinates: two calls,
  * one stream builder over the binned records and one streaming launch.  Neither allocates, waits for the device or reads a
  * size on the host: both may be captured into a graph.  Limits: B <= 65535, H * W * 4 < 2^31.

@@ -1,0 +1,282 @@
+"""GPU: the training targets (csrc/evrep_assign.hip through detector_assign.assign_batch / TaskAlignedAssigner / preprocess)
+against the host restatement tal_host / preprocess_host BIT FOR BIT -- labels, boxes, scores, fg, status, in both output
+dtypes -- and against the golden recorded from the reference's own ComputeLoss.preprocess and TaskAlignedAssigner.forward.
+No tolerance between device and host: they perform the same float64 statements (and the one float32 area).
+
+Shapes: the select launch streams the anchors in chunks of 256 and merges into a list of topk <= 64; the label listing runs in
+rounds of 1024 rows.  A is 21 (below topk = 64), 84, 336 and 8400; M sits on both sides of 1, 64 and 256; topk is 1, 13, 64;
+B is 1 and 5.  The small cases are the dense ones: ties and multiply-claimed anchors are frequent at A = 84."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import assert_bit_equal, load_golden
+import detector_assign_cases as cases
+from guarded import FILLS, Arena
+from test_detector_assign_cpu import HAND, RTOL, golden_names
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+F32, F64 = np.float32, np.float64
+DTYPES = ((torch.float64, F64), (torch.float32, F32))
+
+
+def _da():
+    from event_representation_study_amd import detector_assign
+    return detector_assign
+
+
+def device(scores, boxes, anc, gt, topk=13, alpha=1, beta=6, dtype=torch.float64):
+    out = _da()._assign_device(torch.from_numpy(scores).to(DEV), torch.from_numpy(boxes).to(DEV), torch.from_numpy(anc).to(DEV),
+                               torch.from_numpy(gt).to(DEV), topk, alpha, beta, dtype)
+    torch.cuda.synchronize()
+    labels, tb, ts, fg, status = (t.cpu().numpy() for t in out)
+    return labels, tb, ts, fg.astype(bool), status.view(np.uint32)
+
+
+def check(scores, boxes, anc, gt, what="", topk=13, alpha=1, beta=6):
+    """Device == tal_host on all five, in both output dtypes, twice; returns the float64 host results."""
+    first = None
+    for tdt, ndt in DTYPES:
+        want = _da().tal_host(scores, boxes, anc, gt, topk=topk, alpha=alpha, beta=beta, out_dtype=ndt)
+        for rep in range(2):
+            got = device(scores, boxes, anc, gt, topk, alpha, beta, tdt)
+            for g, w, name in zip(got, want, ("labels", "boxes", "scores", "fg", "status")):
+                assert_bit_equal(g, w, "%s %s %s call %d" % (what, ndt.__name__, name, rep))
+        first = first or want
+    return first
+
+
+def pad_device(targets, B, M, W, H):
+    out = _da()._pad_device(torch.from_numpy(targets).to(DEV), B, M, W, H)
+    torch.cuda.synchronize()
+    gt, n_labels, status = (t.cpu().numpy() for t in out)
+    return gt, n_labels, status.view(np.uint32)
+
+
+# ------------------------------------------------------------------------------------------------------ against the reference
+@pytest.mark.parametrize("name", golden_names())
+def test_device_equals_the_reference_and_the_host(name):
+    g = load_golden("detector_assign")
+    S, B, nc = (int(v) for v in g[name + "/size"])
+    ref_gt = g[name + "/gt"]
+    gt, n_labels, st = pad_device(g[name + "/targets"], B, ref_gt.shape[1], S, S)
+    assert_bit_equal(gt, ref_gt, name + " preprocess")
+    assert not st.any() and n_labels.max() == ref_gt.shape[1]
+    labels, boxes, scores, fg, status = check(g[name + "/pd_scores"], g[name + "/pd_bboxes"], g[name + "/anc"], gt, name)
+    assert_bit_equal(labels, g[name + "/labels"], name)
+    assert_bit_equal(boxes, g[name + "/boxes"], name)
+    assert_bit_equal(fg, g[name + "/fg"], name)
+    want = g[name + "/scores"]
+    assert np.array_equal(scores != 0, want != 0)
+    np.testing.assert_allclose(scores, want, rtol=RTOL, atol=0)
+    assert not status.any()
+
+
+# -------------------------------------------------------------------------------------------------------- the hand-built cases
+@pytest.mark.parametrize("name", sorted(HAND))
+def test_hand_built_cases_on_the_device(name):
+    c = HAND[name]()
+    check(c["scores"], c["boxes"], c["anc"], c["gt"], name, topk=c["topk"])
+
+
+def test_more_than_m_labels_and_the_ordering_of_x2_on_the_device():
+    da = _da()
+    t = np.array([[0, 1, .5, .5, .2, .2], [1, 0, .5, .5, .2, .2], [0, 2, .25, .25, .1, .1], [0, 3, .75, .75, .1, .1],
+                  [0, 0, 0.13167430460453033, 0.13167430460453033, 0.0005333033623173833, 0.0005333033623173833]], F32)
+    for M in (0, 1, 2, 3, 4, 6):
+        want = da.preprocess_host(t, 2, F32(333.3), F32(64), max_labels=M)
+        got = pad_device(t, 2, M, F32(333.3), F32(64))
+        for g, w, name in zip(got, want, ("gt", "n_labels", "status")):
+            assert_bit_equal(g, w, "M %d %s" % (M, name))
+    assert got[0][0, 3, 3] == 43.97591911941277 and want[2].tolist() == [0, 0] and want[1].tolist() == [4, 1]
+
+
+# ------------------------------------------------------------------------------------------------------------------ the shapes
+@pytest.mark.parametrize("S,B", [(64, 1), (64, 5), (128, 5)])
+def test_seeded_sweep(S, B):
+    """Coarse scores (multiples of 1/4) and predictions snapped to whole pixels: equal keys and equal IoUs are frequent, anchors
+    are claimed by several rows."""
+    multi = 0
+    for seed in range(4):
+        nc = (1, 2, 3, 80)[seed]
+        scores, boxes, anc = cases.head(300 + seed, B, S, nc)
+        scores = (np.ceil(scores * 4) / 4).astype(F32)
+        boxes = np.round(boxes).astype(F32)
+        counts = [(3 * b + seed * 5) % 17 for b in range(B)]
+        t = cases.targets(400 + seed, counts, nc, lo=0.1, hi=0.7)
+        t[:, 2:] = np.round(t[:, 2:] * 16) / 16                          # box edges on anchor centres
+        gt = _da().preprocess_host(t, B, S, S)[0]
+        out = check(scores, boxes, anc, gt, "sweep %d" % seed)
+        if gt.shape[1]:
+            d = {}
+            _da().tal_image_host(scores[0], boxes[0], anc, gt[0], 13, nc, 1, 6, details=d)
+            multi += int((d["count"] > 1).sum())
+        assert out[3].any() or not sum(counts)
+    assert multi > 0
+
+
+def test_8400_anchors():
+    """The level boundaries at 6400 and 8000, and anchors far beyond the first chunk of 256 take part: boxes in the lower right."""
+    scores, boxes, anc = cases.head(500, 2, 640, 3)
+    rows = [[0, 1, 560, 560, 640, 640], [0, 2, 300, 300, 640, 640], [1, 0, 0, 0, 640, 640], [1, 1, 500, 100, 620, 400]]
+    t = np.concatenate([cases.xyxy_rows(r[0], [tuple(r[1:])], 640) for r in rows], 0)
+    gt = _da().preprocess_host(t, 2, 640, 640)[0]
+    labels, tb, ts, fg, status = check(scores, boxes, anc, gt, "8400")
+    hit = np.flatnonzero(fg[0])
+    assert hit.min() > 256 and (hit < 6400).any() and fg[1].any() and 0 < fg.sum() <= 4 * 13
+
+
+@pytest.mark.parametrize("M", [0, 1, 2, 63, 64, 65, 255, 256, 257])
+def test_label_counts_around_1_64_and_256(M):
+    da = _da()
+    B, S, nc = 2, 64, 2
+    scores, boxes, anc = cases.head(600 + M, B, S, nc)
+    t = cases.targets(700 + M, [M, min(M, 1)], nc)
+    gt_h, n_h, st_h = da.preprocess_host(t, B, S, S, max_labels=M)
+    gt, n_labels, st = pad_device(t, B, M, S, S)
+    assert_bit_equal(gt, gt_h)
+    assert n_labels.tolist() == n_h.tolist() == [M, min(M, 1)] and not st.any() and not st_h.any()
+    out = check(scores, boxes, anc, gt, "M %d" % M)
+    assert (out[0] == nc).all() if M == 0 else out[3].any()
+
+
+@pytest.mark.parametrize("topk", [1, 13, 64])
+@pytest.mark.parametrize("S", [32, 64])
+def test_topk_1_13_64_and_above_the_anchor_count(S, topk):
+    """S = 32 has 21 anchors: topk = 64 selects them all, and every in-box anchor is a candidate."""
+    scores, boxes, anc = cases.head(800 + topk, 3, S, 2)
+    gt = _da().preprocess_host(cases.targets(810 + topk, [4, 0, 7], 2, lo=0.2, hi=0.8), 3, S, S)[0]
+    assert len(anc) == (21 if S == 32 else 84)
+    out = check(scores, boxes, anc, gt, "topk %d" % topk, topk=topk)
+    assert out[3][0].any() and not out[3][1].any()
+    if topk > len(anc):
+        inside = _da()._in_gt_host(gt[0, :, 1:], anc).any(0)
+        assert np.array_equal(out[3][0], inside)
+
+
+def test_other_exponents():
+    scores, boxes, anc = cases.head(900, 2, 64, 2)
+    gt = _da().preprocess_host(cases.targets(901, [5, 3], 2), 2, 64, 64)[0]
+    for alpha, beta in ((0, 0), (2, 1), (0, 16), (16, 3)):
+        check(scores, boxes, anc, gt, "alpha %d beta %d" % (alpha, beta), alpha=alpha, beta=beta)
+
+
+# ------------------------------------------------------------------------------------------------------------ the public routes
+def test_assign_batch_and_the_drop_in_class_agree():
+    da = _da()
+    B, S, nc = 5, 64, 4
+    scores, boxes, anc = cases.head(1000, B, S, nc)
+    t = cases.targets(1001, [3, 0, 6, 1, 2], nc)
+    s, p, a = (torch.from_numpy(v).to(DEV) for v in (scores, boxes, anc))
+    gt_h = da.preprocess_host(t, B, S, S)[0]
+    want = da.tal_host(scores, boxes, anc, gt_h)
+    for targets, kw in ((torch.from_numpy(t), {}), (torch.from_numpy(t).to(DEV), dict(max_labels=6))):
+        labels, tb, ts, fg, status = da.assign_batch(s, p, a, targets, (S, S), nc, check=True, **kw)
+        assert labels.is_cuda and fg.dtype == torch.bool and tb.dtype == ts.dtype == torch.float64 and status.tolist() == [0] * B
+        for g, w in zip((labels, tb, ts, fg), want):
+            assert_bit_equal(g.cpu().numpy(), w)
+    gt = da.preprocess(torch.from_numpy(t).to(DEV), B, S, S, max_labels=6)
+    assert gt.is_cuda and gt.dtype == torch.float64
+    assert_bit_equal(gt.cpu().numpy(), gt_h)
+    tal = da.TaskAlignedAssigner(topk=13, num_classes=nc, alpha=1.0, beta=6.0)
+    out = tal(s, p, a, gt[:, :, :1], gt[:, :, 1:], (gt[:, :, 1:].sum(-1, keepdim=True) > 0).float())
+    assert [o.dtype for o in out] == [torch.int64, torch.float64, torch.float64, torch.bool] and tal.last_status.tolist() == [0] * B
+    for g, w in zip(out, want):
+        assert_bit_equal(g.cpu().numpy(), w)
+    f32 = da.assign_batch(s, p, a, torch.from_numpy(t), (S, S), nc, out_dtype=torch.float32)
+    assert f32[1].dtype == f32[2].dtype == torch.float32
+    assert_bit_equal(f32[2].cpu().numpy(), want[2].astype(F32))
+    with pytest.raises(ValueError, match="max_labels"):
+        da.assign_batch(s, p, a, torch.from_numpy(t).to(DEV), (S, S), nc)
+    with pytest.raises(ValueError, match=r"\.float\(\)"):
+        da.assign_batch(s.double(), p, a, torch.from_numpy(t), (S, S), nc)
+    with pytest.raises(ValueError, match="image 2: more labels than max_labels"):
+        da.assign_batch(s, p, a, torch.from_numpy(t), (S, S), nc, max_labels=4, check=True)
+    bad = s.clone()
+    bad[3, 7, 1] = float("inf")
+    st = da.assign_batch(bad, p, a, torch.from_numpy(t), (S, S), nc)[4]
+    assert st.tolist() == [0, 0, 0, da.ST_NONFINITE, 0]
+
+
+def test_capture_and_replay():
+    da = _da()
+    B, S, nc = 3, 64, 2
+    scores, boxes, anc = cases.head(1100, B, S, nc)
+    other = cases.head(1101, B, S, nc)
+    t1, t2 = cases.targets(1102, [4, 0, 5], nc), cases.targets(1103, [2, 5, 2], nc)
+    assert t1.shape == t2.shape
+    s, p, a, t = (torch.from_numpy(v).to(DEV) for v in (scores, boxes, anc, t1))
+    eager = da.assign_batch(s, p, a, t, (S, S), nc, max_labels=5)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = da.assign_batch(s, p, a, t, (S, S), nc, max_labels=5)
+    s.copy_(torch.from_numpy(other[0])); p.copy_(torch.from_numpy(other[1])); t.copy_(torch.from_numpy(t2))
+    graph.replay()
+    torch.cuda.synchronize()
+    want = da.tal_host(other[0], other[1], anc, da.preprocess_host(t2, B, S, S, max_labels=5)[0])
+    for g, w, name in zip(out[:4], want, ("labels", "boxes", "scores", "fg")):
+        assert_bit_equal(g.cpu().numpy(), w, "replay on new contents: " + name)
+    s.copy_(torch.from_numpy(scores)); p.copy_(torch.from_numpy(boxes)); t.copy_(torch.from_numpy(t1))
+    graph.replay()
+    torch.cuda.synchronize()
+    assert all(torch.equal(x, y) for x, y in zip(out, eager)), "the same bytes as the eager call"
+
+
+# ------------------------------------------------------------------------------------------------------ the size contracts
+@pytest.mark.parametrize("f32_out", [False, True], ids=["f64", "f32"])
+def test_scratch_and_outputs_are_as_long_as_stated_and_wholly_written(f32_out):
+    """Inputs, scratch and outputs exactly as long as the header says, each between guard bands, the inputs registered
+    read-only; scratch and outputs poisoned with zeros, 0xFF and random bytes give the same bytes (the scratch needs no
+    initialisation, every output byte is written), no band and no input byte changes.  B * A = 105 and B * M = 35: no array
+    of the scratch fills its 256-byte slot."""
+    from event_representation_study_amd import _lib
+    da = _da()
+    lib = _lib.load()
+    B, S, nc, M = 5, 32, 3, 7
+    scores, boxes, anc = cases.head(1200, B, S, nc)
+    t = cases.targets(1201, [7, 0, 3, 9, 1], nc, lo=0.2, hi=0.8)
+    A, n_t = len(anc), len(t)
+    gt_h, n_h, st_h = da.preprocess_host(t, B, S, S, max_labels=M)
+    want = da.tal_host(scores, boxes, anc, gt_h, out_dtype=F32 if f32_out else F64)
+    tdt = torch.float32 if f32_out else torch.float64
+    nbytes = int(lib.evrep_tal_workspace_bytes(B, M, A))
+    assert nbytes == 3 * 512 + 1024 + 2 * 512
+    P = ctypes.c_void_p
+    for seed, fill in tuple((1, f) for f in FILLS) + ((2, "random"),):
+        arena = Arena(DEV, seed)
+        ins = {}
+        for name, v in (("targets", t), ("scores", scores), ("boxes", boxes), ("anc", anc)):
+            arena.carve_like(torch.from_numpy(v), name=name)
+            ins[name] = arena.ptr()
+        outs, ptrs = {}, {}
+        for name, shape, dtype in (("gt", (B, M, 5), torch.float64), ("n_labels", (B,), torch.int32), ("st_pad", (B,), torch.int32),
+                                   ("labels", (B, A), torch.int64), ("tb", (B, A, 4), tdt), ("ts", (B, A, nc), tdt),
+                                   ("fg", (B, A), torch.uint8), ("status", (B,), torch.int32)):
+            outs[name] = arena.carve_shape(shape, dtype, fill=fill, name=name)
+            ptrs[name] = arena.ptr()
+        arena.carve(nbytes, fill=fill, name="scratch")
+        scratch = arena.ptr()
+        stream = P(torch.cuda.current_stream().cuda_stream)
+        _lib.check(lib.evrep_det_targets_pad(P(ins["targets"]), n_t, B, M, float(S), float(S), P(ptrs["gt"]), P(ptrs["n_labels"]),
+                                             P(ptrs["st_pad"]), stream), "evrep_det_targets_pad")
+        _lib.check(lib.evrep_tal_assign(P(ins["scores"]), P(ins["boxes"]), P(ins["anc"]), P(ptrs["gt"]), B, M, A, nc, 13, 1, 6,
+                                        _lib.TAL_F32_OUT if f32_out else 0, P(ptrs["labels"]), P(ptrs["tb"]), P(ptrs["ts"]), P(ptrs["fg"]),
+                                        P(ptrs["status"]), P(scratch), stream), "evrep_tal_assign")
+        torch.cuda.synchronize()
+        arena.check()
+        arena.check_inputs()
+        what = "seed %d fill %s " % (seed, fill)
+        assert_bit_equal(outs["gt"].cpu().numpy(), gt_h, what + "gt")
+        assert_bit_equal(outs["n_labels"].cpu().numpy(), n_h, what + "n_labels")
+        assert_bit_equal(outs["st_pad"].cpu().numpy().view(np.uint32), st_h, what + "pad status")
+        assert st_h.tolist() == [0, 0, 0, da.ST_LABEL_OVERFLOW, 0]
+        for name, w in zip(("labels", "tb", "ts"), want):
+            assert_bit_equal(outs[name].cpu().numpy(), w, what + name)
+        assert_bit_equal(outs["fg"].cpu().numpy().astype(bool), want[3], what + "fg")
+        assert outs["fg"].max().item() == 1, "fg is 0 or 1"
+        assert_bit_equal(outs["status"].cpu().numpy().view(np.uint32), want[4], what + "status")
