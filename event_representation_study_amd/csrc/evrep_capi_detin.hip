@@ -1,8 +1,8 @@
 // evrep_capi_detin.hip -- the extern "C" surface, part 10: the detector's input batch (evrep_detin.hip), its form for frames
 // of different sizes with the tap tables made on the device (evrep_detin_frames.hip), and the detector's output, the batched
 // non_max_suppression (evrep_nms.hip), the scoring of its detections against the labels (evrep_deteval.hip), and the training
-// targets, label padding and the task-aligned assigner (evrep_assign.hip): argument checks and the launches of each entry
-// point.  No plan, no workspace, no allocation, no wait for the device.
+// targets, label padding and the task-aligned assigner (evrep_assign.hip), and the loss terms with their gradients
+// (evrep_detloss.hip): argument checks and the launches of each entry point.  No plan, no workspace, no allocation, no wait for the device.
 #include <limits.h>
 
 #include "evrep_capi_shared.h"
@@ -10,6 +10,7 @@
 #include "evrep_nms.hip"
 #include "evrep_deteval.hip"
 #include "evrep_assign.hip"
+#include "evrep_detloss.hip"
 
 using namespace evrep;
 using evrep_host::hip_check;
@@ -278,6 +279,104 @@ int evrep_tal_assign(const float *pd_scores, const float *pd_bboxes, const float
     LAUNCH_CHECK("k_tal_resolve");
     k_tal_scores<<<dim3(spread((size_t)A * nc), (unsigned)B), kThreads, 0, stream>>>(t);
     LAUNCH_CHECK("k_tal_scores");
+    return EVREP_OK;
+}
+
+static inline bool detloss_shape_ok(int32_t B, int32_t A, int32_t nc) {
+    return B >= 1 && B <= 65535 && A >= 1 && A <= EVREP_TAL_MAX_ANCHORS && nc >= 1 && nc <= EVREP_TAL_MAX_CLASSES && (int64_t)A * nc <= INT32_MAX;
+}
+
+// the grids of evrep_detloss: slices of tss, workgroups per image of the class term, workgroups per image of the box terms
+static inline uint32_t detloss_n_tss(int32_t B, int32_t A) {
+    const size_t chunks = ((size_t)B * (size_t)A + kThreads - 1) / kThreads;
+    return (uint32_t)(chunks < (size_t)kDetlossSlices ? chunks : (size_t)kDetlossSlices);
+}
+static inline uint32_t detloss_gc(int32_t B, int32_t A, int32_t nc) {
+    const size_t need = ((size_t)A * (size_t)nc + kThreads - 1) / kThreads, cap = (2048 + (size_t)B - 1) / (size_t)B;
+    return (uint32_t)(need < cap ? need : cap);
+}
+static inline uint32_t detloss_ga(int32_t A) { return (uint32_t)((A + kThreads - 1) / kThreads); }
+
+// the scratch of evrep_detloss: the rows' sums per (image, anchor), then the partial sums of the four launches
+static size_t detloss_layout(void *scratch, int32_t B, int32_t A, int32_t nc, DetlossArgs *t) {
+    Carver c(scratch);
+    const size_t n_tss = detloss_n_tss(B, A), n_cls = (size_t)B * detloss_gc(B, A, nc), n_box = (size_t)B * detloss_ga(A);
+    double *w = c.take<double>((size_t)B * (size_t)A * 8);
+    double *tss_part = c.take<double>(n_tss * 8);
+    double *cls_part = c.take<double>(n_cls * 8);
+    double *iou_part = c.take<double>(n_box * 8);
+    double *dfl_part = c.take<double>(n_box * 8);
+    double *cnt_part = c.take<double>(n_box * 8);
+    if (t) {
+        t->w = w; t->tss_part = tss_part; t->cls_part = cls_part; t->iou_part = iou_part; t->dfl_part = dfl_part; t->cnt_part = cnt_part;
+        t->n_tss = (uint32_t)n_tss; t->n_cls = (uint32_t)n_cls; t->n_box = (uint32_t)n_box;
+    }
+    return c.off;
+}
+
+size_t evrep_detloss_workspace_bytes(int32_t B, int32_t A, int32_t nc) {
+    return detloss_shape_ok(B, A, nc) ? detloss_layout(nullptr, B, A, nc, nullptr) : 0;
+}
+
+// R with DFL: 1..32 (the bins tl and tl + 1 of a target lie inside the R + 1 logits); without: 0..32, not read
+static inline bool detloss_r_ok(int32_t R, uint32_t flags) {
+    return R <= EVREP_DETLOSS_MAX_REG && R >= ((flags & EVREP_DETLOSS_USE_DFL) ? 1 : 0);
+}
+
+int evrep_detloss_decode(const float *pred_distri, const float *anc_points, const float *stride, int32_t B, int32_t A, int32_t R,
+                         uint32_t flags, float *boxes_s, float *boxes_px, void *stream_) {
+    if (B < 1 || B > 65535 || A < 1 || A > EVREP_TAL_MAX_ANCHORS) return EVREP_EINVAL;
+    if ((flags & ~(uint32_t)EVREP_DETLOSS_USE_DFL) || !detloss_r_ok(R, flags)) return EVREP_EINVAL;
+    if (bad_ptr(pred_distri, 4) || bad_ptr(anc_points, 4) || bad_ptr(stride, 4) || bad_ptr(boxes_s, 4) || bad_ptr(boxes_px, 4))
+        return EVREP_EINVAL;
+    DetlossArgs t;
+    memset(&t, 0, sizeof(t));
+    t.z = pred_distri; t.anc = anc_points; t.stride = stride; t.boxes_s = boxes_s; t.boxes_px = boxes_px;
+    t.B = B; t.A = A; t.R = R;
+    t.use_dfl = (flags & EVREP_DETLOSS_USE_DFL) ? 1 : 0;
+    t.K = t.use_dfl ? R + 1 : 1;
+    k_detloss_decode<<<dim3((unsigned)((4 * (size_t)A + kThreads - 1) / kThreads), (unsigned)B), kThreads, 0, as_stream(stream_)>>>(t);
+    LAUNCH_CHECK("k_detloss_decode");
+    return EVREP_OK;
+}
+
+int evrep_detloss(const float *pred_scores, const float *pred_distri, const float *anc_points, const float *stride,
+                  const int64_t *target_labels, const void *target_bboxes, const void *target_scores, const uint8_t *fg, int32_t B,
+                  int32_t A, int32_t nc, int32_t R, double w_class, double w_iou, double w_dfl, uint32_t flags, double *losses,
+                  float *grad_scores, float *grad_distri, uint32_t *status, void *scratch, void *stream_) {
+    if (!detloss_shape_ok(B, A, nc)) return EVREP_EINVAL;
+    if ((flags & ~(uint32_t)(EVREP_DETLOSS_USE_DFL | EVREP_DETLOSS_NO_GRAD | EVREP_DETLOSS_F32_TARGETS)) || !detloss_r_ok(R, flags))
+        return EVREP_EINVAL;
+    const uintptr_t elem = (flags & EVREP_DETLOSS_F32_TARGETS) ? 4 : 8;
+    const bool grad = !(flags & EVREP_DETLOSS_NO_GRAD);
+    if (bad_ptr(pred_scores, 4) || bad_ptr(pred_distri, 4) || bad_ptr(anc_points, 4) || bad_ptr(stride, 4)) return EVREP_EINVAL;
+    if (bad_ptr(target_labels, 8) || bad_ptr(target_bboxes, elem) || bad_ptr(target_scores, elem) || bad_ptr(fg, 1)) return EVREP_EINVAL;
+    if (grad ? (bad_ptr(grad_scores, 4) || bad_ptr(grad_distri, 4)) : (misaligned(grad_scores, 4) || misaligned(grad_distri, 4)))
+        return EVREP_EINVAL;
+    if (bad_ptr(losses, 8) || bad_ptr(status, 4) || bad_ptr(scratch, 256)) return EVREP_EINVAL;
+    DetlossArgs t;
+    memset(&t, 0, sizeof(t));
+    t.p = pred_scores; t.z = pred_distri; t.anc = anc_points; t.stride = stride;
+    t.labels = target_labels; t.tb = target_bboxes; t.ts = target_scores; t.fg = fg;
+    t.losses = losses; t.gs = grad ? grad_scores : nullptr; t.gz = grad ? grad_distri : nullptr; t.status = status;
+    t.wc = w_class; t.wi = w_iou; t.wd = w_dfl;
+    t.B = B; t.A = A; t.nc = nc; t.R = R;
+    t.use_dfl = (flags & EVREP_DETLOSS_USE_DFL) ? 1 : 0;
+    t.K = t.use_dfl ? R + 1 : 1;
+    t.f32_t = (flags & EVREP_DETLOSS_F32_TARGETS) ? 1 : 0;
+    t.grad = grad ? 1 : 0;
+    detloss_layout(scratch, B, A, nc, &t);
+    hipStream_t stream = as_stream(stream_);
+    int rc = hip_check(hipMemsetAsync(status, 0, (size_t)B * 4u, stream), "hipMemsetAsync(status)");
+    if (rc != EVREP_OK) return rc;
+    k_detloss_rows<<<t.n_tss, kThreads, 0, stream>>>(t);
+    LAUNCH_CHECK("k_detloss_rows");
+    k_detloss_cls<<<dim3(detloss_gc(B, A, nc), (unsigned)B), kThreads, 0, stream>>>(t);
+    LAUNCH_CHECK("k_detloss_cls");
+    k_detloss_box<<<dim3(detloss_ga(A), (unsigned)B), kThreads, 0, stream>>>(t);
+    LAUNCH_CHECK("k_detloss_box");
+    k_detloss_fold<<<1, kThreads, 0, stream>>>(t);
+    LAUNCH_CHECK("k_detloss_fold");
     return EVREP_OK;
 }
 

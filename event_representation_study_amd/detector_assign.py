@@ -30,7 +30,8 @@ that type.  ``max(a, b)`` is ``a > b ? a : b``, ``min`` likewise.
 9. M = 0 is the reference's early return (labels ``num_classes``, the rest zero).  A non-finite value among an image's
    predictions or labels sets ``ST_NONFINITE`` and the image is written as if it had no valid row.
 
-The ATSS assigner of the warm-up epochs, the loss terms and half-precision predictions are not mirrored.
+The ATSS assigner of the warm-up epochs and half-precision predictions are not mirrored.  The loss terms behind the
+assigner are ``detector_loss`` (``decode_boxes`` in front of ``assign_batch``, ``loss_batch`` behind it, ``ComputeLoss`` for both).
 """
 import numpy as np
 import torch

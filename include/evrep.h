@@ -1034,6 +1034,62 @@ int evrep_tal_assign(const float *pd_scores, const float *pd_bboxes, const float
                      int64_t *target_labels, void *target_bboxes, void *target_scores, uint8_t *fg, uint32_t *status,
                      void *scratch, void *stream);
 
+/* The loss terms of ComputeLoss.__call__ (loss.py:176-217: VarifocalLoss, BboxLoss with IOUloss(xyxy, giou, eps = 1e-10) of
+ * yolov6/utils/figure_iou.py and _df_loss) and bbox_decode (loss.py:238-244), values AND gradients, for the targets
+ * evrep_tal_assign wrote.  Every statement below is ONE float64 operation unless a type is named; float32 inputs are widened
+ * exactly; nothing is fused; exp / log are the double library functions; max(a, b) is a > b ? a : b, min(a, b) is a < b ? a : b.
+ * R = reg_max, K = R + 1 with EVREP_DETLOSS_USE_DFL, else K = 1 (pred_distri holds the four distances themselves and R is not
+ * read).  z = pred_distri, p = pred_scores (after the sigmoid).
+ *   decode     aps = fl32(anc / stride) per coordinate, widened.  Per side s of (l, t, r, b), with DFL: m = max_k z[s,k];
+ *              e_k = exp(z[s,k] - m); Z = the e_k added left to right; pr_k = e_k / Z; d_s = the products pr_k * k added left to
+ *              right.  Without: d_s = z[s].  box = [ax - d_l, ay - d_t, ax + d_r, ay + d_b] in stride units.
+ *   sums       w[b,a] = target_scores[b,a,:] added left to right; tss = all w in a fixed order that depends on (B, A) only;
+ *              norm = tss > 1 ? tss : 1, decided on the device.
+ *   class      q = target_scores; lab = fg[b,a] && target_labels[b,a] == c; wt = lab ? q : (0.75 * p) * p;
+ *              bce = -(q * max(log(p), -100) + (1 - q) * max(log(1 - p), -100)); loss_cls = (sum of bce * wt) / norm.
+ *   box        per foreground anchor, tb = target_bboxes / stride: inter = max(min(x2, tx2) - max(x1, tx1), 0) * (y likewise);
+ *              w1 = x2 - x1; h1 = (y2 - y1) + eps; w2, h2 likewise; union = ((w1 * h1 + w2 * h2) - inter) + eps;
+ *              iou = inter / union; cw = max(x2, tx2) - min(x1, tx1), ch likewise; c_area = cw * ch + eps;
+ *              giou = iou - (c_area - union) / c_area; loss_iou = (sum of (1 - giou) * w) / norm.
+ *   DFL        per foreground anchor and side: t = min(max(distance of tb from aps, 0), R - 0.01); tl = (long)t;
+ *              wl = (tl + 1) - t; wr = 1 - wl; lse = m + log(Z); ce(k) = lse - z[s,k]; side = ce(tl) * wl + ce(tl + 1) * wr;
+ *              dfl = (((side_l + side_t) + side_r) + side_b) / 4; loss_dfl = (sum of dfl * w) / norm.  Without DFL loss_dfl = 0;
+ *              with no foreground anchor loss_iou = loss_dfl = 0 and grad_distri is all zeros.
+ *   gradients  of L = w_class * loss_cls + w_iou * loss_iou + w_dfl * loss_dfl with respect to p and z, what torch's autograd
+ *              gives for the reference's statements: BCE's backward is (p - q) / max((1 - p) * p, (double)1e-12f) -- torch holds
+ *              that constant as a float, 9.999999960041972e-13 --, also where the log was clamped; wt is not detached (a non-label element adds bce * (1.5 * p)); the clamp at 0 passes the gradient at
+ *              x >= 0; min / max of equal arguments split it in halves; d d_s / d z[s,k] = pr_k * (k - d_s); the DFL part is
+ *              ((w_dfl * w) / norm / 4) * ((pr_k - wl [k == tl]) - wr [k == tl + 1]).  Formed in float64, rounded ONCE at the
+ *              store.  Every byte of both arrays is written; the rows of background anchors in grad_distri are zeros.
+ *   status     EVREP_DETLOSS_ST_BAD_LABEL: a foreground anchor whose label lies outside [0, nc): background for the class term
+ *              (the reference's one_hot raises), a foreground anchor for the box terms.  Non-finite inputs propagate as in torch.
+ * evrep_detloss_decode: boxes_s DEVICE float [B,A,4] = the float64 box rounded once; boxes_px DEVICE float [B,A,4] =
+ *   fl32(box * stride), what evrep_tal_assign takes as pd_bboxes.  One launch, no scratch.  flags: EVREP_DETLOSS_USE_DFL.
+ * evrep_detloss: pred_scores DEVICE float [B,A,nc]; pred_distri DEVICE float [B,A,4K]; anc_points DEVICE float [A,2] (pixels);
+ *   stride DEVICE float [A]; target_labels DEVICE int64 [B,A]; target_bboxes [B,A,4] (pixels) and target_scores [B,A,nc] DEVICE
+ *   double, or float with EVREP_DETLOSS_F32_TARGETS; fg DEVICE uint8 [B,A].  losses DEVICE double [5] = loss_cls, loss_iou,
+ *   loss_dfl (normalised, unweighted), tss, the number of foreground anchors.  grad_scores DEVICE float [B,A,nc], grad_distri
+ *   DEVICE float [B,A,4K]: with EVREP_DETLOSS_NO_GRAD they may be NULL and nothing of them is computed.  status DEVICE uint32
+ *   [B].  scratch DEVICE, 256-byte aligned, evrep_detloss_workspace_bytes(B, A, nc) bytes (0 for a refused shape): B * A
+ *   doubles, then min(ceil(B * A / 256), 256) doubles, then B * min(ceil(A * nc / 256), ceil(2048 / B)) doubles, then three
+ *   times B * ceil(A / 256) doubles, each array rounded up to 256 bytes.  Needs no initialisation.
+ * 1 <= B <= 65535, 1 <= A <= EVREP_TAL_MAX_ANCHORS, 1 <= nc <= EVREP_TAL_MAX_CLASSES, A * nc < 2^31, 0 <= R <=
+ * EVREP_DETLOSS_MAX_REG (1 <= R with EVREP_DETLOSS_USE_DFL); anything else, an unknown flag, a NULL or misaligned pointer is
+ * EVREP_EINVAL before any launch.  One async memset of status and four launches; no floating-point atomics: two calls give
+ * equal bits.  Does not allocate, does not wait for the device, reads nothing back: the call may be captured into a graph. */
+#define EVREP_DETLOSS_USE_DFL 1u
+#define EVREP_DETLOSS_NO_GRAD 2u
+#define EVREP_DETLOSS_F32_TARGETS 4u
+#define EVREP_DETLOSS_MAX_REG 32
+#define EVREP_DETLOSS_ST_BAD_LABEL 1u
+int evrep_detloss_decode(const float *pred_distri, const float *anc_points, const float *stride, int32_t B, int32_t A, int32_t R,
+                         uint32_t flags, float *boxes_s, float *boxes_px, void *stream);
+size_t evrep_detloss_workspace_bytes(int32_t B, int32_t A, int32_t nc);
+int evrep_detloss(const float *pred_scores, const float *pred_distri, const float *anc_points, const float *stride,
+                  const int64_t *target_labels, const void *target_bboxes, const void *target_scores, const uint8_t *fg, int32_t B,
+                  int32_t A, int32_t nc, int32_t R, double w_class, double w_iou, double w_dfl, uint32_t flags, double *losses,
+                  float *grad_scores, float *grad_distri, uint32_t *status, void *scratch, void *stream);
+
 /* ev-licious' Events.render (ev-licious/src/evlicious/io/utils/render.py:9-141) for B windows of integer coordinates: two calls,
  * one stream builder over the binned records and one streaming launch.  Neither allocates, waits for the device or reads a
  * size on the host: both may be captured into a graph.  Limits: B <= 65535, H * W * 4 < 2^31.
