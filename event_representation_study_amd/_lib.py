@@ -129,6 +129,9 @@ SYMBOLS = {
     "evrep_tal_workspace_bytes": (ctypes.c_size_t, [_i32, _i32, _i32]),
     "evrep_tal_assign": _st([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp]),
+    "evrep_atss_workspace_bytes": (ctypes.c_size_t, [_i32, _i32, _i32]),
+    "evrep_atss_assign": _st([_vp, _I32P, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
+                              _vp]),
     "evrep_detloss_decode": _st([_vp, _vp, _vp, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp]),
     "evrep_detloss_workspace_bytes": (ctypes.c_size_t, [_i32, _i32, _i32]),
     "evrep_detloss": _st([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f64, _f64, _f64, ctypes.c_uint32, _vp, _vp,
@@ -179,6 +182,9 @@ DETEVAL_ST_LABEL_OVERFLOW, DETEVAL_ST_BAD_CLASS, DETEVAL_ST_BAD_COUNT = 1, 2, 4
 TAL_F32_OUT = 1
 TAL_MAX_TOPK, TAL_MAX_LABELS, TAL_MAX_CLASSES, TAL_MAX_ANCHORS, TAL_MAX_POWER = 64, 1024, 4096, 1 << 24, 16
 TAL_ST_LABEL_OVERFLOW, TAL_ST_BAD_CLASS, TAL_ST_NONFINITE = 1, 2, 4
+# evrep_atss_assign: flags, limits (the shapes' limits and the status bits are the TAL ones)
+ATSS_F32_BOXES, ATSS_F32_SCORES = 1, 2
+ATSS_MAX_TOPK, ATSS_MAX_LEVELS, ATSS_MAX_CANDIDATES = 32, 8, 256
 # evrep_detloss_decode / evrep_detloss: flags, the greatest reg_max, per-image status bit
 DETLOSS_USE_DFL, DETLOSS_NO_GRAD, DETLOSS_F32_TARGETS = 1, 2, 4
 DETLOSS_MAX_REG = 32

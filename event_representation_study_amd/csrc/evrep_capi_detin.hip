@@ -1,7 +1,8 @@
 // evrep_capi_detin.hip -- the extern "C" surface, part 10: the detector's input batch (evrep_detin.hip), its form for frames
 // of different sizes with the tap tables made on the device (evrep_detin_frames.hip), and the detector's output, the batched
 // non_max_suppression (evrep_nms.hip), the scoring of its detections against the labels (evrep_deteval.hip), and the training
-// targets, label padding and the task-aligned assigner (evrep_assign.hip), and the loss terms with their gradients
+// targets, label padding and the task-aligned assigner (evrep_assign.hip) with the ATSS assigner of the warm-up epochs
+// (evrep_atss.hip), and the loss terms with their gradients
 // (evrep_detloss.hip): argument checks and the launches of each entry point.  No plan, no workspace, no allocation, no wait for the device.
 #include <limits.h>
 
@@ -10,6 +11,7 @@
 #include "evrep_nms.hip"
 #include "evrep_deteval.hip"
 #include "evrep_assign.hip"
+#include "evrep_atss.hip"
 #include "evrep_detloss.hip"
 
 using namespace evrep;
@@ -279,6 +281,73 @@ int evrep_tal_assign(const float *pd_scores, const float *pd_bboxes, const float
     LAUNCH_CHECK("k_tal_resolve");
     k_tal_scores<<<dim3(spread((size_t)A * nc), (unsigned)B), kThreads, 0, stream>>>(t);
     LAUNCH_CHECK("k_tal_scores");
+    return EVREP_OK;
+}
+
+// the scratch of evrep_atss_assign: per (image, anchor) cnt, first, row and the score value
+static size_t atss_layout(void *scratch, int32_t B, int32_t A, AtssArgs *t) {
+    Carver c(scratch);
+    const size_t ba = (size_t)B * (size_t)A;
+    uint32_t *cnt = c.take<uint32_t>(ba * 4);
+    uint32_t *first = c.take<uint32_t>(ba * 4);
+    int32_t *row = c.take<int32_t>(ba * 4);
+    double *val = c.take<double>(ba * 8);
+    if (t) {
+        t->cnt = cnt; t->first = first; t->row = row; t->val = val;
+    }
+    return c.off;
+}
+
+size_t evrep_atss_workspace_bytes(int32_t B, int32_t M, int32_t A) {
+    return tal_shape_ok(B, M, A) ? atss_layout(nullptr, B, A, nullptr) : 0;
+}
+
+int evrep_atss_assign(const float *anchors, const int32_t *level_counts, int32_t n_levels, const double *gt, const float *pd_bboxes,
+                      int32_t B, int32_t M, int32_t A, int32_t nc, int32_t topk, uint32_t flags, int64_t *target_labels,
+                      void *target_bboxes, void *target_scores, uint8_t *fg, uint32_t *status, void *scratch, void *stream_) {
+    if (!tal_shape_ok(B, M, A) || nc < 1 || nc > EVREP_TAL_MAX_CLASSES || (int64_t)A * nc > INT32_MAX) return EVREP_EINVAL;
+    if (topk < 1 || topk > EVREP_ATSS_MAX_TOPK || n_levels < 1 || n_levels > EVREP_ATSS_MAX_LEVELS || n_levels * topk > EVREP_ATSS_MAX_CANDIDATES || !level_counts)
+        return EVREP_EINVAL;
+    if (flags & ~(uint32_t)(EVREP_ATSS_F32_BOXES | EVREP_ATSS_F32_SCORES)) return EVREP_EINVAL;
+    AtssArgs t;
+    memset(&t, 0, sizeof(t));
+    int64_t total = 0;
+    for (int32_t l = 0; l < n_levels; ++l) {
+        if (level_counts[l] < topk || level_counts[l] > A) return EVREP_EINVAL;
+        t.lvl_start[l] = (int32_t)total;                                // <= A: the sum is held to A below
+        t.lvl_n[l] = level_counts[l];
+        total += level_counts[l];
+        if (total > A) return EVREP_EINVAL;
+    }
+    if (total != A) return EVREP_EINVAL;
+    const uintptr_t elem_b = (flags & EVREP_ATSS_F32_BOXES) ? 4 : 8, elem_s = (flags & EVREP_ATSS_F32_SCORES) ? 4 : 8;
+    if (bad_ptr(anchors, 4) || misaligned(pd_bboxes, 4)) return EVREP_EINVAL;
+    if (M > 0 ? bad_ptr(gt, 8) : misaligned(gt, 8)) return EVREP_EINVAL;
+    if (bad_ptr(target_labels, 8) || bad_ptr(target_bboxes, elem_b) || bad_ptr(target_scores, elem_s) || bad_ptr(fg, 1)) return EVREP_EINVAL;
+    if (bad_ptr(status, 4) || bad_ptr(scratch, 256)) return EVREP_EINVAL;
+    t.anchors = anchors; t.pd_bboxes = pd_bboxes; t.gt = gt;
+    t.labels = target_labels; t.boxes = target_bboxes; t.scores = target_scores; t.fg = fg; t.status = status;
+    t.B = B; t.M = M; t.A = A; t.nc = nc; t.topk = topk; t.n_levels = n_levels;
+    t.f32_boxes = (flags & EVREP_ATSS_F32_BOXES) ? 1 : 0;
+    t.f32_scores = (flags & EVREP_ATSS_F32_SCORES) ? 1 : 0;
+    atss_layout(scratch, B, A, &t);
+    hipStream_t stream = as_stream(stream_);
+    int rc = hip_check(hipMemsetAsync(status, 0, (size_t)B * 4u, stream), "hipMemsetAsync(status)");
+    if (rc != EVREP_OK) return rc;
+    const auto spread = [&](size_t work) {                              // workgroups per image: B * G about 2048
+        const size_t need = (work + kThreads - 1) / kThreads, cap = (2048 + (size_t)B - 1) / (size_t)B;
+        return (unsigned)(need < 1 ? 1 : (need < cap ? need : cap));
+    };
+    if (M > 0) {
+        k_atss_prepare<<<dim3(spread((size_t)A * 4u), (unsigned)B), kThreads, 0, stream>>>(t);
+        LAUNCH_CHECK("k_atss_prepare");
+        k_atss_select<<<dim3((unsigned)M, (unsigned)B), kAtssThreads, 0, stream>>>(t);
+        LAUNCH_CHECK("k_atss_select");
+    }
+    k_atss_resolve<<<dim3((unsigned)((A + kThreads - 1) / kThreads), (unsigned)B), kThreads, 0, stream>>>(t);
+    LAUNCH_CHECK("k_atss_resolve");
+    k_atss_scores<<<dim3(spread((size_t)A * nc), (unsigned)B), kThreads, 0, stream>>>(t);
+    LAUNCH_CHECK("k_atss_scores");
     return EVREP_OK;
 }
 

@@ -28,8 +28,8 @@ sigmoid, as the head returns them in training).
    ``x >= 0``, equal ``min`` / ``max`` arguments splitting in halves -- formed in float64 and rounded once to float32.
 7. A foreground anchor whose label lies outside ``[0, nc)`` sets ``ST_BAD_LABEL`` and is background for the class term.
 
-``siou`` / ``ciou`` / ``diou``, the ATSS assigner of the warm-up epochs (a callable may be handed in) and half-precision
-predictions are not mirrored.
+The warm-up epochs (``epoch_num < warmup_epoch``) assign with the ATSS rules of ``detector_assign`` when ``ComputeLoss`` is
+built with ``warmup_assigner="atss"``.  ``siou`` / ``ciou`` / ``diou`` and half-precision predictions are not mirrored.
 """
 import numpy as np
 import torch
@@ -375,10 +375,12 @@ class ComputeLoss:
     """``yolov6.models.losses.loss.ComputeLoss`` with its constructor arguments and call signature:
     ``__call__(outputs, targets, epoch_num, step_num, batch_height, batch_width) -> (loss, loss_items)`` with
     ``outputs = (feats, pred_scores, pred_distri)``.  The sequence is ``decode_boxes`` -> ``assign_batch`` -> ``loss_batch``; the
-    anchors come from the feature shapes and are cached per shape on the device.  ``epoch_num < warmup_epoch`` calls
-    ``warmup_assigner`` -- a callable with the reference's ``ATSSAssigner`` argument list ``(anchors, n_anchors_list, gt_labels,
-    gt_bboxes, mask_gt, pred_bboxes_px)`` returning ``(target_labels, target_bboxes, target_scores, fg_mask)`` -- or raises
-    NotImplementedError when none was given.  ``max_labels`` is as in ``assign_batch`` (needed for CUDA ``targets``).  CPU tensors
+    anchors come from the feature shapes and are cached per shape on the device.  ``epoch_num < warmup_epoch`` assigns with
+    ``warmup_assigner``: ``"atss"`` (the reference's ``ATSSAssigner(9, num_classes)``) or a ``detector_assign.ATSSAssigner`` takes
+    ``atss_assign_batch`` for CUDA predictions, with no host read, and the host route for CPU tensors; any other callable is called
+    with the reference's argument list ``(anchors, n_anchors_list, gt_labels, gt_bboxes, mask_gt, pred_bboxes_px)`` and returns
+    ``(target_labels, target_bboxes, target_scores, fg_mask)``; the default None raises NotImplementedError there.
+    ``max_labels`` is as in ``assign_batch`` (needed for CUDA ``targets``).  CPU tensors
     take the host routes.  No ``empty_cache``, no CPU fall-back for device tensors.  ``last_status`` holds the (B,) status words of
     the last call (assigner | loss)."""
 
@@ -391,6 +393,12 @@ class ComputeLoss:
         self.use_dfl, self.reg_max, self.iou_type = bool(use_dfl), int(reg_max), "giou"
         _reg(self.reg_max, self.use_dfl)
         self.loss_weight = dict(DEFAULT_WEIGHT if loss_weight is None else loss_weight)
+        if isinstance(warmup_assigner, str):
+            if warmup_assigner.lower() != "atss":
+                raise ValueError("warmup_assigner = %r: 'atss', an assigner object or None" % (warmup_assigner,))
+            warmup_assigner = _da.ATSSAssigner(9, num_classes=self.num_classes)
+        if isinstance(warmup_assigner, _da.ATSSAssigner) and warmup_assigner.num_classes != self.num_classes:
+            raise ValueError("the warm-up assigner has %d classes, the loss %d" % (warmup_assigner.num_classes, self.num_classes))
         self.warmup_assigner, self.max_labels = warmup_assigner, max_labels
         self.formal_assigner = _da.TaskAlignedAssigner(topk=13, num_classes=self.num_classes, alpha=1.0, beta=6.0)
         self.last_status = None
@@ -425,15 +433,22 @@ class ComputeLoss:
         _, boxes_px = decode_boxes(pred_distri, anc, stride, self.reg_max, self.use_dfl)
         if epoch_num < self.warmup_epoch:
             if self.warmup_assigner is None:
-                raise NotImplementedError("epoch %d < warmup_epoch %d: the reference assigns with ATSSAssigner there, which is not mirrored; "
-                                          "hand ComputeLoss a warmup_assigner=, or set warmup_epoch=0" % (epoch_num, self.warmup_epoch))
-            gt = _da.preprocess(targets, B, batch_width, batch_height, self.max_labels)
-            if gt.device != dev:
-                gt = gt.to(dev)
-            gt_labels, gt_bboxes = gt[:, :, :1], gt[:, :, 1:]
-            mask_gt = (gt_bboxes.sum(-1, keepdim=True) > 0).float()
-            labels, tb, ts, fg = self.warmup_assigner(anchors, n_anchors_list, gt_labels, gt_bboxes, mask_gt, boxes_px)
-            st_assign = None
+                raise NotImplementedError("epoch %d < warmup_epoch %d: the reference assigns with ATSSAssigner there; build ComputeLoss "
+                                          "with warmup_assigner='atss' for it (or hand it a callable, or set warmup_epoch=0)"
+                                          % (epoch_num, self.warmup_epoch))
+            ours = isinstance(self.warmup_assigner, _da.ATSSAssigner)
+            if ours and pred_scores.is_cuda:
+                labels, tb, ts, fg, st_assign = _da.atss_assign_batch(anchors, n_anchors_list, boxes_px, targets, (batch_height, batch_width),
+                                                                     self.num_classes, max_labels=self.max_labels,
+                                                                     topk=self.warmup_assigner.topk)
+            else:
+                gt = _da.preprocess(targets, B, batch_width, batch_height, self.max_labels)
+                if gt.device != dev:
+                    gt = gt.to(dev)
+                gt_labels, gt_bboxes = gt[:, :, :1], gt[:, :, 1:]
+                mask_gt = (gt_bboxes.sum(-1, keepdim=True) > 0).float()
+                labels, tb, ts, fg = self.warmup_assigner(anchors, n_anchors_list, gt_labels, gt_bboxes, mask_gt, boxes_px)
+                st_assign = self.warmup_assigner.last_status if ours else None
         elif pred_scores.is_cuda:
             labels, tb, ts, fg, st_assign = _da.assign_batch(pred_scores, boxes_px, anc, targets, (batch_height, batch_width),
                                                             self.num_classes, max_labels=self.max_labels)

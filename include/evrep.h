@@ -1034,6 +1034,56 @@ int evrep_tal_assign(const float *pd_scores, const float *pd_bboxes, const float
                      int64_t *target_labels, void *target_bboxes, void *target_scores, uint8_t *fg, uint32_t *status,
                      void *scratch, void *stream);
 
+/* evrep_atss_assign is ATSSAssigner.forward (yolov6/assigners/atss_assigner.py with iou2d_calculator.py and assigner_utils.py),
+ * what ComputeLoss.__call__ assigns with while epoch_num < warmup_epoch (loss.py:84-97), on the gt evrep_det_targets_pad writes,
+ * with no (B, M, A) array in memory.  Every statement below is ONE float64 operation unless a type is named, none fused with
+ * another; float32 inputs are widened exactly; max(a, b) is a > b ? a : b, min(a, b) is a < b ? a : b.
+ *   anchor      the box is float32 (ax1, ay1, ax2, ay2).  area_a = fl32(fl32(ax2 - ax1) * fl32(ay2 - ay1)), unclamped;
+ *               acx = fl32(fl32(ax1 + ax2) / 2f), acy likewise; all three are then widened.  The centre comes from the box.
+ *   row         VALID as for evrep_tal_assign: ((x1 + y1) + x2) + y2 > 0, the class in [0, nc) (else EVREP_TAL_ST_BAD_CLASS and
+ *               the row counts as padding), the image finite.
+ *   overlap     o(m, a) of bbox_overlaps, mode iou: w = max(min(x2, ax2) - max(x1, ax1), 0), h likewise; ov = w * h;
+ *               area_g = (x2 - x1) * (y2 - y1), unclamped; u = max((area_g + area_a) - ov, 1e-6) -- the double 1e-6 --; o = ov / u.
+ *   distance    dx = (x1 + x2) / 2.0 - acx, dy likewise; d = sqrt(dx * dx + dy * dy), correctly rounded.
+ *   candidates  level l holds the anchors [s_l, s_l + level_counts[l]), s_l the sum of the counts before it.  For every valid row
+ *               each level contributes the first `topk` of its anchors in the TOTAL order (d ascending, anchor index ascending):
+ *               equal distances, which the reference's torch.topk leaves open, go to the lower index.
+ *   threshold   over the n = n_levels * topk values v_i = o(m, c_i) in the order (level, place in the level's order):
+ *               mean = (...((v_0 + v_1) + v_2)...) / n; ss = the (v_i - mean) * (v_i - mean) added in the same order;
+ *               thr = mean + sqrt(ss / (n - 1)).  n == 1 gives the reference's NaN: no positives.  (torch adds in another order:
+ *               thr may differ from torch's in its last bits.)
+ *   positive    a candidate with o > thr whose centre (acx, acy) is in-gt, as for evrep_tal_assign (d > 1e-9).
+ *   anchor      c = the rows it is a positive of.  c == 0: background -- target_labels nc, row 0's box, scores zero.  c == 1: that
+ *               row.  c > 1: the FIRST row of greatest o over ALL M rows (select_highest_overlaps, reproduced).  fg = c > 0;
+ *               target_labels of a foreground anchor = long(cls) of the row when that lies in [0, nc), else 0.
+ *   scores      target_scores[b, a, :] is zero but at a foreground anchor's label: fl32(iou) with iou of evrep_tal_assign (the
+ *               row against pd_bboxes[b, a]), or 1 when pd_bboxes is NULL.  The reference holds target_scores in float32.
+ *   shapes      M == 0 is the reference's early return: labels nc, everything else zero, status 0.
+ *   status      EVREP_TAL_ST_BAD_CLASS as above; EVREP_TAL_ST_NONFINITE: an inf or NaN among gt[b] or pd_bboxes[b] -- the whole
+ *               image is written as if it had no valid row.  (anchors must be finite.)
+ *   outputs     target_labels DEVICE int64 [B,A]; target_bboxes [B,A,4] DEVICE double, or float with EVREP_ATSS_F32_BOXES;
+ *               target_scores [B,A,nc] DEVICE double, or float with EVREP_ATSS_F32_SCORES: the same values, rounded once at the
+ *               store (fl32(iou) is stored exactly in either); fg DEVICE uint8 [B,A]; status DEVICE uint32 [B].  Every byte of
+ *               each is written on every call.
+ *   scratch     DEVICE, 256-byte aligned, evrep_atss_workspace_bytes(B, M, A) bytes (0 for a refused shape): per (image, anchor)
+ *               three 32-bit words and one double, each array rounded up to 256 bytes.  Needs no initialisation.
+ * anchors DEVICE float [A,4] xyxy; level_counts HOST int32 [n_levels], read before the call returns; gt DEVICE double [B,M,5]
+ * (NULL allowed when M == 0); pd_bboxes DEVICE float [B,A,4] xyxy or NULL.  1 <= B <= 65535, 0 <= M <= EVREP_TAL_MAX_LABELS,
+ * 1 <= A <= EVREP_TAL_MAX_ANCHORS, 1 <= nc <= EVREP_TAL_MAX_CLASSES, A * nc < 2^31, 1 <= n_levels <= EVREP_ATSS_MAX_LEVELS,
+ * 1 <= topk <= EVREP_ATSS_MAX_TOPK, n_levels * topk <= EVREP_ATSS_MAX_CANDIDATES, topk <= level_counts[l] for every level (the reference itself fails
+ * on a smaller level), the counts add up to A; anything else, an unknown flag, a NULL or misaligned pointer is EVREP_EINVAL
+ * before any launch.  Integer atomics only: two calls give equal bits.  One async memset of status and up to four launches;
+ * does not allocate, does not wait for the device, reads nothing back: the call may be captured into a graph. */
+#define EVREP_ATSS_F32_BOXES 1u
+#define EVREP_ATSS_F32_SCORES 2u
+#define EVREP_ATSS_MAX_TOPK 32
+#define EVREP_ATSS_MAX_LEVELS 8
+#define EVREP_ATSS_MAX_CANDIDATES 256
+size_t evrep_atss_workspace_bytes(int32_t B, int32_t M, int32_t A);
+int evrep_atss_assign(const float *anchors, const int32_t *level_counts, int32_t n_levels, const double *gt, const float *pd_bboxes,
+                      int32_t B, int32_t M, int32_t A, int32_t nc, int32_t topk, uint32_t flags, int64_t *target_labels,
+                      void *target_bboxes, void *target_scores, uint8_t *fg, uint32_t *status, void *scratch, void *stream);
+
 /* The loss terms of ComputeLoss.__call__ (loss.py:176-217: VarifocalLoss, BboxLoss with IOUloss(xyxy, giou, eps = 1e-10) of
  * yolov6/utils/figure_iou.py and _df_loss) and bbox_decode (loss.py:238-244), values AND gradients, for the targets
  * evrep_tal_assign wrote.  Every statement below is ONE float64 operation unless a type is named; float32 inputs are widened
