@@ -136,6 +136,9 @@ SYMBOLS = {
     "evrep_detloss_workspace_bytes": (ctypes.c_size_t, [_i32, _i32, _i32]),
     "evrep_detloss": _st([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f64, _f64, _f64, ctypes.c_uint32, _vp, _vp,
                           _vp, _vp, _vp, _vp]),
+    "evrep_dethead_predict": _st([_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp]),
+    "evrep_dethead_train": _st([_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp]),
+    "evrep_dethead_train_backward": _st([_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
     "evrep_voxel_normalize_scratch_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32]),
     "evrep_voxel_normalize": _st([_vp, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
     "evrep_decode_scratch_bytes": (ctypes.c_size_t, [_i64]),
@@ -189,6 +192,9 @@ ATSS_MAX_TOPK, ATSS_MAX_LEVELS, ATSS_MAX_CANDIDATES = 32, 8, 256
 DETLOSS_USE_DFL, DETLOSS_NO_GRAD, DETLOSS_F32_TARGETS = 1, 2, 4
 DETLOSS_MAX_REG = 32
 DETLOSS_ST_BAD_LABEL = 1
+# evrep_dethead_*: flag, the most levels, the anchors of a staged tile
+DETHEAD_USE_DFL = 1
+DETHEAD_MAX_LEVELS, DETHEAD_TILE = 8, 64
 # evrep_resize_tap_tables: interpolation codes; the columns of an axis descriptor
 TAPS_LINEAR, TAPS_AREA, TAPS_IDENTITY = 0, 1, 2
 TAPS_AXIS_FIELDS = 6
@@ -202,6 +208,17 @@ class DetinFrame(ctypes.Structure):
                 ("nh", ctypes.c_int32), ("nw", ctypes.c_int32), ("T2", ctypes.c_int32),
                 ("row2", ctypes.c_int32), ("col2", ctypes.c_int32), ("wrow2", ctypes.c_int32), ("wcol2", ctypes.c_int32),
                 ("top", ctypes.c_int32), ("left", ctypes.c_int32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_int32)]
+
+
+class DetheadLevel(ctypes.Structure):
+    """evrep_dethead_level: one level of evrep_dethead_predict / evrep_dethead_train."""
+    _fields_ = [("cls", ctypes.c_void_p), ("reg", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+                ("stride", ctypes.c_float)]
+
+
+class DetheadGradLevel(ctypes.Structure):
+    """evrep_dethead_grad_level: one level of evrep_dethead_train_backward."""
+    _fields_ = [("gcls", ctypes.c_void_p), ("greg", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
 
 
 # evrep_dist / evrep_dense_rank_f32: limits

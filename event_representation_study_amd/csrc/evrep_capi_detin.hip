@@ -3,7 +3,8 @@
 // non_max_suppression (evrep_nms.hip), the scoring of its detections against the labels (evrep_deteval.hip), and the training
 // targets, label padding and the task-aligned assigner (evrep_assign.hip) with the ATSS assigner of the warm-up epochs
 // (evrep_atss.hip), and the loss terms with their gradients
-// (evrep_detloss.hip): argument checks and the launches of each entry point.  No plan, no workspace, no allocation, no wait for the device.
+// (evrep_detloss.hip), and the head's decode and tail in front of all of them (evrep_dethead.hip): argument checks and the
+// launches of each entry point.  No plan, no workspace, no allocation, no wait for the device.
 #include <limits.h>
 
 #include "evrep_capi_shared.h"
@@ -13,6 +14,7 @@
 #include "evrep_assign.hip"
 #include "evrep_atss.hip"
 #include "evrep_detloss.hip"
+#include "evrep_dethead.hip"
 
 using namespace evrep;
 using evrep_host::hip_check;
@@ -446,6 +448,85 @@ int evrep_detloss(const float *pred_scores, const float *pred_distri, const floa
     LAUNCH_CHECK("k_detloss_box");
     k_detloss_fold<<<1, kThreads, 0, stream>>>(t);
     LAUNCH_CHECK("k_detloss_fold");
+    return EVREP_OK;
+}
+
+// the shape checks the three evrep_dethead_* entries share; fills the counts of the level table
+static inline bool dethead_shape_ok(int32_t L, int32_t B, int32_t nc, int32_t R, uint32_t flags) {
+    if (L < 1 || L > EVREP_DETHEAD_MAX_LEVELS || B < 1 || B > 65535 || nc < 1 || nc > EVREP_TAL_MAX_CLASSES) return false;
+    if (flags & ~(uint32_t)EVREP_DETHEAD_USE_DFL) return false;
+    return R >= ((flags & EVREP_DETHEAD_USE_DFL) ? 1 : 0) && R <= EVREP_DETLOSS_MAX_REG;
+}
+
+static inline bool dethead_level(DetheadArgs &t, int32_t l, int32_t h, int32_t w, int64_t &total, int64_t &tiles) {
+    if (h < 1 || w < 1 || (int64_t)h * w > EVREP_TAL_MAX_ANCHORS) return false;
+    t.n[l] = h * w; t.w[l] = w; t.off[l] = (int32_t)total; t.tile0[l] = (int32_t)tiles;
+    total += t.n[l];
+    tiles += (t.n[l] + kDetheadTile - 1) / kDetheadTile;
+    return total <= EVREP_TAL_MAX_ANCHORS;
+}
+
+static int dethead_forward(const evrep_dethead_level *lv, int32_t L, int32_t B, int32_t nc, int32_t R, uint32_t flags, float *pred,
+                           float *scores, float *distri, bool train, void *stream_) {
+    if (!dethead_shape_ok(L, B, nc, R, flags) || bad_ptr(lv, 8)) return EVREP_EINVAL;
+    if (train ? (bad_ptr(scores, 4) || bad_ptr(distri, 4)) : bad_ptr(pred, 4)) return EVREP_EINVAL;
+    DetheadArgs t;
+    memset(&t, 0, sizeof(t));
+    int64_t total = 0, tiles = 0;
+    for (int32_t l = 0; l < L; ++l) {
+        if (!dethead_level(t, l, lv[l].h, lv[l].w, total, tiles)) return EVREP_EINVAL;
+        if (bad_ptr(lv[l].cls, 4) || bad_ptr(lv[l].reg, 4)) return EVREP_EINVAL;
+        if (!(lv[l].stride > 0.0f) || !(lv[l].stride - lv[l].stride == 0.0f)) return EVREP_EINVAL;   // NaN, inf, <= 0
+        t.cls[l] = lv[l].cls; t.reg[l] = lv[l].reg; t.stride[l] = lv[l].stride;
+    }
+    t.pred = pred; t.scores = scores; t.distri = distri;
+    t.L = L; t.N = (int32_t)total; t.nc = nc;
+    t.use_dfl = (flags & EVREP_DETHEAD_USE_DFL) ? 1 : 0;
+    t.K = t.use_dfl ? R + 1 : 1;
+    const dim3 grid((unsigned)tiles, (unsigned)B);
+    if (train) {
+        k_dethead_train<<<grid, kThreads, 0, as_stream(stream_)>>>(t);
+        LAUNCH_CHECK("k_dethead_train");
+    } else {
+        k_dethead_predict<<<grid, kThreads, 0, as_stream(stream_)>>>(t);
+        LAUNCH_CHECK("k_dethead_predict");
+    }
+    return EVREP_OK;
+}
+
+int evrep_dethead_predict(const evrep_dethead_level *levels_host, int32_t L, int32_t B, int32_t nc, int32_t R, uint32_t flags,
+                          float *pred, void *stream_) {
+    return dethead_forward(levels_host, L, B, nc, R, flags, pred, nullptr, nullptr, false, stream_);
+}
+
+int evrep_dethead_train(const evrep_dethead_level *levels_host, int32_t L, int32_t B, int32_t nc, int32_t R, uint32_t flags,
+                        float *pred_scores, float *pred_distri, void *stream_) {
+    return dethead_forward(levels_host, L, B, nc, R, flags, nullptr, pred_scores, pred_distri, true, stream_);
+}
+
+int evrep_dethead_train_backward(const evrep_dethead_grad_level *levels_host, int32_t L, int32_t B, int32_t nc, int32_t R,
+                                 uint32_t flags, const float *pred_scores, const float *grad_scores, const float *grad_distri,
+                                 void *stream_) {
+    if (!dethead_shape_ok(L, B, nc, R, flags) || bad_ptr(levels_host, 8)) return EVREP_EINVAL;
+    if (!grad_scores && !grad_distri) return EVREP_EINVAL;             // nothing asked for
+    if (misaligned(grad_scores, 4) || misaligned(grad_distri, 4)) return EVREP_EINVAL;
+    if (grad_scores ? bad_ptr(pred_scores, 4) : misaligned(pred_scores, 4)) return EVREP_EINVAL;
+    DetheadArgs t;
+    memset(&t, 0, sizeof(t));
+    int64_t total = 0, tiles = 0;
+    for (int32_t l = 0; l < L; ++l) {
+        const evrep_dethead_grad_level &g = levels_host[l];
+        if (!dethead_level(t, l, g.h, g.w, total, tiles)) return EVREP_EINVAL;
+        if (grad_scores ? bad_ptr(g.gcls, 4) : g.gcls != nullptr) return EVREP_EINVAL;   // a half comes whole or not at all
+        if (grad_distri ? bad_ptr(g.greg, 4) : g.greg != nullptr) return EVREP_EINVAL;
+        t.gcls[l] = g.gcls; t.greg[l] = g.greg;
+    }
+    t.p = pred_scores; t.gs = grad_scores; t.gd = grad_distri;
+    t.L = L; t.N = (int32_t)total; t.nc = nc;
+    t.use_dfl = (flags & EVREP_DETHEAD_USE_DFL) ? 1 : 0;
+    t.K = t.use_dfl ? R + 1 : 1;
+    k_dethead_backward<<<dim3((unsigned)tiles, (unsigned)B), kThreads, 0, as_stream(stream_)>>>(t);
+    LAUNCH_CHECK("k_dethead_backward");
     return EVREP_OK;
 }
 

@@ -25,6 +25,7 @@
 // nothing read back, no allocation: the launches can be captured into a graph.
 #pragma once
 #include "evrep_common.h"
+#include "evrep_dfl.h"
 
 #pragma clang fp contract(off)
 
@@ -56,8 +57,6 @@ struct DetlossArgs {
     int32_t B, A, nc, R, K, use_dfl, f32_t, grad;
 };
 
-__device__ inline double dl_max(double a, double b) { return a > b ? a : b; }
-__device__ inline double dl_min(double a, double b) { return a < b ? a : b; }
 __device__ inline double dl_target(const void *base, size_t at, int f32_t) {
     return f32_t ? (double)static_cast<const float *>(base)[at] : static_cast<const double *>(base)[at];
 }
@@ -83,23 +82,13 @@ __device__ inline double detloss_fold(const double *__restrict__ part, uint32_t 
     return detloss_block_sum(s, tmp);
 }
 
-// one side of bbox_decode: the K logits at z -> the maximum, the sum of exponentials and the expectation
-__device__ inline void detloss_side(const float *__restrict__ z, int K, double &m, double &Z, double &d) {
-    m = (double)z[0];
-    for (int k = 1; k < K; ++k) m = dl_max(m, (double)z[k]);
-    Z = 0.0;
-    for (int k = 0; k < K; ++k) Z = __dadd_rn(Z, exp(__dsub_rn((double)z[k], m)));
-    d = 0.0;
-    for (int k = 0; k < K; ++k) d = __dadd_rn(d, __dmul_rn(__ddiv_rn(exp(__dsub_rn((double)z[k], m)), Z), (double)k));
-}
-
 // one side e of anchor a: the centre's coordinate in stride units (float32, widened), the side's expectation (the distance itself
 // without DFL) and the box's coordinate; z: the side's K values
 __device__ inline void detloss_coord(const DetlossArgs &t, const float *__restrict__ z, int a, int e, double &c, double &m, double &Z,
                                      double &d, double &v) {
     c = (double)__fdiv_rn(t.anc[(size_t)a * 2u + (size_t)(e & 1)], t.stride[a]);
     if (t.use_dfl) {
-        detloss_side(z, t.K, m, Z, d);
+        dfl_side(z, 1, t.K, m, Z, d);                                    // evrep_dfl.h: one side of bbox_decode
     } else {
         m = 0.0; Z = 1.0; d = (double)z[0];
     }

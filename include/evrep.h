@@ -1140,6 +1140,56 @@ int evrep_detloss(const float *pred_scores, const float *pred_distri, const floa
                   int32_t A, int32_t nc, int32_t R, double w_class, double w_iou, double w_dfl, uint32_t flags, double *losses,
                   float *grad_scores, float *grad_distri, uint32_t *status, void *scratch, void *stream);
 
+/* What Detect.forward does behind its last convolutions (ev-YOLOv6/yolov6/models/effidehead.py:89-173, with
+ * generate_anchors(is_eval = True) and dist2bbox(xywh) behind it): the per-level maps of cls_preds / reg_preds, NCHW as the
+ * convolutions leave them, -> the prediction tensor of evaluation, the two tensors of training, and the maps' gradients.
+ *   levels     L levels l = 0 .. L-1, 1 <= L <= EVREP_DETHEAD_MAX_LEVELS.  Level l has a map of h_l x w_l, n_l = h_l * w_l anchors,
+ *              offset off_l (the sum of the earlier n) and stride s_l (float32).  N = A = sum n_l.
+ *   anchors    anchor a = off_l + i * w_l + j, row-major as flatten(2) orders it; its point is ax = j + 0.5, ay = i + 0.5 (the
+ *              reference's grid_cell_offset, fixed at 0.5), formed in the kernel: no anchor tensor is read.
+ *   inputs     K = R + 1 with EVREP_DETHEAD_USE_DFL, else K = 1.  cls_l float32 [B, nc, h_l, w_l]: the raw logits of cls_preds[l];
+ *              reg_l float32 [B, 4K, h_l, w_l], channel side * K + k -- what reshape([-1, 4, K, n_l]) means, and the last axis of
+ *              pred_distri.
+ * Evaluation (evrep_dethead_predict).  Every statement is ONE float64 operation; inputs are widened exactly; nothing is fused.
+ *   E1         the side distance d_side is the decode rule of evrep_detloss above (m, e_k, Z, pr_k, d added left to right), by
+ *              the same device function (csrc/evrep_dfl.h); without DFL d = z.
+ *   E2         x1 = ax - d_0; y1 = ay - d_1; x2 = ax + d_2; y2 = ay + d_3; cx = (x1 + x2) / 2, cy likewise; w = x2 - x1;
+ *              h = y2 - y1; each of the four is multiplied by s_l, then rounded once to float32 into pred[b, a, 0:4].
+ *   E3         pred[b, a, 4] = 1.0f.
+ *   E4         pred[b, a, 5 + c] = fl32(1 / (1 + exp(-x))) with x = cls_l[b, c, i, j].
+ * Training (evrep_dethead_train).
+ *   T1         pred_scores[b, a, c] is the value of E4.
+ *   T2         pred_distri[b, a, ch] = reg_l[b, ch, i, j], a bit copy.
+ * Backward (evrep_dethead_train_backward): torch's sigmoid_backward on the stored output, in float32, one operation per
+ * statement.
+ *              gcls_l[b, c, i, j] = (g * (1 - p)) * p with g = grad_scores[b, a, c] and p the stored pred_scores[b, a, c];
+ *              greg_l[b, ch, i, j] = grad_distri[b, a, ch], a bit copy.
+ *              grad_scores with all gcls, or grad_distri with all greg, may be NULL together: that half is skipped
+ *              (pred_scores may then be NULL too); both halves NULL is EVREP_EINVAL.
+ * Inputs must be finite: NaN and infinities do not fault, their results are unspecified.  Large finite logits are inside
+ * the contract.
+ * levels_host HOST [L], read before the call returns and passed to the kernel by value; its cls / reg / gcls / greg DEVICE,
+ * 4-byte aligned.  pred DEVICE float [B,N,5+nc]; pred_scores DEVICE float [B,A,nc]; pred_distri DEVICE float [B,A,4K];
+ * grad_scores, grad_distri DEVICE float of the same shapes.  Every element of every output is written on every call.
+ * 1 <= B <= 65535, 1 <= nc <= EVREP_TAL_MAX_CLASSES, 0 <= R <= EVREP_DETLOSS_MAX_REG (1 <= R with EVREP_DETHEAD_USE_DFL),
+ * h, w >= 1, N <= EVREP_TAL_MAX_ANCHORS, stride finite and > 0; anything else, an unknown flag, a NULL required pointer or a
+ * pointer not aligned to 4 bytes is EVREP_EINVAL before any launch.  One launch each: a workgroup stages a tile of
+ * EVREP_DETHEAD_TILE consecutive anchors of one (image, level) in LDS and moves its rows as one contiguous span, 16 bytes per
+ * lane between the span's 16-byte boundaries.  No scratch, no atomics, no allocation, no wait for the device, nothing read
+ * back: the calls may be captured into a graph, and two calls give equal bits. */
+typedef struct { const float *cls; const float *reg; int32_t h, w; float stride; } evrep_dethead_level;
+typedef struct { float *gcls; float *greg; int32_t h, w; } evrep_dethead_grad_level;
+#define EVREP_DETHEAD_USE_DFL 1u
+#define EVREP_DETHEAD_MAX_LEVELS 8
+#define EVREP_DETHEAD_TILE 64
+int evrep_dethead_predict(const evrep_dethead_level *levels_host, int32_t L, int32_t B, int32_t nc, int32_t R, uint32_t flags,
+                          float *pred, void *stream);
+int evrep_dethead_train(const evrep_dethead_level *levels_host, int32_t L, int32_t B, int32_t nc, int32_t R, uint32_t flags,
+                        float *pred_scores, float *pred_distri, void *stream);
+int evrep_dethead_train_backward(const evrep_dethead_grad_level *levels_host, int32_t L, int32_t B, int32_t nc, int32_t R,
+                                 uint32_t flags, const float *pred_scores, const float *grad_scores, const float *grad_distri,
+                                 void *stream);
+
 /* ev-licious' Events.render (ev-licious/src/evlicious/io/utils/render.py:9-141) for B windows of integer coordinates: two calls,
  * one stream builder over the binned records and one streaming launch.  Neither allocates, waits for the device or reads a
  * size on the host: both may be captured into a graph.  Limits: B <= 65535, H * W * 4 < 2^31.
