@@ -139,6 +139,8 @@ SYMBOLS = {
     "evrep_dethead_predict": _st([_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp]),
     "evrep_dethead_train": _st([_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp]),
     "evrep_dethead_train_backward": _st([_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
+    "evrep_train_step": _st([_vp, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _f64, _f64, _i32, ctypes.c_uint32, _vp]),
+    "evrep_ema_update": _st([_vp, _i32, _vp, _i64, _vp, _vp]),
     "evrep_voxel_normalize_scratch_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32]),
     "evrep_voxel_normalize": _st([_vp, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
     "evrep_decode_scratch_bytes": (ctypes.c_size_t, [_i64]),
@@ -195,6 +197,11 @@ DETLOSS_ST_BAD_LABEL = 1
 # evrep_dethead_*: flag, the most levels, the anchors of a staged tile
 DETHEAD_USE_DFL = 1
 DETHEAD_MAX_LEVELS, DETHEAD_TILE = 8, 64
+# evrep_train_step / evrep_ema_update: per-tensor flags, the call's flags, the elements of a chunk, the most groups, the words
+# of the hyper row in front of the groups' (lr, momentum, weight_decay), the words of the scaler's state
+STEP_HAS_GRAD, STEP_HAS_EMA, STEP_EMA_ONLY = 1, 2, 4
+STEP_ZERO_GRAD, STEP_NO_CHECK, STEP_KEEP_SCALE = 1, 2, 4
+STEP_CHUNK, STEP_MAX_GROUPS, STEP_HYPER_EMA, STEP_AMP_WORDS = 4096, 16, 2, 3
 # evrep_resize_tap_tables: interpolation codes; the columns of an axis descriptor
 TAPS_LINEAR, TAPS_AREA, TAPS_IDENTITY = 0, 1, 2
 TAPS_AXIS_FIELDS = 6
@@ -219,6 +226,17 @@ class DetheadLevel(ctypes.Structure):
 class DetheadGradLevel(ctypes.Structure):
     """evrep_dethead_grad_level: one level of evrep_dethead_train_backward."""
     _fields_ = [("gcls", ctypes.c_void_p), ("greg", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
+
+
+class StepTensor(ctypes.Structure):
+    """evrep_step_tensor: one tensor of evrep_train_step / evrep_ema_update."""
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("buf", ctypes.c_void_p), ("ema", ctypes.c_void_p),
+                ("n", ctypes.c_int64), ("group", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+class StepChunk(ctypes.Structure):
+    """evrep_step_chunk: count elements of a tensor from its element `first` on."""
+    _fields_ = [("first", ctypes.c_int64), ("tensor", ctypes.c_int32), ("count", ctypes.c_int32)]
 
 
 # evrep_dist / evrep_dense_rank_f32: limits

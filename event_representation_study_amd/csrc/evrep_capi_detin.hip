@@ -3,8 +3,8 @@
 // non_max_suppression (evrep_nms.hip), the scoring of its detections against the labels (evrep_deteval.hip), and the training
 // targets, label padding and the task-aligned assigner (evrep_assign.hip) with the ATSS assigner of the warm-up epochs
 // (evrep_atss.hip), and the loss terms with their gradients
-// (evrep_detloss.hip), and the head's decode and tail in front of all of them (evrep_dethead.hip): argument checks and the
-// launches of each entry point.  No plan, no workspace, no allocation, no wait for the device.
+// (evrep_detloss.hip), and the head's decode and tail in front of all of them (evrep_dethead.hip), and the parameter update
+// behind the backward pass (evrep_step.hip): argument checks and the launches of each entry point.  No plan, no workspace, no allocation, no wait for the device.
 #include <limits.h>
 
 #include "evrep_capi_shared.h"
@@ -15,6 +15,7 @@
 #include "evrep_atss.hip"
 #include "evrep_detloss.hip"
 #include "evrep_dethead.hip"
+#include "evrep_step.hip"
 
 using namespace evrep;
 using evrep_host::hip_check;
@@ -527,6 +528,57 @@ int evrep_dethead_train_backward(const evrep_dethead_grad_level *levels_host, in
     t.K = t.use_dfl ? R + 1 : 1;
     k_dethead_backward<<<dim3((unsigned)tiles, (unsigned)B), kThreads, 0, as_stream(stream_)>>>(t);
     LAUNCH_CHECK("k_dethead_backward");
+    return EVREP_OK;
+}
+
+static inline bool step_tables_ok(const evrep_step_tensor *tensors, int32_t n_tensors, const evrep_step_chunk *chunks,
+                                  int64_t n_chunks, const float *hyper) {
+    if (n_tensors < 0 || n_chunks < 0 || n_chunks > INT32_MAX || bad_ptr(hyper, 4)) return false;
+    if (n_tensors > 0 ? bad_ptr(tensors, 8) : misaligned(tensors, 8)) return false;
+    if (n_chunks > 0 ? (bad_ptr(chunks, 8) || n_tensors < 1) : misaligned(chunks, 8)) return false;
+    return true;
+}
+
+int evrep_train_step(const evrep_step_tensor *tensors, int32_t n_tensors, const evrep_step_chunk *chunks, int64_t n_chunks,
+                     const float *hyper, int32_t n_groups, int32_t *amp, int32_t *applied_steps, double growth, double backoff,
+                     int32_t growth_interval, uint32_t flags, void *stream_) {
+    if (!step_tables_ok(tensors, n_tensors, chunks, n_chunks, hyper)) return EVREP_EINVAL;
+    if (n_groups < 1 || n_groups > EVREP_STEP_MAX_GROUPS) return EVREP_EINVAL;
+    if (flags & ~(uint32_t)(EVREP_STEP_ZERO_GRAD | EVREP_STEP_NO_CHECK | EVREP_STEP_KEEP_SCALE)) return EVREP_EINVAL;
+    if (misaligned(amp, 4) || bad_ptr(applied_steps, 4)) return EVREP_EINVAL;
+    if (amp && !(flags & EVREP_STEP_KEEP_SCALE)) {
+        const auto factor = [](double v) { return v > 0.0 && v - v == 0.0; };   // finite and > 0 (NaN fails)
+        if (!factor(growth) || !factor(backoff) || growth_interval < 1) return EVREP_EINVAL;
+    }
+    StepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.tensors = tensors; a.chunks = chunks; a.hyper = hyper; a.amp = amp; a.applied = applied_steps;
+    a.growth = growth; a.backoff = backoff; a.interval = growth_interval;
+    a.n_tensors = n_tensors; a.n_groups = n_groups; a.flags = flags;
+    hipStream_t stream = as_stream(stream_);
+    if (n_chunks > 0 && amp && !(flags & EVREP_STEP_NO_CHECK)) {
+        k_step_check<<<(unsigned)n_chunks, kThreads, 0, stream>>>(a);
+        LAUNCH_CHECK("k_step_check");
+    }
+    if (n_chunks > 0) {
+        k_step_apply<<<(unsigned)n_chunks, kThreads, 0, stream>>>(a);
+        LAUNCH_CHECK("k_step_apply");
+    }
+    k_step_finish<<<1, kWave, 0, stream>>>(a);
+    LAUNCH_CHECK("k_step_finish");
+    return EVREP_OK;
+}
+
+int evrep_ema_update(const evrep_step_tensor *tensors, int32_t n_tensors, const evrep_step_chunk *chunks, int64_t n_chunks,
+                     const float *hyper, void *stream_) {
+    if (!step_tables_ok(tensors, n_tensors, chunks, n_chunks, hyper)) return EVREP_EINVAL;
+    if (n_chunks == 0) return EVREP_OK;
+    StepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.tensors = tensors; a.chunks = chunks; a.hyper = hyper;
+    a.n_tensors = n_tensors; a.ema_only = 1;
+    k_step_apply<<<(unsigned)n_chunks, kThreads, 0, as_stream(stream_)>>>(a);
+    LAUNCH_CHECK("k_step_apply");
     return EVREP_OK;
 }
 

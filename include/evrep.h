@@ -1190,6 +1190,74 @@ int evrep_dethead_train_backward(const evrep_dethead_grad_level *levels_host, in
                                  uint32_t flags, const float *pred_scores, const float *grad_scores, const float *grad_distri,
                                  void *stream);
 
+/* What is left of the training step behind loss.backward() (ev-YOLOv6/yolov6/core/engine.py:547-552): scaler.step(optimizer)
+ * with torch's Nesterov SGD behind it (solver/build.py), scaler.update() and ModelEMA.update(model) (yolov6/utils/ema.py:30-41),
+ * for all tensors of a model at once.  float32 parameters and gradients only.
+ *   tensors    DEVICE [n_tensors] evrep_step_tensor, 8-byte aligned: p the parameter (or, with EVREP_STEP_EMA_ONLY, the model's
+ *              entry of a buffer such as BN running statistics, which is only read), g its gradient, buf its momentum buffer, ema
+ *              the EMA model's entry, all DEVICE float [n], 4-byte aligned; n >= 0, and a tensor of 0 elements has no chunk;
+ *              group its row of the hyper row; flags: EVREP_STEP_HAS_GRAD (g is given and the tensor is stepped; buf is given
+ *              too unless the group's momentum is 0 on every call that uses the table), EVREP_STEP_HAS_EMA (ema is given),
+ *              EVREP_STEP_EMA_ONLY (p is read, only ema is written; g and buf are ignored).  A pointer its flags do not ask
+ *              for may be NULL.  The arrays of different tensors, and the four of one tensor, do not overlap.
+ *   chunks     DEVICE [n_chunks] evrep_step_chunk, 8-byte aligned: elements [first, first + count) of tensor `tensor`,
+ *              1 <= count <= EVREP_STEP_CHUNK; every element of every tensor lies in exactly one chunk.  One workgroup per chunk.
+ *   hyper      DEVICE float [EVREP_STEP_HYPER_EMA + 3 * n_groups]: ema_d = fl32(decay), ema_1md = fl32(1 - decay) with the
+ *              subtraction in double, then per group lr, momentum, weight_decay, each rounded to float32 once.
+ *   amp        DEVICE int32 [EVREP_STEP_AMP_WORDS] or NULL (no scaler): found_inf (0 between calls), scale (the bits of a
+ *              float32), growth_tracker.
+ *   applied    DEVICE int32 [1]: applied_steps, the steps that were not skipped.
+ * evrep_train_step is three launches, ordered by the stream:
+ *   check      (with amp, without EVREP_STEP_NO_CHECK) found_inf = 1 if any element of any g with HAS_GRAD is NaN or an infinity:
+ *              the scaled gradient as stored, what _amp_foreach_non_finite_check_and_unscale_ tests.  An integer atomic.
+ *   apply      per element, every statement ONE float32 operation, rounded on its own, in this order:
+ *                inv = fl32(1 / double(scale)); 1 without amp
+ *                if found_inf == 0 and HAS_GRAD:
+ *                  g' = g * inv
+ *                  d  = weight_decay != 0 ? g' + weight_decay * p : g'
+ *                  momentum != 0:  buf = applied_steps == 0 ? d : buf * momentum + d;   d2 = d + momentum * buf
+ *                  momentum == 0:  d2 = d, buf is neither read nor written
+ *                  p  = p + (-lr) * d2
+ *                if HAS_EMA:  e = e * ema_d;  e = e + ema_1md * p      (p the value just written; also when the step was skipped)
+ *                with EVREP_STEP_ZERO_GRAD and HAS_GRAD:  g = +0.0     (also when the step was skipped)
+ *              On the first applied step buf is not read: it may be uninitialised, as torch leaves it absent.  A first step that
+ *              was skipped leaves it so.  (A buffer of -0.0 is the same as an absent one: -0.0 * momentum + d == d bit for bit.)
+ *   finish     one thread.  With amp and without EVREP_STEP_KEEP_SCALE, _amp_update_scale_'s automaton: found_inf != 0:
+ *              scale = fl32(double(scale) * backoff), tracker = 0; else s = tracker + 1; s == growth_interval:
+ *              scale = fl32(double(scale) * growth) if that is finite, tracker = 0; else tracker = s.
+ *              Then applied_steps += (found_inf == 0) and found_inf = 0.
+ *   EVREP_STEP_NO_CHECK with EVREP_STEP_KEEP_SCALE is the route of a foreign scaler that has made its own check: the caller
+ *   writes found_inf and scale into amp before the call and keeps updating the scale itself.
+ * evrep_ema_update is the apply launch with every tensor taken as EVREP_STEP_EMA_ONLY: only hyper[0], hyper[1], p and ema are
+ * read and only ema is written.
+ * The aligned body of a chunk moves 16 bytes per lane, with 4-byte accesses for the 0..3 elements in front of p's 16-byte
+ * boundary and behind the last whole group; an array that does not share p's offset from a 16-byte boundary moves in 4-byte
+ * accesses.  No access lies outside [first, first + count) of any array.  The tables are the caller's statement: a chunk that
+ * does not fit its tensor, a group >= n_groups, or a momentum != 0 for a tensor without buf is skipped whole and nothing else
+ * is checked on the device.
+ * 0 <= n_tensors, 0 <= n_chunks < 2^31 (0: no apply launch), 1 <= n_groups <= EVREP_STEP_MAX_GROUPS; with amp and without
+ * EVREP_STEP_KEEP_SCALE growth and backoff finite and > 0 and growth_interval >= 1; anything else, an unknown flag, a NULL
+ * required pointer or a misaligned one is EVREP_EINVAL before any launch.  No scratch, no floating-point atomic, no grid-wide
+ * barrier, no allocation, no wait for the device, nothing read back: the calls may be captured into a graph, and two calls
+ * give equal bits. */
+typedef struct { float *p; float *g; float *buf; float *ema; int64_t n; int32_t group; uint32_t flags; } evrep_step_tensor;
+typedef struct { int64_t first; int32_t tensor; int32_t count; } evrep_step_chunk;
+#define EVREP_STEP_HAS_GRAD 1u
+#define EVREP_STEP_HAS_EMA 2u
+#define EVREP_STEP_EMA_ONLY 4u
+#define EVREP_STEP_ZERO_GRAD 1u
+#define EVREP_STEP_NO_CHECK 2u
+#define EVREP_STEP_KEEP_SCALE 4u
+#define EVREP_STEP_CHUNK 4096
+#define EVREP_STEP_MAX_GROUPS 16
+#define EVREP_STEP_HYPER_EMA 2
+#define EVREP_STEP_AMP_WORDS 3
+int evrep_train_step(const evrep_step_tensor *tensors, int32_t n_tensors, const evrep_step_chunk *chunks, int64_t n_chunks,
+                     const float *hyper, int32_t n_groups, int32_t *amp, int32_t *applied_steps, double growth, double backoff,
+                     int32_t growth_interval, uint32_t flags, void *stream);
+int evrep_ema_update(const evrep_step_tensor *tensors, int32_t n_tensors, const evrep_step_chunk *chunks, int64_t n_chunks,
+                     const float *hyper, void *stream);
+
 /* ev-licious' Events.render (ev-licious/src/evlicious/io/utils/render.py:9-141) for B windows of integer coordinates: two calls,
  * one stream builder over the binned records and one streaming launch.  Neither allocates, waits for the device or reads a
  * size on the host: both may be captured into a graph.  Limits: B <= 65535, H * W * 4 < 2^31.
