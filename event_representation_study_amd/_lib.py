@@ -136,6 +136,11 @@ SYMBOLS = {
     "evrep_detloss_workspace_bytes": (ctypes.c_size_t, [_i32, _i32, _i32]),
     "evrep_detloss": _st([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f64, _f64, _f64, ctypes.c_uint32, _vp, _vp,
                           _vp, _vp, _vp, _vp]),
+    "evrep_detloss_distill_workspace_bytes": (ctypes.c_size_t, [_i32, _i32, _i32]),
+    "evrep_detloss_distill": _st([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f64, _f64, _f64, _f64, _f64,
+                                  _f64, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "evrep_detloss_cwd_workspace_bytes": (ctypes.c_size_t, [_vp, _i32]),
+    "evrep_detloss_cwd": _st([_vp, _i32, _f64, ctypes.c_uint32, _vp, _vp, _vp]),
     "evrep_dethead_predict": _st([_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp]),
     "evrep_dethead_train": _st([_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp]),
     "evrep_dethead_train_backward": _st([_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
@@ -194,6 +199,9 @@ ATSS_MAX_TOPK, ATSS_MAX_LEVELS, ATSS_MAX_CANDIDATES = 32, 8, 256
 DETLOSS_USE_DFL, DETLOSS_NO_GRAD, DETLOSS_F32_TARGETS = 1, 2, 4
 DETLOSS_MAX_REG = 32
 DETLOSS_ST_BAD_LABEL = 1
+# evrep_detloss_distill: the most classes; evrep_detloss_cwd: the most levels, the longest row that is staged in LDS
+DISTILL_MAX_CLASSES = 2048
+CWD_MAX_LEVELS, CWD_STAGE = 3, 4096
 # evrep_dethead_*: flag, the most levels, the anchors of a staged tile
 DETHEAD_USE_DFL = 1
 DETHEAD_MAX_LEVELS, DETHEAD_TILE = 8, 64
@@ -221,6 +229,12 @@ class DetheadLevel(ctypes.Structure):
     """evrep_dethead_level: one level of evrep_dethead_predict / evrep_dethead_train."""
     _fields_ = [("cls", ctypes.c_void_p), ("reg", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
                 ("stride", ctypes.c_float)]
+
+
+class CwdLevel(ctypes.Structure):
+    """evrep_cwd_level: one level of evrep_detloss_cwd."""
+    _fields_ = [("s", ctypes.c_void_p), ("t", ctypes.c_void_p), ("grad_s", ctypes.c_void_p), ("n", ctypes.c_int32), ("c", ctypes.c_int32),
+                ("h", ctypes.c_int32), ("w", ctypes.c_int32)]
 
 
 class DetheadGradLevel(ctypes.Structure):

@@ -14,6 +14,7 @@
 #include "evrep_assign.hip"
 #include "evrep_atss.hip"
 #include "evrep_detloss.hip"
+#include "evrep_detdistill.hip"
 #include "evrep_dethead.hip"
 #include "evrep_step.hip"
 
@@ -441,14 +442,142 @@ int evrep_detloss(const float *pred_scores, const float *pred_distri, const floa
     hipStream_t stream = as_stream(stream_);
     int rc = hip_check(hipMemsetAsync(status, 0, (size_t)B * 4u, stream), "hipMemsetAsync(status)");
     if (rc != EVREP_OK) return rc;
-    k_detloss_rows<<<t.n_tss, kThreads, 0, stream>>>(t);
+    k_detloss_rows<false><<<t.n_tss, kThreads, 0, stream>>>(t);
     LAUNCH_CHECK("k_detloss_rows");
     k_detloss_cls<<<dim3(detloss_gc(B, A, nc), (unsigned)B), kThreads, 0, stream>>>(t);
     LAUNCH_CHECK("k_detloss_cls");
-    k_detloss_box<<<dim3(detloss_ga(A), (unsigned)B), kThreads, 0, stream>>>(t);
+    k_detloss_box<false><<<dim3(detloss_ga(A), (unsigned)B), kThreads, 0, stream>>>(t);
     LAUNCH_CHECK("k_detloss_box");
-    k_detloss_fold<<<1, kThreads, 0, stream>>>(t);
+    k_detloss_fold<false><<<1, kThreads, 0, stream>>>(t);
     LAUNCH_CHECK("k_detloss_fold");
+    return EVREP_OK;
+}
+
+// workgroups per image of the distilled class term: a tile of whole rows each, dealt round robin
+static inline uint32_t detdistill_gd(int32_t B, int32_t A, int32_t nc) {
+    const size_t rt = (size_t)distill_tile_rows(nc), need = ((size_t)A + rt - 1) / rt, cap = (2048 + (size_t)B - 1) / (size_t)B;
+    return (uint32_t)(need < cap ? need : cap);
+}
+
+// the scratch of evrep_detloss_distill: the rows' sums, three arrays per slice of the rows launch, two per workgroup of the
+// class launch, four per workgroup of the box launch
+static size_t detdistill_layout(void *scratch, int32_t B, int32_t A, int32_t nc, DetlossArgs *t) {
+    Carver c(scratch);
+    const size_t n_tss = detloss_n_tss(B, A), n_cls = (size_t)B * detdistill_gd(B, A, nc), n_box = (size_t)B * detloss_ga(A);
+    double *w = c.take<double>((size_t)B * (size_t)A * 8);
+    double *tss_part = c.take<double>(n_tss * 8);
+    double *wfg_part = c.take<double>(n_tss * 8);
+    double *nfg_part = c.take<double>(n_tss * 8);
+    double *cls_part = c.take<double>(n_cls * 8);
+    double *dcls_part = c.take<double>(n_cls * 8);
+    double *iou_part = c.take<double>(n_box * 8);
+    double *dfl_part = c.take<double>(n_box * 8);
+    double *cnt_part = c.take<double>(n_box * 8);
+    double *ddfl_part = c.take<double>(n_box * 8);
+    if (t) {
+        t->w = w; t->tss_part = tss_part; t->wfg_part = wfg_part; t->nfg_part = nfg_part; t->cls_part = cls_part; t->dcls_part = dcls_part;
+        t->iou_part = iou_part; t->dfl_part = dfl_part; t->cnt_part = cnt_part; t->ddfl_part = ddfl_part;
+        t->n_tss = (uint32_t)n_tss; t->n_cls = (uint32_t)n_cls; t->n_box = (uint32_t)n_box;
+    }
+    return c.off;
+}
+
+size_t evrep_detloss_distill_workspace_bytes(int32_t B, int32_t A, int32_t nc) {
+    return detloss_shape_ok(B, A, nc) && nc <= EVREP_DISTILL_MAX_CLASSES ? detdistill_layout(nullptr, B, A, nc, nullptr) : 0;
+}
+
+int evrep_detloss_distill(const float *pred_scores, const float *pred_distri, const float *t_pred_scores, const float *t_pred_distri,
+                          const float *anc_points, const float *stride, const int64_t *target_labels, const void *target_bboxes,
+                          const void *target_scores, const uint8_t *fg, int32_t B, int32_t A, int32_t nc, int32_t R, double w_class,
+                          double w_iou, double w_dfl, double temperature, double k_class, double k_dfl, uint32_t flags, double *losses,
+                          float *grad_scores, float *grad_distri, uint32_t *status, void *scratch, void *stream_) {
+    if (!detloss_shape_ok(B, A, nc) || nc > EVREP_DISTILL_MAX_CLASSES) return EVREP_EINVAL;
+    if ((flags & ~(uint32_t)(EVREP_DETLOSS_USE_DFL | EVREP_DETLOSS_NO_GRAD | EVREP_DETLOSS_F32_TARGETS)) || !detloss_r_ok(R, flags))
+        return EVREP_EINVAL;
+    if (!(temperature > 0.0) || !(temperature - temperature == 0.0)) return EVREP_EINVAL;   // NaN, inf, <= 0
+    const uintptr_t elem = (flags & EVREP_DETLOSS_F32_TARGETS) ? 4 : 8;
+    const bool grad = !(flags & EVREP_DETLOSS_NO_GRAD);
+    if (bad_ptr(pred_scores, 4) || bad_ptr(pred_distri, 4) || bad_ptr(t_pred_scores, 4) || bad_ptr(t_pred_distri, 4)) return EVREP_EINVAL;
+    if (bad_ptr(anc_points, 4) || bad_ptr(stride, 4)) return EVREP_EINVAL;
+    if (bad_ptr(target_labels, 8) || bad_ptr(target_bboxes, elem) || bad_ptr(target_scores, elem) || bad_ptr(fg, 1)) return EVREP_EINVAL;
+    if (grad ? (bad_ptr(grad_scores, 4) || bad_ptr(grad_distri, 4)) : (misaligned(grad_scores, 4) || misaligned(grad_distri, 4)))
+        return EVREP_EINVAL;
+    if (bad_ptr(losses, 8) || bad_ptr(status, 4) || bad_ptr(scratch, 256)) return EVREP_EINVAL;
+    DetlossArgs t;
+    memset(&t, 0, sizeof(t));
+    t.p = pred_scores; t.z = pred_distri; t.tp = t_pred_scores; t.tz = t_pred_distri; t.anc = anc_points; t.stride = stride;
+    t.labels = target_labels; t.tb = target_bboxes; t.ts = target_scores; t.fg = fg;
+    t.losses = losses; t.gs = grad ? grad_scores : nullptr; t.gz = grad ? grad_distri : nullptr; t.status = status;
+    t.wc = w_class; t.wi = w_iou; t.wd = w_dfl;
+    t.T = temperature; t.k_class = k_class; t.k_dfl = k_dfl;
+    t.B = B; t.A = A; t.nc = nc; t.R = R;
+    t.use_dfl = (flags & EVREP_DETLOSS_USE_DFL) ? 1 : 0;
+    t.K = t.use_dfl ? R + 1 : 1;
+    t.f32_t = (flags & EVREP_DETLOSS_F32_TARGETS) ? 1 : 0;
+    t.grad = grad ? 1 : 0;
+    detdistill_layout(scratch, B, A, nc, &t);
+    hipStream_t stream = as_stream(stream_);
+    int rc = hip_check(hipMemsetAsync(status, 0, (size_t)B * 4u, stream), "hipMemsetAsync(status)");
+    if (rc != EVREP_OK) return rc;
+    k_detloss_rows<true><<<t.n_tss, kThreads, 0, stream>>>(t);
+    LAUNCH_CHECK("k_detloss_rows<distill>");
+    k_detdistill_cls<<<dim3(detdistill_gd(B, A, nc), (unsigned)B), kThreads, 0, stream>>>(t);
+    LAUNCH_CHECK("k_detdistill_cls");
+    k_detloss_box<true><<<dim3(detloss_ga(A), (unsigned)B), kThreads, 0, stream>>>(t);
+    LAUNCH_CHECK("k_detloss_box<distill>");
+    k_detloss_fold<true><<<1, kThreads, 0, stream>>>(t);
+    LAUNCH_CHECK("k_detloss_fold<distill>");
+    return EVREP_OK;
+}
+
+// the levels of evrep_detloss_cwd: counts, offsets and scales; false for a refused table
+static bool cwd_levels(const evrep_cwd_level *lv, int32_t L, double tau, bool grad, CwdArgs *t, int64_t *rows_out) {
+    if (L < 1 || L > EVREP_CWD_MAX_LEVELS || bad_ptr(lv, 8)) return false;
+    int64_t rows = 0;
+    for (int32_t l = 0; l < L; ++l) {
+        const evrep_cwd_level &v = lv[l];
+        if (v.n < 1 || v.c < 1 || v.h < 1 || v.w < 1) return false;
+        if ((int64_t)v.n * v.c > EVREP_TAL_MAX_ANCHORS || (int64_t)v.h * v.w > EVREP_TAL_MAX_ANCHORS) return false;
+        if (t) {
+            if (bad_ptr(v.s, 4) || bad_ptr(v.t, 4) || (grad ? bad_ptr(v.grad_s, 4) : misaligned(v.grad_s, 4))) return false;
+            const double nc = (double)((int64_t)v.n * v.c);
+            t->s[l] = v.s; t->t[l] = v.t; t->g[l] = grad ? v.grad_s : nullptr;
+            t->hw[l] = v.h * v.w; t->rows[l] = v.n * v.c; t->row0[l] = (int32_t)rows;
+            t->gscale[l] = tau / nc;
+            t->lscale[l] = (tau * tau) / nc;
+        }
+        rows += (int64_t)v.n * v.c;
+    }
+    if (rows > EVREP_TAL_MAX_ANCHORS) return false;
+    *rows_out = rows;
+    return true;
+}
+
+size_t evrep_detloss_cwd_workspace_bytes(const evrep_cwd_level *levels_host, int32_t L) {
+    int64_t rows = 0;
+    if (!cwd_levels(levels_host, L, 1.0, false, nullptr, &rows)) return 0;
+    Carver c(nullptr);
+    c.take<double>((size_t)rows * 8);
+    return c.off;
+}
+
+int evrep_detloss_cwd(const evrep_cwd_level *levels_host, int32_t L, double tau, uint32_t flags, double *out, void *scratch,
+                      void *stream_) {
+    if (flags & ~(uint32_t)EVREP_DETLOSS_NO_GRAD) return EVREP_EINVAL;
+    if (!(tau > 0.0) || !(tau - tau == 0.0)) return EVREP_EINVAL;
+    if (bad_ptr(out, 8) || bad_ptr(scratch, 256)) return EVREP_EINVAL;
+    CwdArgs t;
+    memset(&t, 0, sizeof(t));
+    int64_t rows = 0;
+    if (!cwd_levels(levels_host, L, tau, !(flags & EVREP_DETLOSS_NO_GRAD), &t, &rows)) return EVREP_EINVAL;
+    Carver c(scratch);
+    t.part = c.take<double>((size_t)rows * 8);
+    t.out = out; t.tau = tau; t.L = L;
+    hipStream_t stream = as_stream(stream_);
+    k_detdistill_cw<<<(unsigned)rows, kThreads, 0, stream>>>(t);
+    LAUNCH_CHECK("k_detdistill_cw");
+    k_detdistill_cw_fold<<<1, kThreads, 0, stream>>>(t);
+    LAUNCH_CHECK("k_detdistill_cw_fold");
     return EVREP_OK;
 }
 

@@ -23,9 +23,15 @@
 // Every loop ends at a value the host passed; every index is below the size the host stated (the DFL bin of a target is held
 // to [0, R - 1] whatever the inputs).  Plain C++ stores, one integer atomicOr for the status word, no floating-point atomic,
 // nothing read back, no allocation: the launches can be captured into a graph.
+//
+// evrep_detloss_distill (loss_distill.py) runs the rows, box and fold kernels as their <true> instances: the rows launch also
+// leaves W (the w of the foreground anchors) and their count per slice, norm is tss > 0 ? tss : 1, and a foreground side adds
+// its distillation term and gradient (evrep_kd.h).  The <false> instances are evrep_detloss, bit for bit what they were; the
+// class launch of the distillation entry is k_detdistill_cls (evrep_detdistill.hip), which shares detloss_vfl.
 #pragma once
 #include "evrep_common.h"
 #include "evrep_dfl.h"
+#include "evrep_kd.h"
 
 #pragma clang fp contract(off)
 
@@ -55,7 +61,19 @@ struct DetlossArgs {
     double wc, wi, wd;
     uint32_t n_tss, n_cls, n_box;
     int32_t B, A, nc, R, K, use_dfl, f32_t, grad;
+    // evrep_detloss_distill only
+    const float *tp, *tz;         // the teacher's (B, A, nc) pred_scores and (B, A, 4K) pred_distri
+    double *wfg_part, *nfg_part;  // scratch [n_tss]: the w and the count of the foreground anchors per slice
+    double *dcls_part;            // scratch [n_cls]
+    double *ddfl_part;            // scratch [n_box]
+    double T, k_class, k_dfl;     // temperature, decay * distill_weight["class"], decay * distill_weight["dfl"]
 };
+
+// loss.py divides by tss where it exceeds 1, loss_distill.py where it exceeds 0 (:225, :426, :449; target scores are >= 0)
+template <bool D>
+__device__ inline double detloss_norm(double tss) {
+    return D ? (tss > 0.0 ? tss : 1.0) : (tss > 1.0 ? tss : 1.0);
+}
 
 __device__ inline double dl_target(const void *base, size_t at, int f32_t) {
     return f32_t ? (double)static_cast<const float *>(base)[at] : static_cast<const double *>(base)[at];
@@ -111,22 +129,49 @@ __global__ __launch_bounds__(kThreads) void k_detloss_decode(const DetlossArgs t
 
 // ---------------------------------------------------------------------------------------------------------------------- rows
 // grid (n_tss), 256 threads: chunk c of 256 (image, anchor) pairs belongs to slice c % n_tss
+template <bool D>
 __global__ __launch_bounds__(kThreads) void k_detloss_rows(const DetlossArgs t) {
     __shared__ double tmp[kWaves];
     const size_t n = (size_t)t.B * (size_t)t.A, step = (size_t)gridDim.x * kThreads;
-    double s = 0.0;
+    double s = 0.0, sw = 0.0, sn = 0.0;
     for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += step) {
         const size_t at = i * (size_t)t.nc;
         double w = 0.0;
         for (int c = 0; c < t.nc; ++c) w = __dadd_rn(w, dl_target(t.ts, at + c, t.f32_t));
         t.w[i] = w;
         s = __dadd_rn(s, w);
+        if (D && t.fg[i] != 0) {
+            sw = __dadd_rn(sw, w);
+            sn = __dadd_rn(sn, 1.0);
+        }
     }
     const double tot = detloss_block_sum(s, tmp);
     if (threadIdx.x == 0) t.tss_part[blockIdx.x] = tot;
+    if (D) {                                                           // before the box launch: every foreground gradient needs both
+        const double tw = detloss_block_sum(sw, tmp), tn = detloss_block_sum(sn, tmp);
+        if (threadIdx.x == 0) {
+            t.wfg_part[blockIdx.x] = tw;
+            t.nfg_part[blockIdx.x] = tn;
+        }
+    }
 }
 
 // ----------------------------------------------------------------------------------------------------------------- class term
+// one element of VarifocalLoss: the term bce * wt and, with grad, d term / d p
+__device__ inline void detloss_vfl(double p, double q, bool lab, bool grad, double &term, double &g) {
+    const double wt = lab ? q : __dmul_rn(__dmul_rn(0.75, p), p);
+    const double omp = __dsub_rn(1.0, p);
+    const double lp = dl_max(log(p), -100.0), lq = dl_max(log(omp), -100.0);
+    const double bce = -__dadd_rn(__dmul_rn(q, lp), __dmul_rn(__dsub_rn(1.0, q), lq));
+    term = __dmul_rn(bce, wt);
+    g = 0.0;
+    if (grad) {
+        const double db = __ddiv_rn(__dsub_rn(p, q), dl_max(__dmul_rn(omp, p), kBceEps));
+        g = __dmul_rn(db, wt);
+        if (!lab) g = __dadd_rn(g, __dmul_rn(bce, __dmul_rn(1.5, p)));
+    }
+}
+
 // grid (Gc, B), 256 threads: a lane per element of the image's (A, nc) scores
 __global__ __launch_bounds__(kThreads) void k_detloss_cls(const DetlossArgs t) {
     __shared__ double tmp[kWaves];
@@ -141,17 +186,10 @@ __global__ __launch_bounds__(kThreads) void k_detloss_cls(const DetlossArgs t) {
         const size_t ba = (size_t)b * t.A + a, at = (size_t)b * n + e;
         const double p = (double)t.p[at], q = dl_target(t.ts, at, t.f32_t);
         const bool lab = t.fg[ba] != 0 && t.labels[ba] == (int64_t)c;
-        const double wt = lab ? q : __dmul_rn(__dmul_rn(0.75, p), p);
-        const double omp = __dsub_rn(1.0, p);
-        const double lp = dl_max(log(p), -100.0), lq = dl_max(log(omp), -100.0);
-        const double bce = -__dadd_rn(__dmul_rn(q, lp), __dmul_rn(__dsub_rn(1.0, q), lq));
-        s = __dadd_rn(s, __dmul_rn(bce, wt));
-        if (t.grad) {
-            const double db = __ddiv_rn(__dsub_rn(p, q), dl_max(__dmul_rn(omp, p), kBceEps));
-            double g = __dmul_rn(db, wt);
-            if (!lab) g = __dadd_rn(g, __dmul_rn(bce, __dmul_rn(1.5, p)));
-            t.gs[at] = (float)__dmul_rn(sc, g);
-        }
+        double term, g;
+        detloss_vfl(p, q, lab, t.grad != 0, term, g);
+        s = __dadd_rn(s, term);
+        if (t.grad) t.gs[at] = (float)__dmul_rn(sc, g);
     }
     const double tot = detloss_block_sum(s, tmp);
     if (threadIdx.x == 0) t.cls_part[(size_t)b * gridDim.x + blockIdx.x] = tot;
@@ -167,15 +205,23 @@ __device__ inline double dl_quad(double v, int lane) { return __shfl(v, lane, 64
 // anchors and walks them in four rounds of 64, FOUR LANES PER ANCHOR, one per side: the K logits of neighbouring lanes adjoin in
 // memory and a foreground anchor's chain of exponentials is a quarter as long.  The four lanes exchange their coordinates and
 // side terms by shuffles that every lane executes, then each forms the anchor's GIoU terms itself (the same bits in all four).
+// <true>: a foreground side also forms the softmaxes of its own and the teacher's K logits at temperature T, its row of the
+// distillation sum, and adds cdd * (ps_k * sum(pt) - pt_k) to its gradients before the one store.
+template <bool D>
 __global__ __launch_bounds__(kThreads) void k_detloss_box(const DetlossArgs t) {
     __shared__ double tmp[kWaves];
     __shared__ uint8_t s_fg[kThreads];
     const int b = blockIdx.y, tid = threadIdx.x, e = tid & 3, a0 = blockIdx.x * kThreads, A = t.A, K = t.K;
     const int quad = (tid & 63) & ~3;                                   // the wave's lane of the anchor's side 0
     const double tss = detloss_fold(t.tss_part, t.n_tss, tmp);
-    const double norm = tss > 1.0 ? tss : 1.0;
+    const double norm = detloss_norm<D>(tss);
     const double eps = 1e-10;
-    double l_iou = 0.0, l_dfl = 0.0, n_fg = 0.0;
+    double l_iou = 0.0, l_dfl = 0.0, n_fg = 0.0, l_dd = 0.0, cdd = 0.0;
+    if (D && t.use_dfl && t.grad) {                                    // the same additions in the same order in every workgroup
+        const double W = detloss_fold(t.wfg_part, t.n_tss, tmp), nf = detloss_fold(t.nfg_part, t.n_tss, tmp);
+        if (nf > 0.0)
+            cdd = __ddiv_rn(__ddiv_rn(__dmul_rn(__dmul_rn(__dmul_rn(t.wd, t.k_dfl), t.T), W), norm), __dmul_rn(4.0, nf));
+    }
     for (int round = 0; round < 4; ++round) {
         const int slot = round * 64 + (tid >> 2), a = a0 + slot;
         const bool in = a < A;
@@ -184,6 +230,8 @@ __global__ __launch_bounds__(kThreads) void k_detloss_box(const DetlossArgs t) {
         if (e == 0) s_fg[slot] = fg ? 1 : 0;
         const float *z = t.z + (ba * 4u + e) * (size_t)K;
         double c = 0.0, m = 0.0, Z = 1.0, d = 0.0, v = 0.0, tv = 0.0, side = 0.0, wl = 0.0, wr = 0.0;
+        double ms = 0.0, Zs = 1.0, mt = 0.0, Zt = 1.0, spt = 0.0;
+        const float *tz = D ? t.tz + (ba * 4u + e) * (size_t)K : nullptr;
         int tl = 0;
         if (fg) {
             detloss_coord(t, z, a, e, c, m, Z, d, v);
@@ -198,6 +246,13 @@ __global__ __launch_bounds__(kThreads) void k_detloss_box(const DetlossArgs t) {
                 const double lse = __dadd_rn(m, log(Z));
                 const double cl = __dsub_rn(lse, (double)z[tl]), cr = __dsub_rn(lse, (double)z[tl + 1]);
                 side = __dadd_rn(__dmul_rn(cl, wl), __dmul_rn(cr, wr));
+                if (D) {
+                    double kl;
+                    kd_stats(z, K, t.T, ms, Zs);
+                    kd_stats(tz, K, t.T, mt, Zt);
+                    kd_row(z, tz, K, t.T, ms, Zs, mt, Zt, kl, spt);
+                    l_dd = __dadd_rn(l_dd, kl);
+                }
             }
         }
         // every lane takes part: a quad's values come from its own four lanes
@@ -257,7 +312,12 @@ __global__ __launch_bounds__(kThreads) void k_detloss_box(const DetlossArgs t) {
                         double v2 = pr;
                         if (k == tl) v2 = __dsub_rn(v2, wl);
                         if (k == tl + 1) v2 = __dsub_rn(v2, wr);
-                        gz[k] = (float)__dadd_rn(v1, __dmul_rn(cd, v2));
+                        double gk = __dadd_rn(v1, __dmul_rn(cd, v2));
+                        if (D) {
+                            const double ps = kd_prob(z[k], t.T, ms, Zs), pt = kd_prob(tz[k], t.T, mt, Zt);
+                            gk = __dadd_rn(gk, __dmul_rn(cdd, __dsub_rn(__dmul_rn(ps, spt), pt)));
+                        }
+                        gz[k] = (float)gk;
                     }
                 } else {
                     gz[0] = (float)g_d;
@@ -281,23 +341,44 @@ __global__ __launch_bounds__(kThreads) void k_detloss_box(const DetlossArgs t) {
         t.dfl_part[at] = s_dfl;
         t.cnt_part[at] = s_cnt;
     }
+    if (D) {
+        const double s_dd = detloss_block_sum(l_dd, tmp);
+        if (tid == 0) t.ddfl_part[(size_t)b * gridDim.x + blockIdx.x] = s_dd;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------- fold
-// one workgroup of 256
+// one workgroup of 256.  <true>: losses[8] = loss_cls, loss_iou, loss_dfl, d_loss_cls, d_loss_dfl, tss, n_fg, W
+template <bool D>
 __global__ __launch_bounds__(kThreads) void k_detloss_fold(const DetlossArgs t) {
     __shared__ double tmp[kWaves];
     const double tss = detloss_fold(t.tss_part, t.n_tss, tmp);
     const double cls = detloss_fold(t.cls_part, t.n_cls, tmp);
     const double iou = detloss_fold(t.iou_part, t.n_box, tmp), dfl = detloss_fold(t.dfl_part, t.n_box, tmp);
     const double cnt = detloss_fold(t.cnt_part, t.n_box, tmp);
+    double dcls = 0.0, ddfl = 0.0, W = 0.0;
+    if (D) {
+        dcls = detloss_fold(t.dcls_part, t.n_cls, tmp);
+        ddfl = detloss_fold(t.ddfl_part, t.n_box, tmp);
+        W = detloss_fold(t.wfg_part, t.n_tss, tmp);
+    }
     if (threadIdx.x == 0) {
-        const double norm = tss > 1.0 ? tss : 1.0;
+        const double norm = detloss_norm<D>(tss);
         t.losses[0] = __ddiv_rn(cls, norm);
         t.losses[1] = __ddiv_rn(iou, norm);
         t.losses[2] = __ddiv_rn(dfl, norm);
-        t.losses[3] = tss;
-        t.losses[4] = cnt;
+        if (D) {
+            const double T2 = __dmul_rn(t.T, t.T);
+            t.losses[3] = __dmul_rn(T2, dcls);
+            // the reference's mean over the 4 * n_fg rows, times T^2, times every foreground anchor's w, over norm
+            t.losses[4] = cnt > 0.0 ? __ddiv_rn(__dmul_rn(__dmul_rn(T2, __ddiv_rn(ddfl, __dmul_rn(4.0, cnt))), W), norm) : 0.0;
+            t.losses[5] = tss;
+            t.losses[6] = cnt;
+            t.losses[7] = W;
+        } else {
+            t.losses[3] = tss;
+            t.losses[4] = cnt;
+        }
     }
 }
 

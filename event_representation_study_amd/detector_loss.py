@@ -30,6 +30,7 @@ sigmoid, as the head returns them in training).
 
 The warm-up epochs (``epoch_num < warmup_epoch``) assign with the ATSS rules of ``detector_assign`` when ``ComputeLoss`` is
 built with ``warmup_assigner="atss"``.  ``siou`` / ``ciou`` / ``diou`` and half-precision predictions are not mirrored.
+The distillation losses of ``loss_distill.py`` are ``detector_distill``.
 """
 import numpy as np
 import torch
@@ -98,8 +99,8 @@ def _take(first, tie, g):
 
 
 def loss_host(pred_scores, pred_distri, anc_points, stride, target_labels, target_bboxes, target_scores, fg_mask, reg_max=16,
-              use_dfl=True, loss_weight=None, details=None):
-    """Rules 1-7 in numpy float64: ``(losses float64 (5,) = [loss_cls, loss_iou, loss_dfl, tss, number of foreground anchors],
+              use_dfl=True, loss_weight=None, details=None, norm_floor=1.0):
+    """Rules 1-7 in numpy float64 (``norm_floor``: ``norm = tss > norm_floor ? tss : 1``; detector_distill passes 0): ``(losses float64 (5,) = [loss_cls, loss_iou, loss_dfl, tss, number of foreground anchors],
     grad_scores float32 (B, A, nc), grad_distri float32 (B, A, 4K), status uint32 (B,))``.  ``details``: a dict that receives the
     float64 gradients (``gs``, ``gz``), for each of their elements the sum of the absolute values of its terms (``gs_abs``,
     ``gz_abs``: what an error bound scales with), the same for the three sums (``cls_abs`` ...), ``box``, and the arguments of
@@ -122,7 +123,7 @@ def loss_host(pred_scores, pred_distri, anc_points, stride, target_labels, targe
         for c in range(nc):
             w = w + q[..., c]
         tss = F64(w.sum())
-        norm = tss if tss > 1 else F64(1.0)
+        norm = tss if tss > norm_floor else F64(1.0)
         # the class term
         bad = fg & ((labels < 0) | (labels >= nc))
         status = np.where(bad.any(1), ST_BAD_LABEL, 0).astype(np.uint32)
@@ -423,10 +424,8 @@ class ComputeLoss:
                                   counts, torch.from_numpy(np.concatenate(strides, 0)).to(device))
         return self._anchors[key]
 
-    def __call__(self, outputs, targets, epoch_num, step_num, batch_height, batch_width):
-        feats, pred_scores, pred_distri = outputs
-        _want_f32(pred_scores, "pred_scores")
-        _want_f32(pred_distri, "pred_distri")
+    def targets_of(self, feats, pred_scores, pred_distri, targets, epoch_num, batch_height, batch_width):
+        """``decode_boxes`` and the assigner of the epoch: ``(anc, stride, labels, target_bboxes, target_scores, fg, status or None)``."""
         dev = pred_scores.device
         anchors, anc, n_anchors_list, stride = self.anchors(feats, dev)
         B = int(pred_scores.shape[0])
@@ -456,6 +455,14 @@ class ComputeLoss:
             gt = _da.preprocess(targets, B, batch_width, batch_height, self.max_labels)
             labels, tb, ts, fg = self.formal_assigner(pred_scores.detach(), boxes_px, anc, gt[:, :, :1], gt[:, :, 1:], None)
             st_assign = self.formal_assigner.last_status
+        return anc, stride, labels, tb, ts, fg, st_assign
+
+    def __call__(self, outputs, targets, epoch_num, step_num, batch_height, batch_width):
+        feats, pred_scores, pred_distri = outputs
+        _want_f32(pred_scores, "pred_scores")
+        _want_f32(pred_distri, "pred_distri")
+        anc, stride, labels, tb, ts, fg, st_assign = self.targets_of(feats, pred_scores, pred_distri, targets, epoch_num, batch_height,
+                                                                    batch_width)
         loss, items, st = loss_batch(pred_scores, pred_distri, anc, stride, labels, tb, ts, fg, self.num_classes, self.reg_max,
                                      self.use_dfl, self.loss_weight, return_status=True)
         self.last_status = st if st_assign is None else torch.bitwise_or(st, st_assign.to(st.device))

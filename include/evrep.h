@@ -1140,6 +1140,63 @@ int evrep_detloss(const float *pred_scores, const float *pred_distri, const floa
                   int32_t A, int32_t nc, int32_t R, double w_class, double w_iou, double w_dfl, uint32_t flags, double *losses,
                   float *grad_scores, float *grad_distri, uint32_t *status, void *scratch, void *stream);
 
+/* The distillation losses of loss_distill.py (ComputeLoss.__call__ :62-279, distill_loss_cls :281-292, BboxLoss.forward
+ * :395-464 with distill_loss_dfl :489-500, distill_loss_cw :294-340), values AND gradients with respect to the student's
+ * tensors.  Every statement is ONE float64 operation as above; x / T is a float64 division; exp / log are the double library
+ * functions.  p, z = the student's pred_scores, pred_distri; tp, tz = the teacher's; T = temperature.
+ *   terms      loss_cls, loss_iou, loss_dfl, w, tss, status: the statements of evrep_detloss, by the same device code, but
+ *              norm = tss > 0 ? tss : 1 (loss_distill.py divides loss_cls where tss > 0 and the box terms unless tss == 0).
+ *   softmax    of n logits x at T: m = max_k (x_k / T); e_k = exp(x_k / T - m); Z = the e_k added left to right; pr_k = e_k / Z.
+ *   KL row     ps = softmax of the student's row, pt = of the teacher's: the terms pt_k * log(pt_k) - pt_k * log(ps_k), the first
+ *              product being 0 where pt_k == 0 (torch's xlogy); spt = the pt_k added left to right.
+ *   class      over ALL B * A rows of nc scores: d_loss_cls = (T * T) * (the rows' KL sums in a fixed order that depends on the
+ *              shape only, as every sum of KL terms here).  Not normalised.  With nc == 1 it is exactly 0, and so is its part of every gradient.
+ *   DFL        with EVREP_DETLOSS_USE_DFL, over the 4 * n_fg rows of K bins of the foreground anchors' sides (n_fg = their
+ *              number): sum = their KL sums in a fixed order; W = the w[b,a] of the FOREGROUND anchors in a fixed order;
+ *              d_loss_dfl = (((T * T) * (sum / (4 * n_fg))) * W) / norm -- the reference multiplies the mean over the rows by
+ *              every anchor's bbox_weight and adds.  0 without DFL and with n_fg == 0.  The teacher's boxes are not decoded.
+ *   gradients  of L = w_class * (loss_cls + k_class * d_loss_cls) + w_iou * loss_iou + w_dfl * (loss_dfl + k_dfl * d_loss_dfl):
+ *              grad_scores = (w_class / norm) * g_vfl + ((w_class * k_class) * T) * (ps_c * spt - pt_c), g_vfl the class
+ *              gradient of evrep_detloss; a foreground side's grad_distri[k] = (the value of evrep_detloss's rule with this norm)
+ *              + cdd * (ps_k * spt - pt_k), cdd = ((((w_dfl * k_dfl) * T) * W) / norm) / (4 * n_fg).  Each sum is formed in
+ *              float64 and rounded ONCE at the store; every element is written once; background rows of grad_distri are zeros.
+ *              The teacher's tensors get no gradient.
+ * evrep_detloss_distill: the arguments of evrep_detloss, plus t_pred_scores DEVICE float [B,A,nc], t_pred_distri DEVICE float
+ *   [B,A,4K], temperature (finite, > 0, else EVREP_EINVAL), k_class = decay * distill_weight["class"], k_dfl = decay *
+ *   distill_weight["dfl"] (the caller forms decay = ((1 - cos(epoch * pi / max_epoch)) / 2) * (0.01 - 1) + 1).  losses DEVICE
+ *   double [8] = loss_cls, loss_iou, loss_dfl (normalised), d_loss_cls, d_loss_dfl (before k_*), tss, n_fg, W.  flags, limits
+ *   and refusals as evrep_detloss, but nc <= EVREP_DISTILL_MAX_CLASSES (a whole row of scores lies in LDS).  scratch DEVICE, 256-byte aligned, evrep_detloss_distill_workspace_bytes(B, A, nc) bytes (0
+ *   for a refused shape): B * A doubles; three times min(ceil(B * A / 256), 256) doubles; two times B * min(ceil(A / rt),
+ *   ceil(2048 / B)) doubles with rt = min(256, 2048 / nc), the whole rows of a staged tile; four times B * ceil(A / 256)
+ *   doubles; each array rounded up to 256 bytes.  Needs no initialisation.  One async memset of status and FOUR launches: rows
+ *   (w, tss, and W and n_fg, which every foreground gradient needs, in a fixed order), class (p and tp held in LDS, each
+ *   read from memory once), box, fold.  No floating-point atomics: two calls give equal bits.  Does not allocate, does not
+ *   wait for the device, reads nothing back: the call may be captured into a graph.  What a NaN tss gives is not pinned.
+ * evrep_detloss_cwd: distill_loss_cw over L <= EVREP_CWD_MAX_LEVELS levels of maps s, t DEVICE float [n,c,h,w].  Per (n, c)
+ *   row of h * w values, x = s / tau, y = t / tau: ms = max x, Zs = sum exp(x - ms), ls_i = (x_i - ms) - log(Zs); lt_i likewise;
+ *   pt_i = exp(lt_i); row = sum pt_i * (lt_i - ls_i); spt = sum pt_i; grad_s_i = (tau / (n * c)) * (exp(ls_i) * spt - pt_i),
+ *   rounded once at the store.  The three sums of a row are taken in an order that depends on h * w only.  A level's loss =
+ *   (its rows in index order) * ((tau * tau) / (n * c)).  out DEVICE double [4] = the levels added left to right, then each
+ *   level (0 beyond L).  A row of at most EVREP_CWD_STAGE values is held in LDS between the passes, a longer one is re-read.
+ *   levels_host HOST [L], read before the call returns; grad_s may be NULL with EVREP_DETLOSS_NO_GRAD (the only flag).
+ *   n, c, h, w >= 1; n * c, h * w and the rows of all levels <= EVREP_TAL_MAX_ANCHORS; tau finite and > 0; anything else, a NULL
+ *   or misaligned pointer is EVREP_EINVAL before any launch.  scratch DEVICE, 256-byte aligned,
+ *   evrep_detloss_cwd_workspace_bytes(levels_host, L) bytes (0 for a refused table): one double per row, rounded up to 256
+ *   bytes; needs no initialisation.  Two launches, no atomics, no allocation, no wait, nothing read back. */
+typedef struct { const float *s; const float *t; float *grad_s; int32_t n, c, h, w; } evrep_cwd_level;
+#define EVREP_DISTILL_MAX_CLASSES 2048
+#define EVREP_CWD_MAX_LEVELS 3
+#define EVREP_CWD_STAGE 4096
+size_t evrep_detloss_distill_workspace_bytes(int32_t B, int32_t A, int32_t nc);
+int evrep_detloss_distill(const float *pred_scores, const float *pred_distri, const float *t_pred_scores, const float *t_pred_distri,
+                          const float *anc_points, const float *stride, const int64_t *target_labels, const void *target_bboxes,
+                          const void *target_scores, const uint8_t *fg, int32_t B, int32_t A, int32_t nc, int32_t R, double w_class,
+                          double w_iou, double w_dfl, double temperature, double k_class, double k_dfl, uint32_t flags, double *losses,
+                          float *grad_scores, float *grad_distri, uint32_t *status, void *scratch, void *stream);
+size_t evrep_detloss_cwd_workspace_bytes(const evrep_cwd_level *levels_host, int32_t L);
+int evrep_detloss_cwd(const evrep_cwd_level *levels_host, int32_t L, double tau, uint32_t flags, double *out, void *scratch,
+                      void *stream);
+
 /* What Detect.forward does behind its last convolutions (ev-YOLOv6/yolov6/models/effidehead.py:89-173, with
  * generate_anchors(is_eval = True) and dist2bbox(xywh) behind it): the per-level maps of cls_preds / reg_preds, NCHW as the
  * convolutions leave them, -> the prediction tensor of evaluation, the two tensors of training, and the maps' gradients.
