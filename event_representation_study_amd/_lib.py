@@ -144,6 +144,12 @@ SYMBOLS = {
     "evrep_dethead_predict": _st([_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp]),
     "evrep_dethead_train": _st([_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp]),
     "evrep_dethead_train_backward": _st([_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
+    "evrep_cast16_host": _st([_vp, _vp, _i64, _i32, _i32]),
+    "evrep_detloss_cwd_typed_workspace_bytes": (ctypes.c_size_t, [_vp, _i32]),
+    "evrep_detloss_cwd_typed": _st([_vp, _i32, _f64, ctypes.c_uint32, _i32, _i32, _vp, _vp, _vp]),
+    "evrep_dethead_predict_typed": _st([_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _i32, _vp, _vp]),
+    "evrep_dethead_train_typed": _st([_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _i32, _vp, _vp, _vp]),
+    "evrep_dethead_train_backward_typed": _st([_vp, _i32, _i32, _i32, _i32, ctypes.c_uint32, _i32, _vp, _vp, _vp, _vp]),
     "evrep_train_step": _st([_vp, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _f64, _f64, _i32, ctypes.c_uint32, _vp]),
     "evrep_ema_update": _st([_vp, _i32, _vp, _i64, _vp, _vp]),
     "evrep_voxel_normalize_scratch_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32]),
@@ -205,6 +211,10 @@ CWD_MAX_LEVELS, CWD_STAGE = 3, 4096
 # evrep_dethead_*: flag, the most levels, the anchors of a staged tile
 DETHEAD_USE_DFL = 1
 DETHEAD_MAX_LEVELS, DETHEAD_TILE = 8, 64
+# the *_typed entries: the dtype codes of the maps (DetheadLevel, DetheadGradLevel and CwdLevel hold plain addresses and serve
+# the typed entries as they are: the typed structs of the header differ in their pointee types only)
+DT_F32, DT_F16, DT_BF16 = 0, 1, 2
+MAP_DTYPES = {torch.float32: DT_F32, torch.float16: DT_F16, torch.bfloat16: DT_BF16}
 # evrep_train_step / evrep_ema_update: per-tensor flags, the call's flags, the elements of a chunk, the most groups, the words
 # of the hyper row in front of the groups' (lr, momentum, weight_decay), the words of the scaler's state
 STEP_HAS_GRAD, STEP_HAS_EMA, STEP_EMA_ONLY = 1, 2, 4

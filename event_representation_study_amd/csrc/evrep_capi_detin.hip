@@ -531,15 +531,24 @@ int evrep_detloss_distill(const float *pred_scores, const float *pred_distri, co
 }
 
 // the levels of evrep_detloss_cwd: counts, offsets and scales; false for a refused table
-static bool cwd_levels(const evrep_cwd_level *lv, int32_t L, double tau, bool grad, CwdArgs *t, int64_t *rows_out) {
-    if (L < 1 || L > EVREP_CWD_MAX_LEVELS || bad_ptr(lv, 8)) return false;
+// (the two level structs differ in the pointee types of s and t only: the float32 entry's table is read as the typed one)
+static_assert(sizeof(evrep_cwd_level) == sizeof(evrep_cwd_level_typed) && offsetof(evrep_cwd_level, grad_s) == offsetof(evrep_cwd_level_typed, grad_s) &&
+              offsetof(evrep_cwd_level, n) == offsetof(evrep_cwd_level_typed, n), "one layout");
+
+// the bytes of a map element of dtype code dt; 0 for an unknown code
+static inline uintptr_t dt_size(int32_t dt) { return dt == EVREP_DT_F32 ? 4u : (dt == EVREP_DT_F16 || dt == EVREP_DT_BF16) ? 2u : 0u; }
+
+static bool cwd_levels(const evrep_cwd_level_typed *lv, int32_t L, double tau, bool grad, int32_t sdt, int32_t tdt, CwdArgs *t,
+                       int64_t *rows_out) {
+    if (L < 1 || L > EVREP_CWD_MAX_LEVELS || bad_ptr(lv, 8) || !dt_size(sdt) || !dt_size(tdt)) return false;
     int64_t rows = 0;
     for (int32_t l = 0; l < L; ++l) {
-        const evrep_cwd_level &v = lv[l];
+        const evrep_cwd_level_typed &v = lv[l];
         if (v.n < 1 || v.c < 1 || v.h < 1 || v.w < 1) return false;
         if ((int64_t)v.n * v.c > EVREP_TAL_MAX_ANCHORS || (int64_t)v.h * v.w > EVREP_TAL_MAX_ANCHORS) return false;
         if (t) {
-            if (bad_ptr(v.s, 4) || bad_ptr(v.t, 4) || (grad ? bad_ptr(v.grad_s, 4) : misaligned(v.grad_s, 4))) return false;
+            if (bad_ptr(v.s, dt_size(sdt)) || bad_ptr(v.t, dt_size(tdt)) || (grad ? bad_ptr(v.grad_s, 4) : misaligned(v.grad_s, 4)))
+                return false;
             const double nc = (double)((int64_t)v.n * v.c);
             t->s[l] = v.s; t->t[l] = v.t; t->g[l] = grad ? v.grad_s : nullptr;
             t->hw[l] = v.h * v.w; t->rows[l] = v.n * v.c; t->row0[l] = (int32_t)rows;
@@ -553,31 +562,54 @@ static bool cwd_levels(const evrep_cwd_level *lv, int32_t L, double tau, bool gr
     return true;
 }
 
-size_t evrep_detloss_cwd_workspace_bytes(const evrep_cwd_level *levels_host, int32_t L) {
+size_t evrep_detloss_cwd_typed_workspace_bytes(const evrep_cwd_level_typed *levels_host, int32_t L) {
     int64_t rows = 0;
-    if (!cwd_levels(levels_host, L, 1.0, false, nullptr, &rows)) return 0;
+    if (!cwd_levels(levels_host, L, 1.0, false, EVREP_DT_F32, EVREP_DT_F32, nullptr, &rows)) return 0;
     Carver c(nullptr);
     c.take<double>((size_t)rows * 8);
     return c.off;
 }
 
-int evrep_detloss_cwd(const evrep_cwd_level *levels_host, int32_t L, double tau, uint32_t flags, double *out, void *scratch,
-                      void *stream_) {
+size_t evrep_detloss_cwd_workspace_bytes(const evrep_cwd_level *levels_host, int32_t L) {
+    return evrep_detloss_cwd_typed_workspace_bytes(reinterpret_cast<const evrep_cwd_level_typed *>(levels_host), L);
+}
+
+int evrep_detloss_cwd_typed(const evrep_cwd_level_typed *levels_host, int32_t L, double tau, uint32_t flags, int32_t s_dtype,
+                            int32_t t_dtype, double *out, void *scratch, void *stream_) {
     if (flags & ~(uint32_t)EVREP_DETLOSS_NO_GRAD) return EVREP_EINVAL;
     if (!(tau > 0.0) || !(tau - tau == 0.0)) return EVREP_EINVAL;
     if (bad_ptr(out, 8) || bad_ptr(scratch, 256)) return EVREP_EINVAL;
     CwdArgs t;
     memset(&t, 0, sizeof(t));
     int64_t rows = 0;
-    if (!cwd_levels(levels_host, L, tau, !(flags & EVREP_DETLOSS_NO_GRAD), &t, &rows)) return EVREP_EINVAL;
+    if (!cwd_levels(levels_host, L, tau, !(flags & EVREP_DETLOSS_NO_GRAD), s_dtype, t_dtype, &t, &rows)) return EVREP_EINVAL;
     Carver c(scratch);
     t.part = c.take<double>((size_t)rows * 8);
-    t.out = out; t.tau = tau; t.L = L;
+    t.out = out; t.tau = tau; t.L = L; t.sdt = s_dtype; t.tdt = t_dtype;
     hipStream_t stream = as_stream(stream_);
-    k_detdistill_cw<<<(unsigned)rows, kThreads, 0, stream>>>(t);
+    if (s_dtype == EVREP_DT_F32 && t_dtype == EVREP_DT_F32) k_detdistill_cw<false><<<(unsigned)rows, kThreads, 0, stream>>>(t);
+    else k_detdistill_cw<true><<<(unsigned)rows, kThreads, 0, stream>>>(t);
     LAUNCH_CHECK("k_detdistill_cw");
     k_detdistill_cw_fold<<<1, kThreads, 0, stream>>>(t);
     LAUNCH_CHECK("k_detdistill_cw_fold");
+    return EVREP_OK;
+}
+
+int evrep_detloss_cwd(const evrep_cwd_level *levels_host, int32_t L, double tau, uint32_t flags, double *out, void *scratch,
+                      void *stream_) {
+    return evrep_detloss_cwd_typed(reinterpret_cast<const evrep_cwd_level_typed *>(levels_host), L, tau, flags, EVREP_DT_F32,
+                                   EVREP_DT_F32, out, scratch, stream_);
+}
+
+// widen (dir 0: src 16-bit, dst float32) or round (dir 1: src float32, dst 16-bit) n elements on the HOST by the functions the
+// kernels use
+int evrep_cast16_host(const void *src, void *dst, int64_t n, int32_t dtype, int32_t dir) {
+    if ((dtype != EVREP_DT_F16 && dtype != EVREP_DT_BF16) || (dir != 0 && dir != 1) || n < 0) return EVREP_EINVAL;
+    if (n > 0 && (bad_ptr(src, dir ? 4 : 2) || bad_ptr(dst, dir ? 2 : 4))) return EVREP_EINVAL;
+    for (int64_t i = 0; i < n; ++i) {
+        if (dir) static_cast<uint16_t *>(dst)[i] = round16(static_cast<const float *>(src)[i], dtype);
+        else static_cast<float *>(dst)[i] = widen16(static_cast<const uint16_t *>(src)[i], dtype);
+    }
     return EVREP_OK;
 }
 
@@ -596,16 +628,30 @@ static inline bool dethead_level(DetheadArgs &t, int32_t l, int32_t h, int32_t w
     return total <= EVREP_TAL_MAX_ANCHORS;
 }
 
-static int dethead_forward(const evrep_dethead_level *lv, int32_t L, int32_t B, int32_t nc, int32_t R, uint32_t flags, float *pred,
-                           float *scores, float *distri, bool train, void *stream_) {
-    if (!dethead_shape_ok(L, B, nc, R, flags) || bad_ptr(lv, 8)) return EVREP_EINVAL;
+static_assert(sizeof(evrep_dethead_level) == sizeof(evrep_dethead_level_typed) && offsetof(evrep_dethead_level, h) == offsetof(evrep_dethead_level_typed, h) &&
+              offsetof(evrep_dethead_level, stride) == offsetof(evrep_dethead_level_typed, stride) &&
+              sizeof(evrep_dethead_grad_level) == sizeof(evrep_dethead_grad_level_typed) &&
+              offsetof(evrep_dethead_grad_level, h) == offsetof(evrep_dethead_grad_level_typed, h), "one layout");
+
+// a launch of the kernel template K<dtype> (the dtype was checked)
+#define DETHEAD_LAUNCH(K, dtype, grid, stream, t)                                                              \
+    do {                                                                                                       \
+        if ((dtype) == EVREP_DT_F32) K<EVREP_DT_F32><<<grid, kThreads, 0, stream>>>(t);                         \
+        else if ((dtype) == EVREP_DT_F16) K<EVREP_DT_F16><<<grid, kThreads, 0, stream>>>(t);                    \
+        else K<EVREP_DT_BF16><<<grid, kThreads, 0, stream>>>(t);                                               \
+    } while (0)
+
+static int dethead_forward(const evrep_dethead_level_typed *lv, int32_t L, int32_t B, int32_t nc, int32_t R, uint32_t flags,
+                           int32_t dtype, float *pred, float *scores, float *distri, bool train, void *stream_) {
+    const uintptr_t elem = dt_size(dtype);
+    if (!dethead_shape_ok(L, B, nc, R, flags) || bad_ptr(lv, 8) || !elem) return EVREP_EINVAL;
     if (train ? (bad_ptr(scores, 4) || bad_ptr(distri, 4)) : bad_ptr(pred, 4)) return EVREP_EINVAL;
     DetheadArgs t;
     memset(&t, 0, sizeof(t));
     int64_t total = 0, tiles = 0;
     for (int32_t l = 0; l < L; ++l) {
         if (!dethead_level(t, l, lv[l].h, lv[l].w, total, tiles)) return EVREP_EINVAL;
-        if (bad_ptr(lv[l].cls, 4) || bad_ptr(lv[l].reg, 4)) return EVREP_EINVAL;
+        if (bad_ptr(lv[l].cls, elem) || bad_ptr(lv[l].reg, elem)) return EVREP_EINVAL;
         if (!(lv[l].stride > 0.0f) || !(lv[l].stride - lv[l].stride == 0.0f)) return EVREP_EINVAL;   // NaN, inf, <= 0
         t.cls[l] = lv[l].cls; t.reg[l] = lv[l].reg; t.stride[l] = lv[l].stride;
     }
@@ -615,10 +661,10 @@ static int dethead_forward(const evrep_dethead_level *lv, int32_t L, int32_t B, 
     t.K = t.use_dfl ? R + 1 : 1;
     const dim3 grid((unsigned)tiles, (unsigned)B);
     if (train) {
-        k_dethead_train<<<grid, kThreads, 0, as_stream(stream_)>>>(t);
+        DETHEAD_LAUNCH(k_dethead_train, dtype, grid, as_stream(stream_), t);
         LAUNCH_CHECK("k_dethead_train");
     } else {
-        k_dethead_predict<<<grid, kThreads, 0, as_stream(stream_)>>>(t);
+        DETHEAD_LAUNCH(k_dethead_predict, dtype, grid, as_stream(stream_), t);
         LAUNCH_CHECK("k_dethead_predict");
     }
     return EVREP_OK;
@@ -626,18 +672,31 @@ static int dethead_forward(const evrep_dethead_level *lv, int32_t L, int32_t B, 
 
 int evrep_dethead_predict(const evrep_dethead_level *levels_host, int32_t L, int32_t B, int32_t nc, int32_t R, uint32_t flags,
                           float *pred, void *stream_) {
-    return dethead_forward(levels_host, L, B, nc, R, flags, pred, nullptr, nullptr, false, stream_);
+    return dethead_forward(reinterpret_cast<const evrep_dethead_level_typed *>(levels_host), L, B, nc, R, flags, EVREP_DT_F32, pred,
+                           nullptr, nullptr, false, stream_);
 }
 
 int evrep_dethead_train(const evrep_dethead_level *levels_host, int32_t L, int32_t B, int32_t nc, int32_t R, uint32_t flags,
                         float *pred_scores, float *pred_distri, void *stream_) {
-    return dethead_forward(levels_host, L, B, nc, R, flags, nullptr, pred_scores, pred_distri, true, stream_);
+    return dethead_forward(reinterpret_cast<const evrep_dethead_level_typed *>(levels_host), L, B, nc, R, flags, EVREP_DT_F32, nullptr,
+                           pred_scores, pred_distri, true, stream_);
 }
 
-int evrep_dethead_train_backward(const evrep_dethead_grad_level *levels_host, int32_t L, int32_t B, int32_t nc, int32_t R,
-                                 uint32_t flags, const float *pred_scores, const float *grad_scores, const float *grad_distri,
-                                 void *stream_) {
-    if (!dethead_shape_ok(L, B, nc, R, flags) || bad_ptr(levels_host, 8)) return EVREP_EINVAL;
+int evrep_dethead_predict_typed(const evrep_dethead_level_typed *levels_host, int32_t L, int32_t B, int32_t nc, int32_t R,
+                                uint32_t flags, int32_t dtype, float *pred, void *stream_) {
+    return dethead_forward(levels_host, L, B, nc, R, flags, dtype, pred, nullptr, nullptr, false, stream_);
+}
+
+int evrep_dethead_train_typed(const evrep_dethead_level_typed *levels_host, int32_t L, int32_t B, int32_t nc, int32_t R,
+                              uint32_t flags, int32_t dtype, float *pred_scores, float *pred_distri, void *stream_) {
+    return dethead_forward(levels_host, L, B, nc, R, flags, dtype, nullptr, pred_scores, pred_distri, true, stream_);
+}
+
+int evrep_dethead_train_backward_typed(const evrep_dethead_grad_level_typed *levels_host, int32_t L, int32_t B, int32_t nc,
+                                       int32_t R, uint32_t flags, int32_t dtype, const float *pred_scores,
+                                       const float *grad_scores, const float *grad_distri, void *stream_) {
+    const uintptr_t elem = dt_size(dtype);
+    if (!dethead_shape_ok(L, B, nc, R, flags) || bad_ptr(levels_host, 8) || !elem) return EVREP_EINVAL;
     if (!grad_scores && !grad_distri) return EVREP_EINVAL;             // nothing asked for
     if (misaligned(grad_scores, 4) || misaligned(grad_distri, 4)) return EVREP_EINVAL;
     if (grad_scores ? bad_ptr(pred_scores, 4) : misaligned(pred_scores, 4)) return EVREP_EINVAL;
@@ -645,19 +704,26 @@ int evrep_dethead_train_backward(const evrep_dethead_grad_level *levels_host, in
     memset(&t, 0, sizeof(t));
     int64_t total = 0, tiles = 0;
     for (int32_t l = 0; l < L; ++l) {
-        const evrep_dethead_grad_level &g = levels_host[l];
+        const evrep_dethead_grad_level_typed &g = levels_host[l];
         if (!dethead_level(t, l, g.h, g.w, total, tiles)) return EVREP_EINVAL;
-        if (grad_scores ? bad_ptr(g.gcls, 4) : g.gcls != nullptr) return EVREP_EINVAL;   // a half comes whole or not at all
-        if (grad_distri ? bad_ptr(g.greg, 4) : g.greg != nullptr) return EVREP_EINVAL;
+        if (grad_scores ? bad_ptr(g.gcls, elem) : g.gcls != nullptr) return EVREP_EINVAL;   // a half comes whole or not at all
+        if (grad_distri ? bad_ptr(g.greg, elem) : g.greg != nullptr) return EVREP_EINVAL;
         t.gcls[l] = g.gcls; t.greg[l] = g.greg;
     }
     t.p = pred_scores; t.gs = grad_scores; t.gd = grad_distri;
     t.L = L; t.N = (int32_t)total; t.nc = nc;
     t.use_dfl = (flags & EVREP_DETHEAD_USE_DFL) ? 1 : 0;
     t.K = t.use_dfl ? R + 1 : 1;
-    k_dethead_backward<<<dim3((unsigned)tiles, (unsigned)B), kThreads, 0, as_stream(stream_)>>>(t);
+    DETHEAD_LAUNCH(k_dethead_backward, dtype, dim3((unsigned)tiles, (unsigned)B), as_stream(stream_), t);
     LAUNCH_CHECK("k_dethead_backward");
     return EVREP_OK;
+}
+
+int evrep_dethead_train_backward(const evrep_dethead_grad_level *levels_host, int32_t L, int32_t B, int32_t nc, int32_t R,
+                                 uint32_t flags, const float *pred_scores, const float *grad_scores, const float *grad_distri,
+                                 void *stream_) {
+    return evrep_dethead_train_backward_typed(reinterpret_cast<const evrep_dethead_grad_level_typed *>(levels_host), L, B, nc, R, flags,
+                                              EVREP_DT_F32, pred_scores, grad_scores, grad_distri, stream_);
 }
 
 static inline bool step_tables_ok(const evrep_step_tensor *tensors, int32_t n_tensors, const evrep_step_chunk *chunks,

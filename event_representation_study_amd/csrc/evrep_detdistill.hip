@@ -21,7 +21,11 @@
 //                          kCwStage floats is staged in LDS in the first pass and the later passes read LDS; a longer row is
 //                          re-read from memory (at 80 x 80 both rows are 51 KB, which stay in L2 between the passes).  A thread
 //                          reads in every pass the elements it read in the first, so no barrier lies between a store to LDS and
-//                          its load.
+//                          its load.  The maps' element types (EVREP_DT_*, the student's and the teacher's apart) are
+//                          two codes, the same in every thread: a 16-bit element is widened exactly at the load (rule
+//                          W1, evrep_f16.h) by a switch on the code -- the kernel is bound by its float64 arithmetic, so
+//                          the switch replaces nine template instances; a second instance without the switch serves two
+//                          float32 sides, which keep their time.  The LDS stage and the gradients stay float32.
 //   k_detdistill_cw_fold   one workgroup: a level's partials in index order, times tau^2 / (N * C).
 //
 // ROUNDING as in evrep_detloss.hip: every statement is ONE float64 operation, float32 inputs widened exactly, x / T a float64
@@ -31,6 +35,7 @@
 #include "evrep_common.h"
 #include "evrep_detloss.hip"
 #include "evrep_kd.h"
+#include "evrep_f16.h"
 
 #pragma clang fp contract(off)
 
@@ -130,7 +135,7 @@ __global__ __launch_bounds__(kThreads) void k_detdistill_cls(const DetlossArgs t
 
 // ------------------------------------------------------------------------------------------------- channel-wise distillation
 struct CwdArgs {
-    const float *s[kCwLevels], *t[kCwLevels];   // (N, C, H, W) each
+    const void *s[kCwLevels], *t[kCwLevels];    // (N, C, H, W) each, of the element types sdt and tdt
     float *g[kCwLevels];                        // the same shape, or null
     int32_t hw[kCwLevels];                      // H * W
     int32_t rows[kCwLevels], row0[kCwLevels];   // N * C and the sum of the earlier levels'
@@ -138,8 +143,16 @@ struct CwdArgs {
     double tau;
     double *part;                               // scratch [rows of all levels]
     double *out;                                // [4]
-    int32_t L;
+    int32_t L, sdt, tdt;                        // EVREP_DT_* of s and of t
 };
+
+// element i of a row that starts `at` elements into a map of the element type dt (the same in every thread); the instance
+// without 16-bit maps (kTyped false: both maps float32) is the plain load it always was
+template <bool kTyped>
+__device__ inline float cw_load(const void *map, size_t at, int i, int dt) {
+    if (!kTyped || dt == EVREP_DT_F32) return static_cast<const float *>(map)[at + i];
+    return widen16(static_cast<const uint16_t *>(map)[at + i], dt);
+}
 
 // the maximum over a workgroup of 256 (a > b ? a : b); valid in every thread; contains __syncthreads()
 __device__ inline double cw_block_max(double v, double *tmp) {
@@ -154,7 +167,8 @@ __device__ inline double cw_block_max(double v, double *tmp) {
     return r;
 }
 
-// grid (rows of all levels), 256 threads
+// grid (rows of all levels), 256 threads; kTyped: either side is 16-bit
+template <bool kTyped>
 __global__ __launch_bounds__(kThreads) void k_detdistill_cw(const CwdArgs t) {
     __shared__ double tmp[kWaves];
     __shared__ float s_s[kCwStage], s_t[kCwStage];
@@ -164,12 +178,12 @@ __global__ __launch_bounds__(kThreads) void k_detdistill_cw(const CwdArgs t) {
     if (t.L > 2 && row >= t.row0[2]) l = 2;
     const int n = t.hw[l];
     const size_t at = (size_t)(row - t.row0[l]) * (size_t)n;
-    const float *S = t.s[l] + at, *Tt = t.t[l] + at;
+    const void *S = t.s[l], *Tt = t.t[l];
     const bool staged = n <= kCwStage;
     const double ninf = -__longlong_as_double(0x7ff0000000000000ll);
     double ms = ninf, mt = ninf;
     for (int i = tid; i < n; i += kThreads) {
-        const float a = S[i], b = Tt[i];
+        const float a = cw_load<kTyped>(S, at, i, t.sdt), b = cw_load<kTyped>(Tt, at, i, t.tdt);
         if (staged) { s_s[i] = a; s_t[i] = b; }
         ms = dl_max(ms, __ddiv_rn((double)a, t.tau));
         mt = dl_max(mt, __ddiv_rn((double)b, t.tau));
@@ -178,14 +192,14 @@ __global__ __launch_bounds__(kThreads) void k_detdistill_cw(const CwdArgs t) {
     mt = cw_block_max(mt, tmp);
     double zs = 0.0, zt = 0.0;
     for (int i = tid; i < n; i += kThreads) {
-        const float a = staged ? s_s[i] : S[i], b = staged ? s_t[i] : Tt[i];
+        const float a = staged ? s_s[i] : cw_load<kTyped>(S, at, i, t.sdt), b = staged ? s_t[i] : cw_load<kTyped>(Tt, at, i, t.tdt);
         zs = __dadd_rn(zs, exp(__dsub_rn(__ddiv_rn((double)a, t.tau), ms)));
         zt = __dadd_rn(zt, exp(__dsub_rn(__ddiv_rn((double)b, t.tau), mt)));
     }
     const double lZs = log(detloss_block_sum(zs, tmp)), lZt = log(detloss_block_sum(zt, tmp));
     double kl = 0.0, spt = 0.0;
     for (int i = tid; i < n; i += kThreads) {
-        const float a = staged ? s_s[i] : S[i], b = staged ? s_t[i] : Tt[i];
+        const float a = staged ? s_s[i] : cw_load<kTyped>(S, at, i, t.sdt), b = staged ? s_t[i] : cw_load<kTyped>(Tt, at, i, t.tdt);
         const double ls = __dsub_rn(__dsub_rn(__ddiv_rn((double)a, t.tau), ms), lZs);
         const double lt = __dsub_rn(__dsub_rn(__ddiv_rn((double)b, t.tau), mt), lZt);
         const double pt = exp(lt);
@@ -199,7 +213,7 @@ __global__ __launch_bounds__(kThreads) void k_detdistill_cw(const CwdArgs t) {
     float *G = t.g[l] + at;
     const double gsc = t.gscale[l];
     for (int i = tid; i < n; i += kThreads) {
-        const float a = staged ? s_s[i] : S[i], b = staged ? s_t[i] : Tt[i];
+        const float a = staged ? s_s[i] : cw_load<kTyped>(S, at, i, t.sdt), b = staged ? s_t[i] : cw_load<kTyped>(Tt, at, i, t.tdt);
         const double ls = __dsub_rn(__dsub_rn(__ddiv_rn((double)a, t.tau), ms), lZs);
         const double lt = __dsub_rn(__dsub_rn(__ddiv_rn((double)b, t.tau), mt), lZt);
         G[i] = (float)__dmul_rn(gsc, __dsub_rn(__dmul_rn(exp(ls), spt), exp(lt)));

@@ -19,9 +19,16 @@
 // (span_store).  A row wider than kDetheadCols floats goes through in chunks of that many columns; a chunk that is not the
 // whole row leaves as one span per anchor, a wave per row.
 //
-// ROUNDING.  Box and class columns: every statement ONE float64 operation (__dadd_rn ...), float32 inputs widened exactly, one
+// ROUNDING.  Box and class columns: every statement ONE float64 operation (__dadd_rn ...), the maps' values widened exactly, one
 // rounding to float32 at the store into the tile.  The backward is float32, one operation per statement (__fsub_rn / __fmul_rn).
 // The library is compiled with -ffp-contract=off and this file repeats it as a pragma.
+//
+// THE MAPS' DTYPE.  The three kernels take the maps' element type as a template parameter (EVREP_DT_F32, _F16, _BF16: float, or
+// the 16 bits of a float16 / bfloat16 as uint16_t).  Only planes_to_tile, the E1 logit loads and tile_to_planes touch the maps:
+// a 16-bit element is widened exactly at the load (rule W1) and the backward's float32 value is rounded once at the store (W2),
+// by the integer functions of evrep_f16.h.  A lane moves ONE element, 2 bytes: a wave's 64 anchors of a plane are 128
+// contiguous bytes whatever the plane's start (planes of odd h * w start 2-byte aligned only), so there is no wide path whose
+// first, last and odd-start elements would need a narrow twin.  The LDS tile, dfl_side and the float32 spans are as before.
 //
 // Every loop ends at a value the host passed and every index is below the size the host stated.  Plain C++ and vector stores,
 // no atomic, no scratch, nothing read back, no allocation: the launches can be captured into a graph and two calls give equal
@@ -29,6 +36,7 @@
 #pragma once
 #include "evrep_common.h"
 #include "evrep_dfl.h"
+#include "evrep_f16.h"
 
 #pragma clang fp contract(off)
 
@@ -41,10 +49,10 @@ static_assert(kDetheadTile == kWave && kThreads == 4 * kWave, "a lane per anchor
 static_assert(kDetheadLds >= (EVREP_DETLOSS_MAX_REG + 1) * kThreads, "the sides' logits share the tile's LDS");
 
 struct DetheadArgs {
-    const float *cls[EVREP_DETHEAD_MAX_LEVELS];   // [B, nc, h, w] per level: logits (the forward), null in the backward
-    const float *reg[EVREP_DETHEAD_MAX_LEVELS];   // [B, 4K, h, w]
-    float *gcls[EVREP_DETHEAD_MAX_LEVELS];        // the backward's outputs, same shapes
-    float *greg[EVREP_DETHEAD_MAX_LEVELS];
+    const void *cls[EVREP_DETHEAD_MAX_LEVELS];    // [B, nc, h, w] per level: logits (the forward), null in the backward
+    const void *reg[EVREP_DETHEAD_MAX_LEVELS];    // [B, 4K, h, w]; the element type is the kernel's template parameter
+    void *gcls[EVREP_DETHEAD_MAX_LEVELS];         // the backward's outputs, same shapes and element type
+    void *greg[EVREP_DETHEAD_MAX_LEVELS];
     int32_t n[EVREP_DETHEAD_MAX_LEVELS];          // h * w
     int32_t w[EVREP_DETHEAD_MAX_LEVELS];
     int32_t off[EVREP_DETHEAD_MAX_LEVELS];        // the level's first anchor
@@ -103,31 +111,51 @@ __device__ inline float dethead_sigmoid(float x) {
     return (float)__ddiv_rn(1.0, __dadd_rn(1.0, e));
 }
 
+// a map's element: float, or the 16 bits of a float16 / bfloat16; W1 at the load, W2 at the store
+template <int kDt> struct DetheadMap { typedef uint16_t elem; };
+template <> struct DetheadMap<EVREP_DT_F32> { typedef float elem; };
+template <int kDt> __device__ inline float dethead_widen(typename DetheadMap<kDt>::elem v) {
+    if constexpr (kDt == EVREP_DT_F32) return v;
+    else if constexpr (kDt == EVREP_DT_F16) return widen_f16(v);
+    else return widen_bf16(v);
+}
+__device__ inline void gstore_u16(uint16_t *p, uint16_t v) {
+    *reinterpret_cast<uint16_t __attribute__((address_space(1))) *>(reinterpret_cast<uintptr_t>(p)) = v;
+}
+template <int kDt> __device__ inline void dethead_store(typename DetheadMap<kDt>::elem *p, float v) {
+    if constexpr (kDt == EVREP_DT_F32) gstore_f32(p, v);
+    else if constexpr (kDt == EVREP_DT_F16) gstore_u16(p, round_f16(v));
+    else gstore_u16(p, round_bf16(v));
+}
+
 // planes [ch0, ch0 + cw) of a level's map (of `chans` planes per image) -> the tile's columns [col0, col0 + cw): a wave per
 // plane, a lane per anchor
-template <bool kSigmoid>
-__device__ inline void planes_to_tile(const float *__restrict__ map, int b, int chans, int n, int a0, int cnt, int ch0, int cw,
+template <bool kSigmoid, int kDt>
+__device__ inline void planes_to_tile(const void *__restrict__ map, int b, int chans, int n, int a0, int cnt, int ch0, int cw,
                                       float *tile, int ld, int col0) {
+    typedef typename DetheadMap<kDt>::elem E;
     const int lane = (int)(threadIdx.x & 63);
     if (lane >= cnt) return;
-    const float *src = map + ((size_t)b * chans + (size_t)ch0) * (size_t)n + (size_t)(a0 + lane);   // plane c: src[c * n]
+    const E *src = static_cast<const E *>(map) + ((size_t)b * chans + (size_t)ch0) * (size_t)n + (size_t)(a0 + lane);   // plane c: src[c * n]
     float *dst = tile + (size_t)lane * ld + col0;
     int c = (int)(threadIdx.x >> 6);
     for (; c + 3 * kWaves < cw; c += 4 * kWaves) {                       // four loads in flight per lane
         float x[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) x[q] = src[(size_t)(c + q * kWaves) * n];
+        for (int q = 0; q < 4; ++q) x[q] = dethead_widen<kDt>(src[(size_t)(c + q * kWaves) * n]);
 #pragma unroll
         for (int q = 0; q < 4; ++q) dst[c + q * kWaves] = kSigmoid ? dethead_sigmoid(x[q]) : x[q];
     }
     for (; c < cw; c += kWaves) {
-        const float x = src[(size_t)c * n];
+        const float x = dethead_widen<kDt>(src[(size_t)c * n]);
         dst[c] = kSigmoid ? dethead_sigmoid(x) : x;
     }
 }
 
 // ------------------------------------------------------------------------------------------------------------------- predict
+template <int kDt>
 __global__ __launch_bounds__(kThreads) void k_dethead_predict(const DetheadArgs t) {
+    typedef typename DetheadMap<kDt>::elem E;
     __shared__ float tile[kDetheadLds];
     __shared__ double dist[4][kDetheadTile];
     int l, a0, cnt;
@@ -137,17 +165,17 @@ __global__ __launch_bounds__(kThreads) void k_dethead_predict(const DetheadArgs 
     float *out_row0 = t.pred + ((size_t)b * t.N + (size_t)(t.off[l] + a0)) * (size_t)row;
     // E1: the lane's K logits, one read each, into its own column of LDS
     if (lane < cnt) {
-        const float *z = t.reg[l] + ((size_t)b * 4u * t.K + (size_t)side * t.K) * (size_t)n + (size_t)(a0 + lane);
+        const E *z = static_cast<const E *>(t.reg[l]) + ((size_t)b * 4u * t.K + (size_t)side * t.K) * (size_t)n + (size_t)(a0 + lane);
         float *mine = tile + threadIdx.x;
         int k = 0;
         for (; k + 3 < t.K; k += 4) {                                    // four loads in flight per lane
             float x[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) x[q] = z[(size_t)(k + q) * n];
+            for (int q = 0; q < 4; ++q) x[q] = dethead_widen<kDt>(z[(size_t)(k + q) * n]);
 #pragma unroll
             for (int q = 0; q < 4; ++q) mine[(k + q) * kThreads] = x[q];
         }
-        for (; k < t.K; ++k) mine[k * kThreads] = z[(size_t)k * n];
+        for (; k < t.K; ++k) mine[k * kThreads] = dethead_widen<kDt>(z[(size_t)k * n]);
         double m, Z, d;
         if (t.use_dfl) dfl_side(mine, kThreads, t.K, m, Z, d);
         else d = (double)mine[0];
@@ -174,7 +202,7 @@ __global__ __launch_bounds__(kThreads) void k_dethead_predict(const DetheadArgs 
                 r[4] = 1.0f;
             }
         }
-        planes_to_tile<true>(t.cls[l], b, t.nc, n, a0, cnt, c0 + first - 5, cw - first, tile, ld, first);   // E4
+        planes_to_tile<true, kDt>(t.cls[l], b, t.nc, n, a0, cnt, c0 + first - 5, cw - first, tile, ld, first);   // E4
         __syncthreads();
         tile_store(out_row0, row, c0, cw, cnt, tile, ld);
         __syncthreads();
@@ -182,6 +210,7 @@ __global__ __launch_bounds__(kThreads) void k_dethead_predict(const DetheadArgs 
 }
 
 // --------------------------------------------------------------------------------------------------------------------- train
+template <int kDt>
 __global__ __launch_bounds__(kThreads) void k_dethead_train(const DetheadArgs t) {
     __shared__ float tile[kDetheadLds];
     int l, a0, cnt;
@@ -190,13 +219,13 @@ __global__ __launch_bounds__(kThreads) void k_dethead_train(const DetheadArgs t)
     const size_t at = (size_t)b * t.N + (size_t)(t.off[l] + a0);
     for (int c0 = 0; c0 < t.nc; c0 += kDetheadCols) {                    // T1
         const int cw = t.nc - c0 < kDetheadCols ? t.nc - c0 : kDetheadCols, ld = cw | 1;
-        planes_to_tile<true>(t.cls[l], b, t.nc, n, a0, cnt, c0, cw, tile, ld, 0);
+        planes_to_tile<true, kDt>(t.cls[l], b, t.nc, n, a0, cnt, c0, cw, tile, ld, 0);
         __syncthreads();
         tile_store(t.scores + at * (size_t)t.nc, t.nc, c0, cw, cnt, tile, ld);
         __syncthreads();
     }
     const int row = 4 * t.K, ld = row | 1;                               // T2: row <= kDetheadCols, one chunk
-    planes_to_tile<false>(t.reg[l], b, row, n, a0, cnt, 0, row, tile, ld, 0);
+    planes_to_tile<false, kDt>(t.reg[l], b, row, n, a0, cnt, 0, row, tile, ld, 0);
     __syncthreads();
     tile_store(t.distri + at * (size_t)row, row, 0, row, cnt, tile, ld);
 }
@@ -248,14 +277,18 @@ __device__ inline void tile_load(const float *in_row0, const float *p_row0, int 
 }
 
 // the tile's columns [0, cw) -> planes [ch0, ch0 + cw) of a level's gradient map: a wave per plane, a lane per anchor
-__device__ inline void tile_to_planes(float *__restrict__ map, int b, int chans, int n, int a0, int cnt, int ch0, int cw,
+template <int kDt>
+__device__ inline void tile_to_planes(void *__restrict__ map, int b, int chans, int n, int a0, int cnt, int ch0, int cw,
                                       const float *tile, int ld) {
+    typedef typename DetheadMap<kDt>::elem E;
     const int lane = (int)(threadIdx.x & 63);
     if (lane >= cnt) return;
     for (int c = (int)(threadIdx.x >> 6); c < cw; c += kWaves)
-        gstore_f32(map + ((size_t)b * chans + (size_t)(ch0 + c)) * (size_t)n + (size_t)(a0 + lane), tile[(size_t)lane * ld + c]);
+        dethead_store<kDt>(static_cast<E *>(map) + ((size_t)b * chans + (size_t)(ch0 + c)) * (size_t)n + (size_t)(a0 + lane),
+                           tile[(size_t)lane * ld + c]);
 }
 
+template <int kDt>
 __global__ __launch_bounds__(kThreads) void k_dethead_backward(const DetheadArgs t) {
     __shared__ float tile[kDetheadLds];
     int l, a0, cnt;
@@ -267,7 +300,7 @@ __global__ __launch_bounds__(kThreads) void k_dethead_backward(const DetheadArgs
             const int cw = t.nc - c0 < kDetheadCols ? t.nc - c0 : kDetheadCols, ld = cw | 1;
             tile_load(t.gs + at * (size_t)t.nc, t.p + at * (size_t)t.nc, t.nc, c0, cw, cnt, tile, ld);
             __syncthreads();
-            tile_to_planes(t.gcls[l], b, t.nc, n, a0, cnt, c0, cw, tile, ld);
+            tile_to_planes<kDt>(t.gcls[l], b, t.nc, n, a0, cnt, c0, cw, tile, ld);
             __syncthreads();
         }
     }
@@ -275,7 +308,7 @@ __global__ __launch_bounds__(kThreads) void k_dethead_backward(const DetheadArgs
         const int row = 4 * t.K, ld = row | 1;
         tile_load(t.gd + at * (size_t)row, nullptr, row, 0, row, cnt, tile, ld);
         __syncthreads();
-        tile_to_planes(t.greg[l], b, row, n, a0, cnt, 0, row, tile, ld);
+        tile_to_planes<kDt>(t.greg[l], b, row, n, a0, cnt, 0, row, tile, ld);
     }
 }
 

@@ -29,7 +29,15 @@ teacher's ``pred_scores`` / ``pred_distri``, everything else as in ``detector_lo
    ``k_dfl = decay * dw["dfl"]``; ``loss = ((wc * cls_all + wi * loss_iou) + wd * dfl_all) + d_loss_cw * (decay * w_cwd)``,
    with ``cls_all = loss_cls + d_loss_cls * k_class`` and ``dfl_all = loss_dfl + d_loss_dfl * k_dfl``.
 
-Half precision, ``loss_distill_ns.py`` and ``fuse_ab`` are not mirrored."""
+16-bit feature maps (training under ``torch.autocast``): ``distill_cw`` takes float16 or bfloat16 maps as they are -- the three
+student maps of one dtype, the three teacher maps of one, and the two may differ (a teacher may run outside autocast).  An
+element is widened exactly to float32 at its load, so the loss has the bits it has for ``map.float()`` and stays float64.  The
+gradient arrays of rule 7 stay FLOAT32 whatever the maps' dtype: an element is ``tau / (N * C)`` times a difference of
+probabilities, about 1e-8 at the reference's shapes, below float16's smallest subnormal before the loss scale multiplies it.
+The autograd node returns ``(g32 * grad_output).to(student's dtype)``: the one rounding comes after the scale.
+
+float64 maps, 16-bit ``pred_scores`` / ``pred_distri`` (with ``detector_head``'s tail they are float32 by construction),
+``loss_distill_ns.py`` and ``fuse_ab`` are not mirrored."""
 import ctypes
 import math
 
@@ -271,24 +279,31 @@ def distill_batch(pred_scores, pred_distri, t_pred_scores, t_pred_distri, anc_po
 
 
 class _CwNode(torch.autograd.Function):
-    """``d_loss_cw`` carrying the three maps' gradient arrays."""
+    """``d_loss_cw`` carrying the three maps' float32 gradient arrays.  The backward returns ``(g32 * grad_output).to(student's
+    dtype)``: the one rounding of a 16-bit student's gradient comes after the loss scale.  ``custom_fwd`` without ``cast_inputs``
+    and ``custom_bwd``: 16-bit maps stay as they are inside an autocast region, the backward runs under the forward's state."""
 
     @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda")
     def forward(ctx, loss, g0, g1, g2, s0, s1, s2):
         ctx.save_for_backward(g0, g1, g2)
+        ctx.dtype = s0.dtype
         return loss.clone()
 
     @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_output):
         g = grad_output.to(torch.float32)
-        return (None, None, None, None) + tuple(gi * g if ctx.needs_input_grad[4 + i] else None for i, gi in enumerate(ctx.saved_tensors))
+        return (None, None, None, None) + tuple((gi * g).to(ctx.dtype) if ctx.needs_input_grad[4 + i] else None
+                                                for i, gi in enumerate(ctx.saved_tensors))
 
 
 def _cw_device(s, t, tau, grad):
-    """The C entry on three pairs of contiguous CUDA maps: ``(out float64 (4,), [grad_s] or None)``."""
+    """The C entry on three pairs of contiguous CUDA maps (the student's of one dtype, the teacher's of one):
+    ``(out float64 (4,), [grad_s float32] or None)``."""
     dev = s[0].device
     lv = (_lib.CwdLevel * CW_LEVELS)()
-    grads = [torch.empty_like(x) for x in s] if grad else None
+    grads = [torch.empty(x.shape, dtype=torch.float32, device=dev) for x in s] if grad else None
     for l in range(CW_LEVELS):
         N, C, H, W = (int(v) for v in s[l].shape)
         lv[l].s, lv[l].t = s[l].data_ptr(), t[l].data_ptr()
@@ -297,27 +312,38 @@ def _cw_device(s, t, tau, grad):
     out = torch.empty((4,), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         api = _lib.api()
-        nbytes = api.evrep_detloss_cwd_workspace_bytes(ctypes.cast(lv, ctypes.c_void_p), CW_LEVELS)
+        nbytes = api.evrep_detloss_cwd_typed_workspace_bytes(ctypes.cast(lv, ctypes.c_void_p), CW_LEVELS)
         if nbytes == 0:
             raise ValueError("distill_cw takes maps of at most 2^24 rows (N * C, all levels) of at most 2^24 values (H * W)")
         scratch = _lib.scratch(nbytes, dev)
-        api.evrep_detloss_cwd(ctypes.cast(lv, ctypes.c_void_p), CW_LEVELS, float(tau), 0 if grad else _lib.DETLOSS_NO_GRAD, _lib.ptr(out),
-                              _lib.ptr(scratch), _lib.stream_ptr())
+        api.evrep_detloss_cwd_typed(ctypes.cast(lv, ctypes.c_void_p), CW_LEVELS, float(tau), 0 if grad else _lib.DETLOSS_NO_GRAD,
+                                    _lib.MAP_DTYPES[s[0].dtype], _lib.MAP_DTYPES[t[0].dtype], _lib.ptr(out), _lib.ptr(scratch),
+                                    _lib.stream_ptr())
     return out, grads
+
+
+def _want_map(t, what, dtype, first):
+    """A feature map of float32, float16 or bfloat16 (float64 keeps the loss's refusal), of the dtype of its side's first map."""
+    if not isinstance(t, torch.Tensor) or t.dtype not in _lib.MAP_DTYPES:
+        _dl._want_f32(t, what)
+    if dtype is not None and t.dtype != dtype:
+        raise ValueError("%s is %s, %s %s: the maps of one side share one dtype" % (what, t.dtype, first, dtype))
+    return t.dtype
 
 
 def distill_cw(s_feats, t_feats, temperature=1):
     """``distill_loss_cw`` (loss_distill.py:294-340) over the FIRST THREE maps of ``s_feats`` / ``t_feats`` ((N, C, H, W) float32,
-    further levels are ignored as the reference ignores them): a float64 scalar on the maps' device carrying ONE autograd node
-    over the three student maps; the teacher's maps get no gradient.  CUDA maps take the kernel (two launches, no host read),
-    CPU maps ``cw_host``."""
+    float16 or bfloat16, one dtype per side; further levels are ignored as the reference ignores them): a float64 scalar on the
+    maps' device carrying ONE autograd node over the three student maps, whose gradients come in the student's dtype; the
+    teacher's maps get no gradient.  CUDA maps take the kernel (two launches, no host read), CPU maps ``cw_host``."""
     tau = _temperature(temperature)
     if len(s_feats) < CW_LEVELS or len(t_feats) < CW_LEVELS:
         raise ValueError("distill_cw takes at least %d levels of student and teacher maps" % CW_LEVELS)
     s, t = list(s_feats[:CW_LEVELS]), list(t_feats[:CW_LEVELS])
+    sdt = tdt = None
     for l in range(CW_LEVELS):
-        _dl._want_f32(s[l], "s_feats[%d]" % l)
-        _dl._want_f32(t[l], "t_feats[%d]" % l)
+        sdt = _want_map(s[l], "s_feats[%d]" % l, sdt, "s_feats[0]")
+        tdt = _want_map(t[l], "t_feats[%d]" % l, tdt, "t_feats[0]")
         if s[l].dim() != 4:
             raise ValueError("s_feats[%d] must be (N, C, H, W), got %s" % (l, tuple(s[l].shape)))
         _same_shape(s[l], t[l], "t_feats[%d]" % l)
@@ -328,7 +354,7 @@ def distill_cw(s_feats, t_feats, temperature=1):
     if s[0].is_cuda:
         out, grads = _cw_device(sc, tc, tau, grad)
     else:
-        o, g = cw_host([x.numpy() for x in sc], [x.numpy() for x in tc], tau)
+        o, g = cw_host([x.float().numpy() for x in sc], [x.float().numpy() for x in tc], tau)      # .float(): the exact widening
         out, grads = torch.from_numpy(o), ([torch.from_numpy(x) for x in g] if grad else None)
     loss = out[0]
     if grad:

@@ -11,7 +11,7 @@ backward, and ``predict_batch`` hands the prediction tensor on to ``detector_out
 
 The rules (include/evrep.h states them with ``evrep_dethead_predict``).  Level ``l`` has a map of ``h_l x w_l``, ``n_l = h_l * w_l``
 anchors, offset ``off_l`` and stride ``s_l``; anchor ``a = off_l + i * w_l + j`` has the point ``ax = j + 0.5``, ``ay = i + 0.5``.
-``cls_l`` is float32 ``[B, nc, h_l, w_l]`` (raw logits), ``reg_l`` float32 ``[B, 4K, h_l, w_l]`` with channel ``side * K + k``,
+``cls_l`` is ``[B, nc, h_l, w_l]`` (raw logits), ``reg_l`` ``[B, 4K, h_l, w_l]`` with channel ``side * K + k``, float32 or 16-bit (below),
 K = ``reg_max + 1`` with DFL and 1 without.  Every statement of E1-E4 is one float64 operation on exactly widened inputs.
 
 E1. The side distance ``d`` is rule 1 of ``detector_loss`` (``m``, ``e_k``, ``Z``, ``pr_k``, ``d`` added left to right); without DFL ``d = z``.
@@ -23,8 +23,18 @@ T1. ``pred_scores[b, a, c]`` is the value of E4.   T2. ``pred_distri[b, a, ch] =
 Backward, float32, one operation per statement (torch's ``sigmoid_backward`` on the stored output):
 ``gcls_l[b, c, i, j] = (g * (1 - p)) * p``; ``greg_l[b, ch, i, j] = grad_distri[b, a, ch]``.
 
-Inputs must be finite.  Half precision, ``Detect.export``, the anchor-based and distillation heads and a ``proj`` other than
-``linspace(0, reg_max, reg_max + 1)`` are not mirrored.
+16-bit maps (training under ``torch.autocast``, evaluation with ``model.half()``): the 2L maps of a call may be float16 or
+bfloat16 instead of float32, all of one dtype, and go into the same launches as they are (``evrep_dethead_*_typed``).
+W1. A 16-bit element is widened exactly to float32 at its load (float16 by IEEE conversion, bfloat16 by its 16 bits on top of
+    16 zero bits; subnormals and -0.0 keep value and sign), and E1-E4 / T1 run on that; T2 is the exact widening.  So
+    ``predict`` and ``train_outputs`` give the bits they give for ``map.float()``, and all outputs stay float32.
+W2. The backward forms its float32 value as above and rounds it once, to nearest even, to the maps' dtype at the store
+    (overflow to +-inf, which the scaler's ``found_inf`` exists for; a NaN stays a NaN): ``float32_gradient.to(dtype)`` bit for
+    bit wherever it is no NaN.  The gradient maps are allocated in the maps' dtype and handed to autograd as they are.
+CPU maps of a 16-bit dtype take the host mirrors on ``map.float()`` and return ``.to(dtype)`` gradients.
+
+Inputs must be finite.  float64 maps, ``Detect.export``, the anchor-based and distillation heads and a ``proj`` other than
+``linspace(0, reg_max, reg_max + 1)`` are not mirrored; ``pred_scores`` / ``pred_distri`` and everything behind them stay float32.
 """
 import numpy as np
 import torch
@@ -46,13 +56,17 @@ def _levels(cls_maps, reg_maps, K, strides=None, nc=None):
         raise ValueError("the head takes 1..%d levels and as many reg maps as cls maps, got %d and %d" % (MAX_LEVELS, L, len(reg_maps)))
     if strides is not None and len(strides) != L:
         raise ValueError("%d strides for %d levels" % (len(strides), L))
-    dev, B, shapes = None, None, []
+    dev, B, shapes, dtype = None, None, [], None
     for l, (c, r) in enumerate(zip(cls_maps, reg_maps)):
         for name, t in (("cls", c), ("reg", r)):
             what = "level %d: %s map" % (l, name)
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-                raise ValueError("%s is %s: the head takes float32 maps (half precision is not mirrored), call .float() on it first"
-                                 % (what, getattr(t, "dtype", type(t).__name__)))
+            if not isinstance(t, torch.Tensor) or t.dtype not in _lib.MAP_DTYPES:
+                raise ValueError("%s is %s: the head takes float32, float16 or bfloat16 maps (float64 is not mirrored), call .float() "
+                                 "on it first" % (what, getattr(t, "dtype", type(t).__name__)))
+            if dtype is None:
+                dtype = t.dtype
+            elif t.dtype != dtype:
+                raise ValueError("%s is %s, level 0's cls map %s: all maps of a call share one dtype" % (what, t.dtype, dtype))
             if t.dim() != 4:
                 raise ValueError("%s must be (B, C, h, w), got %s" % (what, tuple(t.shape)))
             if not t.is_contiguous():
@@ -107,7 +121,8 @@ def _sigmoid_host(x32):
 
 
 def _np_maps(maps):
-    return [np.ascontiguousarray(m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else m, dtype=F32) for m in maps]
+    """float32 arrays of the maps; a 16-bit tensor is widened exactly by ``.float()`` (numpy has no bfloat16)."""
+    return [np.ascontiguousarray(m.detach().cpu().float().numpy() if isinstance(m, torch.Tensor) else m, dtype=F32) for m in maps]
 
 
 def predict_host(cls_maps, reg_maps, strides=(8, 16, 32), reg_max=16, use_dfl=True):
@@ -173,6 +188,11 @@ def _flags(use_dfl):
     return _lib.DETHEAD_USE_DFL if use_dfl else 0
 
 
+def _dt(maps):
+    """The dtype code of the call: that of its first map (``_levels`` has held the others to it)."""
+    return _lib.MAP_DTYPES[maps[0].dtype]
+
+
 def predict(cls_maps, reg_maps, strides=(8, 16, 32), reg_max=16, use_dfl=True, out=None):
     """``Detect.forward`` in evaluation, behind the convolutions: lists of L maps ``cls_l (B, nc, h_l, w_l)`` (raw logits) and
     ``reg_l (B, 4K, h_l, w_l)`` float32 -> ``pred (B, N, 5 + nc)`` float32 ``[cx, cy, w, h, 1, scores]`` in pixels.  CUDA maps take
@@ -189,8 +209,8 @@ def predict(cls_maps, reg_maps, strides=(8, 16, 32), reg_max=16, use_dfl=True, o
     else:
         _lib.want(out, "out", torch.float32, shape=(B, N, 5 + nc), device=dev)
     with torch.cuda.device(dev):
-        _lib.api().evrep_dethead_predict(_level_table(cls_maps, reg_maps, shapes, strides), len(shapes), B, nc, R, _flags(use_dfl),
-                                         _lib.ptr(out), _lib.stream_ptr())
+        _lib.api().evrep_dethead_predict_typed(_level_table(cls_maps, reg_maps, shapes, strides), len(shapes), B, nc, R, _flags(use_dfl),
+                                               _dt(cls_maps), _lib.ptr(out), _lib.stream_ptr())
     return out
 
 
@@ -199,32 +219,43 @@ def _train_device(cls_maps, reg_maps, shapes, B, nc, R, K, use_dfl, dev, scores=
     scores = torch.empty((B, N, nc), dtype=torch.float32, device=dev) if scores is None else scores
     distri = torch.empty((B, N, 4 * K), dtype=torch.float32, device=dev) if distri is None else distri
     with torch.cuda.device(dev):
-        _lib.api().evrep_dethead_train(_level_table(cls_maps, reg_maps, shapes, [1.0] * len(shapes)), len(shapes), B, nc, R,
-                                       _flags(use_dfl), _lib.ptr(scores), _lib.ptr(distri), _lib.stream_ptr())
+        _lib.api().evrep_dethead_train_typed(_level_table(cls_maps, reg_maps, shapes, [1.0] * len(shapes)), len(shapes), B, nc, R,
+                                             _flags(use_dfl), _dt(cls_maps), _lib.ptr(scores), _lib.ptr(distri), _lib.stream_ptr())
     return scores, distri
 
 
-def _backward_device(pred_scores, grad_scores, grad_distri, shapes, B, nc, R, K, use_dfl, dev, gcls=None, greg=None):
-    """The backward launch: new maps (or the given ones) for the halves whose gradient is not None."""
+def _backward_device(pred_scores, grad_scores, grad_distri, shapes, B, nc, R, K, use_dfl, dev, gcls=None, greg=None,
+                     dtype=torch.float32):
+    """The backward launch: new maps of ``dtype`` (or the given ones, whose dtype then counts) for the halves whose gradient is
+    not None.  The float32 value is rounded once to the maps' dtype at the store."""
+    given = [g for g in (gcls, greg) if g is not None]
+    if given:
+        dtype = given[0][0].dtype
+        if any(m.dtype != dtype for g in given for m in g) or dtype not in _lib.MAP_DTYPES:
+            raise ValueError("the gradient maps of a call share one dtype of float32, float16, bfloat16")
     if grad_scores is not None and gcls is None:
-        gcls = [torch.empty((B, nc, h, w), dtype=torch.float32, device=dev) for h, w in shapes]
+        gcls = [torch.empty((B, nc, h, w), dtype=dtype, device=dev) for h, w in shapes]
     if grad_distri is not None and greg is None:
-        greg = [torch.empty((B, 4 * K, h, w), dtype=torch.float32, device=dev) for h, w in shapes]
+        greg = [torch.empty((B, 4 * K, h, w), dtype=dtype, device=dev) for h, w in shapes]
     table = (_lib.DetheadGradLevel * len(shapes))()
     for l, (h, w) in enumerate(shapes):
         table[l] = _lib.DetheadGradLevel(gcls[l].data_ptr() if grad_scores is not None else None,
                                          greg[l].data_ptr() if grad_distri is not None else None, h, w)
     with torch.cuda.device(dev):
-        _lib.api().evrep_dethead_train_backward(table, len(shapes), B, nc, R, _flags(use_dfl),
-                                                _lib.ptr(pred_scores) if grad_scores is not None else None,
-                                                _lib.ptr(grad_scores), _lib.ptr(grad_distri), _lib.stream_ptr())
+        _lib.api().evrep_dethead_train_backward_typed(table, len(shapes), B, nc, R, _flags(use_dfl), _lib.MAP_DTYPES[dtype],
+                                                      _lib.ptr(pred_scores) if grad_scores is not None else None,
+                                                      _lib.ptr(grad_scores), _lib.ptr(grad_distri), _lib.stream_ptr())
     return (gcls if grad_scores is not None else None), (greg if grad_distri is not None else None)
 
 
 class _TrainOutputs(torch.autograd.Function):
-    """(pred_scores, pred_distri) of the maps; the backward is the backward launch and returns a gradient per map."""
+    """(pred_scores, pred_distri) of the maps; the backward is the backward launch and returns a gradient per map, in the maps'
+    dtype.  ``custom_fwd`` without ``cast_inputs`` leaves 16-bit maps as they are inside an autocast region (a cast to float32
+    is the launch this node saves) and ``custom_bwd`` runs the backward under the forward's autocast state; neither launch is
+    a torch operator, so autocast changes no bit of either."""
 
     @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda")
     def forward(ctx, meta, *maps):
         L, R, use_dfl = meta
         K = R + 1 if use_dfl else 1
@@ -236,12 +267,13 @@ class _TrainOutputs(torch.autograd.Function):
             scores, distri = (torch.from_numpy(a) for a in train_outputs_host(cls_maps, reg_maps, R, use_dfl))
         ctx.save_for_backward(scores)
         ctx.set_materialize_grads(False)                                 # an output the loss does not use arrives as None
-        ctx.meta = (L, R, K, use_dfl, B, nc, shapes, dev)
+        ctx.meta = (L, R, K, use_dfl, B, nc, shapes, dev, maps[0].dtype)
         return scores, distri
 
     @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_scores, grad_distri):
-        L, R, K, use_dfl, B, nc, shapes, dev = ctx.meta
+        L, R, K, use_dfl, B, nc, shapes, dev, dtype = ctx.meta
         scores, = ctx.saved_tensors
         need_c, need_r = any(ctx.needs_input_grad[1:1 + L]), any(ctx.needs_input_grad[1 + L:])
         gs = grad_scores.to(torch.float32).contiguous() if (grad_scores is not None and need_c) else None
@@ -249,12 +281,12 @@ class _TrainOutputs(torch.autograd.Function):
         gcls = greg = None
         if gs is not None or gd is not None:
             if dev.type == "cuda":
-                gcls, greg = _backward_device(scores, gs, gd, shapes, B, nc, R, K, use_dfl, dev)
+                gcls, greg = _backward_device(scores, gs, gd, shapes, B, nc, R, K, use_dfl, dev, dtype=dtype)
             else:
                 gcls, greg = train_backward_host(scores.numpy(), None if gs is None else gs.numpy(), None if gd is None else gd.numpy(),
                                                  shapes)
-                gcls = None if gcls is None else [torch.from_numpy(g) for g in gcls]
-                greg = None if greg is None else [torch.from_numpy(g) for g in greg]
+                gcls = None if gcls is None else [torch.from_numpy(g).to(dtype) for g in gcls]      # the one rounding
+                greg = None if greg is None else [torch.from_numpy(g).to(dtype) for g in greg]
         none = [None] * L
         return (None,) + tuple(gcls or none) + tuple(greg or none)
 

@@ -1182,8 +1182,33 @@ int evrep_detloss(const float *pred_scores, const float *pred_distri, const floa
  *   n, c, h, w >= 1; n * c, h * w and the rows of all levels <= EVREP_TAL_MAX_ANCHORS; tau finite and > 0; anything else, a NULL
  *   or misaligned pointer is EVREP_EINVAL before any launch.  scratch DEVICE, 256-byte aligned,
  *   evrep_detloss_cwd_workspace_bytes(levels_host, L) bytes (0 for a refused table): one double per row, rounded up to 256
- *   bytes; needs no initialisation.  Two launches, no atomics, no allocation, no wait, nothing read back. */
+ *   bytes; needs no initialisation.  Two launches, no atomics, no allocation, no wait, nothing read back.
+ *
+ * 16-BIT MAPS (training under autocast, evaluation with model.half()).  The entries that take the network's own maps have a
+ * typed twin beside them -- evrep_detloss_cwd_typed here, evrep_dethead_predict_typed, _train_typed and _train_backward_typed
+ * below -- whose level structs hold void pointers and which take a dtype code EVREP_DT_F32, EVREP_DT_F16 (IEEE binary16) or
+ * EVREP_DT_BF16 (bfloat16): one per call for the head, one for the student's maps and one for the teacher's here.
+ *   W1 widen   a 16-bit map element is widened EXACTLY to float32 at its load: float16 by IEEE conversion, bfloat16 by placing
+ *              its 16 bits on top of 16 zero bits.  Subnormals and -0.0 keep value and sign; nothing is flushed.  From there
+ *              every rule stated for float32 maps applies unchanged, so a typed entry gives the bits the float32 entry gives on
+ *              the widened maps; all forward outputs stay float32 (out here stays float64).
+ *   W2 round   the head's backward forms its float32 value as stated below and rounds it ONCE, to nearest even, to the maps'
+ *              dtype at the store: overflow gives +-inf, a NaN stays a NaN, and what is too small gives +-0 (float16: every
+ *              |x| <= 2^-25, so every float32 subnormal; bfloat16 has float32's exponent range and keeps float32 subnormals as
+ *              its own).  The result is torch's float32_tensor.to(dtype) bit for bit wherever it is no NaN.
+ *   W3 cwd     evrep_detloss_cwd_typed writes grad_s in FLOAT32 whatever the maps' dtype: an element is tau / (n * c) times a
+ *              difference of probabilities, about 1e-8 at the reference's shapes, below float16's smallest subnormal before
+ *              the loss scale multiplies it.  The caller multiplies by the incoming gradient first and rounds once after.
+ * With EVREP_DT_F32 a typed entry is the float32 entry.  Limits and refusals are those of the float32 entries; a map pointer
+ * must be aligned to ITS element size (2 bytes for the 16-bit codes); an unknown dtype code is EVREP_EINVAL before any launch.
+ * evrep_cast16_host(src, dst, n, dtype, dir): W1 (dir 0: src HOST 16-bit [n] -> dst HOST float [n]) and W2 (dir 1: float ->
+ * 16-bit) on the HOST, by the very functions the kernels use (csrc/evrep_f16.h); dtype EVREP_DT_F16 or EVREP_DT_BF16. */
+#define EVREP_DT_F32 0
+#define EVREP_DT_F16 1
+#define EVREP_DT_BF16 2
+int evrep_cast16_host(const void *src, void *dst, int64_t n, int32_t dtype, int32_t dir);
 typedef struct { const float *s; const float *t; float *grad_s; int32_t n, c, h, w; } evrep_cwd_level;
+typedef struct { const void *s; const void *t; float *grad_s; int32_t n, c, h, w; } evrep_cwd_level_typed;
 #define EVREP_DISTILL_MAX_CLASSES 2048
 #define EVREP_CWD_MAX_LEVELS 3
 #define EVREP_CWD_STAGE 4096
@@ -1196,6 +1221,9 @@ int evrep_detloss_distill(const float *pred_scores, const float *pred_distri, co
 size_t evrep_detloss_cwd_workspace_bytes(const evrep_cwd_level *levels_host, int32_t L);
 int evrep_detloss_cwd(const evrep_cwd_level *levels_host, int32_t L, double tau, uint32_t flags, double *out, void *scratch,
                       void *stream);
+size_t evrep_detloss_cwd_typed_workspace_bytes(const evrep_cwd_level_typed *levels_host, int32_t L);
+int evrep_detloss_cwd_typed(const evrep_cwd_level_typed *levels_host, int32_t L, double tau, uint32_t flags, int32_t s_dtype,
+                            int32_t t_dtype, double *out, void *scratch, void *stream);
 
 /* What Detect.forward does behind its last convolutions (ev-YOLOv6/yolov6/models/effidehead.py:89-173, with
  * generate_anchors(is_eval = True) and dist2bbox(xywh) behind it): the per-level maps of cls_preds / reg_preds, NCHW as the
@@ -1233,9 +1261,14 @@ int evrep_detloss_cwd(const evrep_cwd_level *levels_host, int32_t L, double tau,
  * pointer not aligned to 4 bytes is EVREP_EINVAL before any launch.  One launch each: a workgroup stages a tile of
  * EVREP_DETHEAD_TILE consecutive anchors of one (image, level) in LDS and moves its rows as one contiguous span, 16 bytes per
  * lane between the span's 16-byte boundaries.  No scratch, no atomics, no allocation, no wait for the device, nothing read
- * back: the calls may be captured into a graph, and two calls give equal bits. */
+ * back: the calls may be captured into a graph, and two calls give equal bits.
+ * The *_typed entries (16-BIT MAPS above): the maps cls_l / reg_l / gcls_l / greg_l of a call share ONE dtype, given by its
+ * code; W1 stands in front of E1-E4 and T1, T2 becomes "the exact widening" instead of "a bit copy", and W2 stands behind both
+ * backward rules (greg_l is grad_distri rounded once).  pred, pred_scores, pred_distri, grad_scores, grad_distri stay float32. */
 typedef struct { const float *cls; const float *reg; int32_t h, w; float stride; } evrep_dethead_level;
 typedef struct { float *gcls; float *greg; int32_t h, w; } evrep_dethead_grad_level;
+typedef struct { const void *cls; const void *reg; int32_t h, w; float stride; } evrep_dethead_level_typed;
+typedef struct { void *gcls; void *greg; int32_t h, w; } evrep_dethead_grad_level_typed;
 #define EVREP_DETHEAD_USE_DFL 1u
 #define EVREP_DETHEAD_MAX_LEVELS 8
 #define EVREP_DETHEAD_TILE 64
@@ -1246,6 +1279,13 @@ int evrep_dethead_train(const evrep_dethead_level *levels_host, int32_t L, int32
 int evrep_dethead_train_backward(const evrep_dethead_grad_level *levels_host, int32_t L, int32_t B, int32_t nc, int32_t R,
                                  uint32_t flags, const float *pred_scores, const float *grad_scores, const float *grad_distri,
                                  void *stream);
+int evrep_dethead_predict_typed(const evrep_dethead_level_typed *levels_host, int32_t L, int32_t B, int32_t nc, int32_t R,
+                                uint32_t flags, int32_t dtype, float *pred, void *stream);
+int evrep_dethead_train_typed(const evrep_dethead_level_typed *levels_host, int32_t L, int32_t B, int32_t nc, int32_t R,
+                              uint32_t flags, int32_t dtype, float *pred_scores, float *pred_distri, void *stream);
+int evrep_dethead_train_backward_typed(const evrep_dethead_grad_level_typed *levels_host, int32_t L, int32_t B, int32_t nc,
+                                       int32_t R, uint32_t flags, int32_t dtype, const float *pred_scores,
+                                       const float *grad_scores, const float *grad_distri, void *stream);
 
 /* What is left of the training step behind loss.backward() (ev-YOLOv6/yolov6/core/engine.py:547-552): scaler.step(optimizer)
  * with torch's Nesterov SGD behind it (solver/build.py), scaler.update() and ModelEMA.update(model) (yolov6/utils/ema.py:30-41),

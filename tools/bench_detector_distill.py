@@ -2,7 +2,10 @@
 """Times of the distillation losses (detector_distill.distill_batch and distill_cw, forward and backward) beside the
 reference's route and beside loss_batch on the same shape, in the same run.
 
-    python tools/bench_detector_distill.py [--reps 50] [--batch 32] [--out FILE.json]
+    python tools/bench_detector_distill.py [--reps 50] [--batch 32] [--out FILE.json] [--dtype float32|float16|bfloat16]
+
+With --dtype float16 / bfloat16 the tool times distill_cw on a 16-bit model's maps instead: the cast route (.float() per map,
+the float32 entry, autograd's cast back) against the maps as they are, and a copy of the typed route's bytes.
 
 distill_batch: B = 32 images at 640 x 640 (A = 8400 anchors), nc in {2, 80}, 50 labels per image, T = 20; the targets are
 assign_batch's on tests/detector_assign_cases' head, the logits tests/detector_loss_cases', the teacher
@@ -105,11 +108,46 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dtype", choices=("float32", "float16", "bfloat16"), default="float32",
+                    help="the feature maps' dtype; a 16-bit one times distill_cw's cast route against the typed entry instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_detector_distill needs the GPU: no time is taken without one")
     dev, B, K = torch.device("cuda:0"), args.batch, R + 1
     rows, n_lab = [], 50
+    if args.dtype != "float32":
+        # the channel-wise term on a 16-bit model's maps: (a) today's route -- .float() per map (six launches), the float32
+        # entry, autograd's cast of the three gradients back -- against (b) the maps as they are, and (c) a copy of (b)'s bytes
+        dtype = getattr(torch, args.dtype)
+        rng = np.random.default_rng(8200)
+        s0 = [torch.from_numpy(rng.normal(0, 1.5, (B,) + sh).astype(np.float32)).to(dev).to(dtype) for sh in FEATS]
+        t0 = [(x.float() + 0.7 * torch.randn_like(x.float())).to(dtype) for x in s0]
+
+        def cw(cast, scale=65536.0):
+            s = [x.detach().requires_grad_(True) for x in s0]
+            loss = dd.distill_cw([x.float() for x in s], [x.float() for x in t0]) if cast else dd.distill_cw(s, t0)
+            (loss * scale).backward()
+            return loss.detach(), [x.grad for x in s]
+        (la, ga), (lb, gb) = cw(True), cw(False)
+        same = bool(la.item() == lb.item()) and all(a.dtype == b.dtype == dtype and torch.equal(a.view(torch.int16), b.view(torch.int16))
+                                                    for a, b in zip(ga, gb))
+        t_a, t_b = event_us(lambda: cw(True), args.reps), event_us(lambda: cw(False), args.reps)
+        with torch.no_grad():
+            t_a_fwd = event_us(lambda: dd.distill_cw([x.float() for x in s0], [x.float() for x in t0]), args.reps)
+            t_b_fwd = event_us(lambda: dd.distill_cw(s0, t0), args.reps)
+        kern, launches = profiled(lambda: cw(False), 10)
+        _, launches_a = profiled(lambda: cw(True), 10)
+        nbytes = sum(x.numel() for x in s0) * (2 + 2 + 4)
+        tc = copy_us(nbytes, args.reps)
+        row = {"what": "distill_cw", "dtype": args.dtype, "B": B, "maps": [list(sh) for sh in FEATS], "reps": args.reps,
+               "a_cast_fwd_bwd_us": round(t_a, 1), "b_typed_fwd_bwd_us": round(t_b, 1), "a_cast_fwd_us": round(t_a_fwd, 1),
+               "b_typed_fwd_us": round(t_b_fwd, 1), "c_copy_us": round(tc, 1), "bytes": nbytes, "kernels_us": kern,
+               "launches": {"typed": launches, "cast": launches_a}, "b_below_a": bool(t_b < t_a), "routes_agree_bit_for_bit": same}
+        print(json.dumps(row), flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(row) + "\n")
+        return
     for nc in (2, 80):
         scores_h, _, anc_h = acases.head(8000 + nc, B, S, nc)
         c = dcases.with_teacher(lcases.base(8001 + nc, S=S, B=B, nc=1), 8002 + nc, T=T, epoch=EPOCH, max_epoch=MAX_EPOCH)

@@ -2,7 +2,10 @@
 """Times of the head's decode and tail (detector_head.predict / train_outputs / predict_batch) beside the reference's route, in
 the same run.
 
-    python tools/bench_detector_head.py [--reps 50] [--out FILE.json]
+    python tools/bench_detector_head.py [--reps 50] [--out FILE.json] [--dtype float32|float16|bfloat16]
+
+With --dtype float16 / bfloat16 the tool times a 16-bit model's maps instead (amp_rows below): the cast route against the typed
+entry.  The default float32 gives what is described here.
 
 B = 32 images at 640 x 640, three levels (strides 8, 16, 32: N = 8400) and four levels (strides 8 .. 64: N = 8500), nc in
 {2, 80}, reg_max = 16.  Medians over `reps` runs after warm-up, in us.  Device calls are bracketed by HIP events; the torch
@@ -123,18 +126,81 @@ def reference_train(cls_maps, reg_maps):
     return scores, distri
 
 
+def amp_rows(args, dev, B, K, dtype):
+    """--dtype float16 / bfloat16: a 16-bit model's maps.  (a) today's route for them -- .float() per map, the float32 entry,
+    and in training autograd's cast of every gradient map back to the maps' dtype -- against (b) the typed entry on the 16-bit
+    maps as they are, with (c) a device copy of half the bytes (b) reads plus writes; evaluation (predict), the training
+    forward, and forward plus backward.  HIP events around the whole of each; the three launches apart from torch.profiler."""
+    rows = []
+    for strides in ((8, 16, 32), (8, 16, 32, 64)):
+        shapes = [(S // s, S // s) for s in strides]
+        N = sum(h * w for h, w in shapes)
+        for nc in (2, 80):
+            g = torch.Generator(device=dev).manual_seed(100 * len(strides) + nc)
+            cls = [(torch.randn((B, nc, h, w), device=dev, generator=g) * 2.0 - 5.0).to(dtype) for h, w in shapes]
+            reg = [(torch.randn((B, 4 * K, h, w), device=dev, generator=g) * 2.0).to(dtype) for h, w in shapes]
+            out = torch.empty((B, N, 5 + nc), device=dev)
+            gs, gd = torch.randn((B, N, nc), device=dev, generator=g), torch.randn((B, N, 4 * K), device=dev, generator=g)
+            cls_g, reg_g = [c.clone().requires_grad_(True) for c in cls], [r.clone().requires_grad_(True) for r in reg]
+            in_bytes, out_bytes = sum(t.numel() * 2 for t in cls + reg), out.numel() * 4
+            half = (in_bytes + out_bytes) // 2
+            src, dst = torch.empty(half, dtype=torch.uint8, device=dev), torch.empty(half, dtype=torch.uint8, device=dev)
+
+            def clear():
+                for t in cls_g + reg_g:
+                    t.grad = None
+
+            def train_cast():
+                clear()
+                torch.autograd.backward(list(dh.train_outputs([c.float() for c in cls_g], [r.float() for r in reg_g], R, True)), [gs, gd])
+
+            def train_typed():
+                clear()
+                torch.autograd.backward(list(dh.train_outputs(cls_g, reg_g, R, True)), [gs, gd])
+
+            train_cast()
+            want_g = [t.grad.clone() for t in cls_g + reg_g]
+            train_typed()
+            same = all(t.grad.dtype == dtype and torch.equal(t.grad.view(torch.int16), w_.view(torch.int16)) for t, w_ in zip(cls_g + reg_g, want_g))
+            same = same and torch.equal(dh.predict(cls, reg, strides, R, True).view(torch.int32),
+                                        dh.predict([c.float() for c in cls], [r.float() for r in reg], strides, R, True).view(torch.int32))
+            t = {"a_predict_cast_us": event_us(lambda: dh.predict([c.float() for c in cls], [r.float() for r in reg], strides, R, True, out=out), args.reps),
+                 "b_predict_typed_us": event_us(lambda: dh.predict(cls, reg, strides, R, True, out=out), args.reps),
+                 "c_copy_us": event_us(lambda: dst.copy_(src), args.reps),
+                 "a_train_cast_fwd_bwd_us": event_us(train_cast, args.reps), "b_train_typed_fwd_bwd_us": event_us(train_typed, args.reps)}
+            with torch.no_grad():
+                t["a_train_cast_fwd_us"] = event_us(lambda: dh.train_outputs([c.float() for c in cls], [r.float() for r in reg], R, True), args.reps)
+                t["b_train_typed_fwd_us"] = event_us(lambda: dh.train_outputs(cls, reg, R, True), args.reps)
+            kernels = kernel_us(lambda: dh.predict(cls, reg, strides, R, True, out=out))
+            kernels.update(kernel_us(train_typed))
+            row = {"dtype": str(dtype).replace("torch.", ""), "B": B, "levels": len(strides), "N": N, "nc": nc, "reps": args.reps}
+            row.update({k: round(v, 1) for k, v in t.items()})
+            row.update({"bytes_read_plus_written_mb": round((in_bytes + out_bytes) / 1e6, 1), "kernels_us": kernels,
+                        "b_below_a_predict": bool(t["b_predict_typed_us"] < t["a_predict_cast_us"]),
+                        "b_below_a_train": bool(t["b_train_typed_fwd_bwd_us"] < t["a_train_cast_fwd_bwd_us"]),
+                        "b_over_c": round(t["b_predict_typed_us"] / t["c_copy_us"], 2), "routes_agree_bit_for_bit": bool(same)})
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            del cls, reg, out, src, dst, gs, gd, cls_g, reg_g, want_g
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dtype", choices=("float32", "float16", "bfloat16"), default="float32",
+                    help="the maps' dtype; a 16-bit one times the cast route against the typed entry instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_detector_head needs the GPU: no time is taken without one")
     dev, B, K = torch.device("cuda:0"), args.batch, R + 1
     proj = torch.linspace(0, R, K, device=dev).view(1, K, 1, 1)
     rows = []
-    for strides in ((8, 16, 32), (8, 16, 32, 64)):
+    if args.dtype != "float32":
+        rows = amp_rows(args, dev, B, K, getattr(torch, args.dtype))
+    for strides in ((8, 16, 32), (8, 16, 32, 64)) if args.dtype == "float32" else ():
         shapes = [(S // s, S // s) for s in strides]
         N = sum(h * w for h, w in shapes)
         for nc in (2, 80):
