@@ -125,6 +125,10 @@ SYMBOLS = {
     "evrep_nms": _st([_vp, _i32, _i32, _i32, _f32, _f64, ctypes.c_uint32, _I32P, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "evrep_det_match": _st([_vp, _vp, _i32, _i32, _vp, _i64, _vp, _i32, _i32, ctypes.POINTER(ctypes.c_float), _i32, ctypes.c_uint32, _vp, _i32,
                             _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "evrep_det_ap_workspace_bytes": (ctypes.c_size_t, [_i64, _i32, _i32]),
+    "evrep_det_ap": _st([_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                         ctypes.c_size_t, _vp]),
+    "evrep_det_ap_gather": _st([_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "evrep_det_targets_pad": _st([_vp, _i64, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "evrep_tal_workspace_bytes": (ctypes.c_size_t, [_i32, _i32, _i32]),
     "evrep_tal_assign": _st([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp,
@@ -194,6 +198,11 @@ NMS_MAX_DET, NMS_MAX_CLASSES, NMS_MAX_ROWS = 1024, 4096, 1 << 24
 DETEVAL_NATIVE, DETEVAL_SKIP_EMPTY = 1, 2
 DETEVAL_MAX_LABELS, DETEVAL_MAX_T, DETEVAL_MAX_TARGETS = 1024, 16, 1 << 24
 DETEVAL_ST_LABEL_OVERFLOW, DETEVAL_ST_BAD_CLASS, DETEVAL_ST_BAD_COUNT = 1, 2, 4
+# evrep_det_ap: the rows of a radix tile and of a scan tile, the status bits, the points of the curves and of compute_ap
+AP_SORT_TILE, AP_SCAN_TILE = 2048, 512
+AP_GATHER_CHUNK, AP_GATHER_IMAGES = 1024, 256      # evrep_det_ap_gather: targets / images per round of its second launch, images per round of its first
+AP_ST_BAD_CLASS, AP_ST_NAN_CONF = 1, 2
+AP_PX, AP_X = 1000, 101
 # evrep_det_targets_pad / evrep_tal_assign: flag, limits, per-image status bits
 TAL_F32_OUT = 1
 TAL_MAX_TOPK, TAL_MAX_LABELS, TAL_MAX_CLASSES, TAL_MAX_ANCHORS, TAL_MAX_POWER = 64, 1024, 4096, 1 << 24, 16

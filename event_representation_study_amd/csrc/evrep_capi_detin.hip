@@ -1,6 +1,7 @@
 // evrep_capi_detin.hip -- the extern "C" surface, part 10: the detector's input batch (evrep_detin.hip), its form for frames
 // of different sizes with the tap tables made on the device (evrep_detin_frames.hip), and the detector's output, the batched
-// non_max_suppression (evrep_nms.hip), the scoring of its detections against the labels (evrep_deteval.hip), and the training
+// non_max_suppression (evrep_nms.hip), the scoring of its detections against the labels (evrep_deteval.hip) with the average
+// precision behind it (evrep_detap.hip), and the training
 // targets, label padding and the task-aligned assigner (evrep_assign.hip) with the ATSS assigner of the warm-up epochs
 // (evrep_atss.hip), and the loss terms with their gradients
 // (evrep_detloss.hip), and the head's decode and tail in front of all of them (evrep_dethead.hip), and the parameter update
@@ -11,6 +12,7 @@
 #include "evrep_detin_frames.hip"
 #include "evrep_nms.hip"
 #include "evrep_deteval.hip"
+#include "evrep_detap.hip"
 #include "evrep_assign.hip"
 #include "evrep_atss.hip"
 #include "evrep_detloss.hip"
@@ -206,6 +208,145 @@ int evrep_det_match(const float *det, const int32_t *count, int32_t B, int32_t m
     a.skip_empty = (flags & EVREP_DETEVAL_SKIP_EMPTY) ? 1 : 0;
     k_det_match<<<(unsigned)B, kDistThreads, 0, as_stream(stream_)>>>(a);
     LAUNCH_CHECK("k_det_match");
+    return EVREP_OK;
+}
+
+static inline bool ap_shape_ok(int64_t n, int32_t T, int32_t nc) {
+    return n >= 0 && n < ((int64_t)1 << 31) && T >= 1 && T <= EVREP_DETEVAL_MAX_T && nc >= 1 && nc <= EVREP_NMS_MAX_CLASSES;
+}
+static inline int64_t ap_sort_tiles(int64_t n) { return (n + kApSortTile - 1) / kApSortTile; }
+static inline int64_t ap_scan_tiles(int64_t n) { return (n + kApScanTile - 1) / kApScanTile; }
+
+// the workspace of evrep_det_ap: the two (key, row) buffers of the sort, its (digit, tile) table, the class counts and
+// starts, the sorted confidences, the counts and running maxima per (row, threshold), and the scan tiles' words
+static size_t ap_layout(void *ws, int64_t n, int32_t T, int32_t nc, ApArgs *a) {
+    Carver c(ws);
+    const size_t rows = (size_t)n, st = (size_t)ap_scan_tiles(n);
+    unsigned long long *key_a = c.take<unsigned long long>(rows * 8), *key_b = c.take<unsigned long long>(rows * 8);
+    uint32_t *idx_a = c.take<uint32_t>(rows * 4), *idx_b = c.take<uint32_t>(rows * 4);
+    uint32_t *hist = c.take<uint32_t>(256 * (size_t)ap_sort_tiles(n) * 4);
+    uint32_t *cnt_p = c.take<uint32_t>(((size_t)nc + 1) * 4), *cnt_l = c.take<uint32_t>(((size_t)nc + 1) * 4);
+    uint32_t *seg = c.take<uint32_t>(((size_t)nc + 2) * 4);
+    float *sconf = c.take<float>(rows * 4);
+    uint32_t *cum = c.take<uint32_t>(rows * T * 4);
+    double *mpre = c.take<double>(rows * T * 8);
+    uint32_t *tsum = c.take<uint32_t>(st * T * 4);
+    double *thead = c.take<double>(st * T * 8), *tcarry = c.take<double>(st * T * 8);
+    uint32_t *tcls_head = c.take<uint32_t>(st * 4), *tcls_tail = c.take<uint32_t>(st * 4);
+    if (a) {
+        a->key_a = key_a; a->key_b = key_b; a->idx_a = idx_a; a->idx_b = idx_b; a->hist = hist; a->cnt_p = cnt_p; a->cnt_l = cnt_l;
+        a->seg = seg; a->sconf = sconf; a->cum = cum; a->mpre = mpre; a->tsum = tsum; a->thead = thead; a->tcarry = tcarry;
+        a->tcls_head = tcls_head; a->tcls_tail = tcls_tail;
+    }
+    return c.off;
+}
+
+size_t evrep_det_ap_workspace_bytes(int64_t n, int32_t T, int32_t nc) {
+    return ap_shape_ok(n, T, nc) ? ap_layout(nullptr, n, T, nc, nullptr) : 0;
+}
+
+int evrep_det_ap_gather(const uint8_t *correct, const float *conf_cls, const int32_t *count, int32_t B, int32_t max_det, int32_t T,
+                        const float *targets, int64_t n_t, uint8_t *tp, float *conf, float *pred_cls, int64_t cap_n,
+                        float *target_cls, int64_t cap_m, int64_t *cursor, void *stream_) {
+    if (B < 1 || B > 65535 || max_det < 1 || max_det > EVREP_NMS_MAX_DET || T < 1 || T > EVREP_DETEVAL_MAX_T) return EVREP_EINVAL;
+    if (n_t < 0 || n_t > EVREP_DETEVAL_MAX_TARGETS || cap_m < 0 || cap_m >= ((int64_t)1 << 31)) return EVREP_EINVAL;
+    if (cap_n < (int64_t)B * max_det || cap_n >= ((int64_t)1 << 31)) return EVREP_EINVAL;
+    if (bad_ptr(correct, 1) || bad_ptr(conf_cls, 4) || bad_ptr(count, 4) || bad_ptr(cursor, 8)) return EVREP_EINVAL;
+    if (bad_ptr(tp, 1) || bad_ptr(conf, 4) || bad_ptr(pred_cls, 4)) return EVREP_EINVAL;
+    if (n_t > 0 ? bad_ptr(targets, 4) : misaligned(targets, 4)) return EVREP_EINVAL;
+    if (n_t > 0 && cap_m > 0 ? bad_ptr(target_cls, 4) : misaligned(target_cls, 4)) return EVREP_EINVAL;
+    ApGatherArgs g;
+    g.correct = correct; g.conf_cls = conf_cls; g.count = count; g.targets = targets; g.tp = tp; g.conf = conf; g.pcls = pred_cls;
+    g.tcls = target_cls; g.cursor = cursor; g.n_t = n_t; g.cap_n = cap_n; g.cap_m = target_cls ? cap_m : 0;
+    g.B = B; g.max_det = max_det; g.T = T;
+    hipStream_t stream = as_stream(stream_);
+    k_ap_gather_rows<<<(unsigned)B, kThreads, 0, stream>>>(g);
+    LAUNCH_CHECK("k_ap_gather_rows");
+    k_ap_gather_finish<<<1, kDistThreads, 0, stream>>>(g);
+    LAUNCH_CHECK("k_ap_gather_finish");
+    return EVREP_OK;
+}
+
+int evrep_det_ap(const uint8_t *tp, const float *conf, const float *pred_cls, const float *target_cls, int64_t n, int64_t m,
+                 int32_t T, int32_t nc, const int64_t *counts_dev, const double *tables, double *p, double *r, double *f1,
+                 double *ap, int64_t *n_labels, int64_t *n_pred, uint32_t *any_correct, uint32_t *status, void *workspace,
+                 size_t workspace_bytes, void *stream_) {
+    if (!ap_shape_ok(n, T, nc) || m < 0 || m >= ((int64_t)1 << 31)) return EVREP_EINVAL;
+    if (n > 0 ? (bad_ptr(tp, 1) || bad_ptr(conf, 4) || bad_ptr(pred_cls, 4)) : (misaligned(conf, 4) || misaligned(pred_cls, 4)))
+        return EVREP_EINVAL;
+    if (m > 0 ? bad_ptr(target_cls, 4) : misaligned(target_cls, 4)) return EVREP_EINVAL;
+    if (misaligned(counts_dev, 8) || bad_ptr(tables, 8)) return EVREP_EINVAL;
+    if (bad_ptr(p, 8) || bad_ptr(r, 8) || bad_ptr(f1, 8) || bad_ptr(ap, 8) || bad_ptr(n_labels, 8) || bad_ptr(n_pred, 8)) return EVREP_EINVAL;
+    if (bad_ptr(any_correct, 4) || bad_ptr(status, 4) || bad_ptr(workspace, 256)) return EVREP_EINVAL;
+    if (workspace_bytes < ap_layout(nullptr, n, T, nc, nullptr)) return EVREP_EWORKSPACE;
+    ApArgs a;
+    memset(&a, 0, sizeof(a));
+    a.tp = tp; a.conf = conf; a.pcls = pred_cls; a.tcls = target_cls; a.counts_dev = counts_dev; a.tables = tables;
+    a.p = p; a.r = r; a.f1 = f1; a.ap = ap; a.n_labels = n_labels; a.n_pred = n_pred; a.any_correct = any_correct; a.status = status;
+    a.n = n; a.m = m; a.T = T; a.nc = nc;
+    ap_layout(workspace, n, T, nc, &a);
+    hipStream_t stream = as_stream(stream_);
+    const size_t curve = (size_t)nc * kApPx * 8;
+    const struct { void *at; size_t bytes; const char *what; } zero[] = {
+        {p, curve, "hipMemsetAsync(p)"}, {r, curve, "hipMemsetAsync(r)"}, {f1, curve, "hipMemsetAsync(f1)"},
+        {ap, (size_t)nc * T * 8, "hipMemsetAsync(ap)"}, {any_correct, 4, "hipMemsetAsync(any_correct)"}, {status, 4, "hipMemsetAsync(status)"},
+        {a.cnt_p, ((size_t)nc + 1) * 4, "hipMemsetAsync(cnt_p)"}, {a.cnt_l, ((size_t)nc + 1) * 4, "hipMemsetAsync(cnt_l)"}};
+    for (const auto &z : zero) {
+        const int rc = hip_check(hipMemsetAsync(z.at, 0, z.bytes, stream), z.what);
+        if (rc != EVREP_OK) return rc;
+    }
+    const auto spread = [](int64_t items) {                             // workgroups of a grid-stride launch
+        const int64_t need = (items + kThreads - 1) / kThreads;
+        return (unsigned)(need < 1024 ? need : 1024);
+    };
+    if (n > 0) {
+        k_ap_keys<<<spread(n), kThreads, 0, stream>>>(a);
+        LAUNCH_CHECK("k_ap_keys");
+    }
+    if (m > 0) {
+        k_ap_targets<<<spread(m), kThreads, 0, stream>>>(a);
+        LAUNCH_CHECK("k_ap_targets");
+    }
+    k_ap_segments<<<1, kDistThreads, 0, stream>>>(a);
+    LAUNCH_CHECK("k_ap_segments");
+    if (n == 0) return EVREP_OK;
+    ApSortArgs s;
+    s.hist = a.hist; s.tiles = (int32_t)ap_sort_tiles(n);
+    const int passes = 4 + (nc + 1 <= 256 ? 1 : 2);                     // the 32 bits of the confidence, then the class's
+    for (int pass = 0; pass < passes; ++pass) {
+        const bool even = (pass & 1) == 0;
+        s.key_in = even ? a.key_a : a.key_b; s.idx_in = even ? a.idx_a : a.idx_b;
+        s.key_out = even ? a.key_b : a.key_a; s.idx_out = even ? a.idx_b : a.idx_a;
+        s.shift = 8 * pass;
+        k_ap_radix_count<<<(unsigned)s.tiles, kThreads, 0, stream>>>(a, s);
+        LAUNCH_CHECK("k_ap_radix_count");
+        k_ap_radix_scan<<<1, kDistThreads, 0, stream>>>(s);
+        LAUNCH_CHECK("k_ap_radix_scan");
+        k_ap_radix_scatter<<<(unsigned)s.tiles, kThreads, 0, stream>>>(a, s);
+        LAUNCH_CHECK("k_ap_radix_scatter");
+    }
+    const unsigned long long *key = (passes & 1) ? a.key_b : a.key_a;
+    const uint32_t *idx = (passes & 1) ? a.idx_b : a.idx_a;
+    const unsigned wave_tiles = (unsigned)((ap_scan_tiles(n) + kWaves - 1) / kWaves);
+    k_ap_cum<false><<<wave_tiles, kThreads, 0, stream>>>(a, idx);
+    LAUNCH_CHECK("k_ap_cum<sums>");
+    k_ap_cum_scan<<<1, kWave, 0, stream>>>(a);
+    LAUNCH_CHECK("k_ap_cum_scan");
+    if (m == 0) return EVREP_OK;                                        // no class has a label: every curve stays zero
+    k_ap_cum<true><<<wave_tiles, kThreads, 0, stream>>>(a, idx);
+    LAUNCH_CHECK("k_ap_cum<write>");
+    k_ap_sorted_conf<<<(unsigned)((n + kThreads - 1) / kThreads), kThreads, 0, stream>>>(a, idx);
+    LAUNCH_CHECK("k_ap_sorted_conf");
+    k_ap_max<false><<<wave_tiles, kThreads, 0, stream>>>(a, key);
+    LAUNCH_CHECK("k_ap_max<heads>");
+    k_ap_max_carry<<<1, kWave, 0, stream>>>(a);
+    LAUNCH_CHECK("k_ap_max_carry");
+    k_ap_max<true><<<wave_tiles, kThreads, 0, stream>>>(a, key);
+    LAUNCH_CHECK("k_ap_max<write>");
+    k_ap_curves<<<dim3((kApPx + kThreads - 1) / kThreads, (unsigned)nc), kThreads, 0, stream>>>(a);
+    LAUNCH_CHECK("k_ap_curves");
+    k_ap_area<<<(unsigned)(((int64_t)nc * T + kWaves - 1) / kWaves), kThreads, 0, stream>>>(a);
+    LAUNCH_CHECK("k_ap_area");
     return EVREP_OK;
 }
 

@@ -5,9 +5,10 @@ and the labels to the source frame, and calls ``yolov6/utils/metrics.py:process_
 ``.cpu().numpy()`` -> ``argsort`` -> ``np.unique`` -> ``np.unique``) and optionally ``ConfusionMatrix.process_batch``.  Here
 ``match_batch`` does all of it for the padded batch ``nms_batch`` returned in ONE launch of ``evrep_det_match``
 (csrc/evrep_deteval.hip: one workgroup per image), with no host read; ``DetectionEvaluator`` keeps the per-batch results on the
-device and reads them back once, in ``compute()``, where the reference's ``ap_per_class`` (numpy, on the host, once per
-evaluation) turns them into mAP.  ``match_host`` is the same rules in numpy float32: what the tests hold the kernel to bit
-for bit, and the CPU route.
+device.  ``compute()`` reads them back once and runs the reference's ``ap_per_class`` (its numpy statements, on the host: the
+numpy route); ``compute_device()`` turns them into mAP where they lie (``evrep_det_ap_gather`` and ``evrep_det_ap``,
+csrc/evrep_detap.hip: the device route, rules A1-A7 below) and reads back the small result.  ``match_host`` is the same rules
+in numpy float32: what the tests hold the kernel to bit for bit, and the CPU route; ``ap_host`` is that for A1-A7.
 
 The rules (include/evrep.h states them with the C entry point).  Per image b the detections are rows ``0 .. count[b]-1`` of
 ``det[b]``, ``[x1, y1, x2, y2, conf, cls]`` in NMS order; the labels are the rows of ``targets`` whose column 0 equals b, in
@@ -39,6 +40,30 @@ outside ``[0, max_det]`` is clamped and sets ``ST_BAD_COUNT``.
 
 The geometry is pinned to the reference's own ``Evaler.scale_coords`` and ``xywh2xyxy`` by tests/golden/detector_eval.npz, as
 ``process_batch``, ``ConfusionMatrix.process_batch`` and ``ap_per_class`` are (inputs without label ties).
+
+Average precision, the device route and ``ap_host`` (include/evrep.h states the rules with evrep_det_ap).  Inputs: tp (n, T)
+bool, conf (n,), pred_cls (n,), target_cls (m,) float32, nc.  Every float64 statement is one IEEE operation rounded on its own
+(nothing fused, no float atomic, no reassociation): the same bits from run to run.
+
+A1. Order: descending ``conf``; rows of equal confidence keep array order (stable; ``-0.0`` equals ``+0.0``), and array order is
+    (batch, image, detection), the layout ``compute()`` builds.  The declared TIE rule: the reference's ``argsort(-conf)`` is
+    numpy's unstable sort and leaves the curves open where two rows of a class tie.
+A2. Classes: class c in ``[0, nc)`` owns the rows with ``pred_cls == c`` and ``n_l[c]`` targets.  A class outside ``[0, nc)`` or
+    not integral sets ``AP_ST_BAD_CLASS`` and takes part in nothing; a NaN confidence sets ``AP_ST_NAN_CONF`` (its class's rows
+    are then unspecified).
+A3. Counts: at a class's k-th row (1-based) ``tpc[k, j]`` = the integer count of true ``tp[., j]`` among its first k rows,
+    ``recall = double(tpc) / double(n_l)`` (``n_l + 1e-16`` is ``n_l`` in float64), ``precision = double(tpc) / double(k)``.  A
+    class with ``n_p == 0`` or ``n_l == 0`` has all-zero rows in every output.
+A4. Curves: ``px = np.linspace(0, 1, 1000)`` (uploaded, not recomputed); ``r[c] = interp(-px, -conf_c, recall[:, 0], left=0)``,
+    ``p[c] = interp(-px, -conf_c, precision[:, 0], left=1)``, ``conf_c`` widened to float64.
+A5. ``interp(x, xp, fp, left, right=fp[-1])``: ``x < xp[0]`` -> left; ``x > xp[-1]`` -> right; else j the LARGEST index with
+    ``xp[j] <= x``: the last -> ``fp[-1]``; ``xp[j] == x`` -> ``fp[j]``; else
+    ``((fp[j+1] - fp[j]) / (xp[j+1] - xp[j])) * (x - xp[j]) + fp[j]``.
+A6. ``compute_ap`` per (class, threshold): ``mrec = [0, recall[:, j], recall[-1, j] + 0.01]``, ``mpre = [1, precision[:, j], 0]``
+    replaced by its running maximum from the right, ``y = interp(linspace(0, 1, 101), mrec, mpre)``,
+    ``ap = sum_i (d_i * (y_i + y_{i+1})) / 2.0`` with ``d = np.diff(linspace(0, 1, 101))``, added in ascending i one at a time
+    (numpy's ``trapz`` adds pairwise: within 2.2e-14 of it).
+A7. ``f1 = ((2 * p) * r) / ((p + r) + 1e-16)``.
 
 Not mirrored: plots and ``print``; pycocotools' evaluation; ``scale_exact=True``; half-precision input.
 """
@@ -386,9 +411,16 @@ def compute_ap(recall, precision):
     return ap, mpre, mrec
 
 
-def ap_per_class(tp, conf, pred_cls, target_cls):
+def ap_per_class(tp, conf, pred_cls, target_cls, nc=None):
     """``metrics.ap_per_class`` without its plots: (p, r, ap, f1, unique_classes int32); p, r, f1 are (classes, 1000) curves
-    over confidence, ap is (classes, T).  The reference's numpy statements, on the host, once per evaluation."""
+    over confidence, ap is (classes, T).  numpy arrays: the reference's numpy statements, on the host.  CUDA tensors: the device
+    route (``ap_device``, rules A1-A7), the small result read back once and restricted to the classes present in
+    ``target_cls``; ``nc`` (the number of classes) defaults to the largest target class + 1, which costs no read when
+    ``target_cls`` lives on the host and one scalar read in front of the launches when it lives on the device.  On the device
+    route a NaN confidence raises ValueError (the status word comes back in the same read); a predicted class outside
+    ``[0, nc)`` is, as in the reference, a class without labels and takes part in nothing."""
+    if any(isinstance(v, torch.Tensor) and v.is_cuda for v in (tp, conf, pred_cls)):
+        return _ap_per_class_device(tp, conf, pred_cls, target_cls, nc)
     i = np.argsort(-conf)
     tp, conf, pred_cls = tp[i], conf[i], pred_cls[i]
     unique_classes = np.unique(target_cls)
@@ -420,11 +452,206 @@ def summarize(stats, nc, seen):
     if not (len(stats) and stats[0].any()):
         return 0.0, 0.0
     p, r, ap, f1, ap_class = ap_per_class(*stats)
+    nt = np.bincount(stats[3].astype(np.int64), minlength=nc)
+    return _summary(p, r, ap, f1, ap_class, nt, seen)
+
+
+def _summary(p, r, ap, f1, ap_class, nt, seen):
+    """evaler.py:266-283: the means at the best-F1 confidence, behind either route to ``p, r, ap, f1``."""
     best = len(f1.mean(0)) - f1.mean(0)[::-1].argmax() - 1
     ap50, ap_mean = ap[:, 0], ap.mean(1)
-    nt = np.bincount(stats[3].astype(np.int64), minlength=nc)
     return dict(p=p, r=r, ap=ap, f1=f1, ap_class=ap_class, best_f1_index=int(best), mp=p[:, best].mean(), mr=r[:, best].mean(),
                 map50=ap50.mean(), map=ap_mean.mean(), nt=nt, seen=int(seen))
+
+
+# ------------------------------------------------------------------------------------- AP: the declared rules, host and device
+AP_ST_BAD_CLASS, AP_ST_NAN_CONF = _lib.AP_ST_BAD_CLASS, _lib.AP_ST_NAN_CONF
+_AP_STATUS_TEXT = ((AP_ST_BAD_CLASS, "a prediction or target class outside [0, nc) or not integral"), (AP_ST_NAN_CONF, "a NaN confidence"))
+
+
+def ap_tables():
+    """float64 [1201]: ``linspace(0, 1, 1000)``, ``linspace(0, 1, 101)`` and the latter's ``diff`` -- numpy's own values, which
+    the device route uploads and does not recompute (A4, A6)."""
+    x = np.linspace(0, 1, _lib.AP_X)
+    return np.concatenate([np.linspace(0, 1, _lib.AP_PX), x, np.diff(x)])
+
+
+def _interp_host(x, xp, fp, left, right):
+    """A5 for ascending ``xp``: numpy's interp restated, one float64 operation per statement."""
+    last = xp.size - 1
+    j = np.searchsorted(xp, x, side="right") - 1                      # the LARGEST j with xp[j] <= x; -1: x < xp[0]
+    j0 = np.clip(j, 0, max(last - 1, 0))
+    j1 = np.minimum(j0 + 1, last)
+    with np.errstate(all="ignore"):
+        slope = (fp[j1] - fp[j0]) / (xp[j1] - xp[j0])
+        out = slope * (x - xp[j0]) + fp[j0]
+    out = np.where(xp[j0] == x, fp[j0], out)
+    out = np.where(j >= last, fp[last], out)
+    out = np.where(x > xp[last], right, out)
+    return np.where(x < xp[0], left, out)
+
+
+def _class_bins(cls, nc):
+    """A2: (the class of every element as int64, nc for one that takes part in nothing; whether any such element exists)."""
+    cls = np.asarray(cls, F32).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        ok = (cls >= 0) & (cls < nc) & (cls == np.floor(cls))
+    return np.where(ok, cls, nc).astype(np.int64), bool((~ok).any())
+
+
+def ap_host(tp, conf, pred_cls, target_cls, nc):
+    """Rules A1-A7 (include/evrep.h, with evrep_det_ap) in numpy: the CPU route, and what the tests hold the kernels to bit for
+    bit.  tp (n, T) bool / uint8, conf (n,), pred_cls (n,), target_cls (m,) -> ``(p, r, ap, f1, n_labels, n_pred, any_correct,
+    status)``: p, r, f1 float64 (nc, 1000), ap float64 (nc, T), n_labels and n_pred int64 (nc,), two ints."""
+    tp = np.asarray(tp)
+    conf = np.ascontiguousarray(conf, dtype=F32).reshape(-1)
+    n, nc = conf.size, int(nc)
+    if tp.ndim != 2 or tp.shape[0] != n:
+        raise ValueError("tp must be (n, T) with one row per confidence")
+    tp = tp != 0
+    T = tp.shape[1]
+    if not (1 <= T <= MAX_T and 1 <= nc <= _lib.NMS_MAX_CLASSES):
+        raise ValueError("ap_host: 1 <= T <= %d and 1 <= nc <= %d" % (MAX_T, _lib.NMS_MAX_CLASSES))
+    pc, bad_p = _class_bins(pred_cls, nc)
+    tc, bad_t = _class_bins(target_cls, nc)
+    if pc.size != n:
+        raise ValueError("tp, conf and pred_cls must have one row per prediction")
+    status = (AP_ST_BAD_CLASS if bad_p or bad_t else 0) | (AP_ST_NAN_CONF if np.isnan(conf).any() else 0)
+    n_pred = np.bincount(pc, minlength=nc + 1)[:nc].astype(np.int64)
+    n_labels = np.bincount(tc, minlength=nc + 1)[:nc].astype(np.int64)
+    tables = ap_tables()
+    px, x101, d = tables[:_lib.AP_PX], tables[_lib.AP_PX:_lib.AP_PX + _lib.AP_X], tables[_lib.AP_PX + _lib.AP_X:]
+    p, r, ap = np.zeros((nc, _lib.AP_PX)), np.zeros((nc, _lib.AP_PX)), np.zeros((nc, T))
+    order = np.argsort(-conf, kind="stable")                          # A1: descending, equal confidences in array order
+    pc_sorted = pc[order]
+    for c in np.flatnonzero((n_pred > 0) & (n_labels > 0)):
+        rows = order[pc_sorted == c]
+        tpc = tp[rows].cumsum(0, dtype=np.int64)
+        recall = tpc.astype(np.float64) / np.float64(n_labels[c])
+        precision = tpc.astype(np.float64) / np.arange(1, rows.size + 1, dtype=np.float64)[:, None]
+        xp = -conf[rows].astype(np.float64)
+        r[c] = _interp_host(-px, xp, recall[:, 0], 0.0, recall[-1, 0])
+        p[c] = _interp_host(-px, xp, precision[:, 0], 1.0, precision[-1, 0])
+        for j in range(T):
+            mrec = np.concatenate(([0.0], recall[:, j], [recall[-1, j] + 0.01]))
+            mpre = np.concatenate(([1.0], precision[:, j], [0.0]))
+            mpre = np.flip(np.maximum.accumulate(np.flip(mpre)))
+            y = _interp_host(x101, mrec, mpre, mpre[0], mpre[-1])
+            ap[c, j] = np.add.accumulate((d * (y[:-1] + y[1:])) / 2.0)[-1]      # ascending, one addition at a time
+    f1 = ((2 * p) * r) / ((p + r) + 1e-16)
+    return p, r, ap, f1, n_labels, n_pred, int(tp.any()), int(status)
+
+
+_AP_TABLES = {}
+
+
+def _ap_tables_device(dev):
+    if dev not in _AP_TABLES:
+        _AP_TABLES[dev] = torch.from_numpy(ap_tables()).to(dev)
+    return _AP_TABLES[dev]
+
+
+def ap_workspace_bytes(n, T, nc):
+    """``evrep_det_ap_workspace_bytes``: the scratch of ``ap_device`` for up to n rows."""
+    size = _lib.api().evrep_det_ap_workspace_bytes(int(n), int(T), int(nc))
+    if size == 0:
+        raise ValueError("ap_device: 0 <= n < 2**31, 1 <= T <= %d and 1 <= nc <= %d" % (MAX_T, _lib.NMS_MAX_CLASSES))
+    return size
+
+
+def ap_device(tp, conf, pred_cls, target_cls, nc, counts=None, out=None, workspace=None):
+    """Rules A1-A7 on CUDA tensors: tp (n, T) bool / uint8, conf (n,), pred_cls (n,), target_cls (m,) float32 -> the device
+    tensors ``(p, r, ap, f1, n_labels, n_pred, any_correct, status)`` of ``ap_host``'s shapes (the last two int32 of one
+    element).  The launch sequence of evrep_det_ap; nothing is read back, nothing waits.  ``counts``: an int64 (2,) device
+    tensor holding the true n and m, when only the device knows them (the tensors' sizes are then capacities).  ``out`` /
+    ``workspace``: tensors to write into, as returned / of ``ap_workspace_bytes`` bytes."""
+    if not (isinstance(conf, torch.Tensor) and conf.is_cuda):
+        raise ValueError("ap_device: conf must be a CUDA tensor (CPU arrays go through ap_host)")
+    dev, n, nc = conf.device, int(conf.shape[0]), int(nc)
+    if tp.dtype == torch.bool:
+        tp = tp.view(torch.uint8)
+    _lib.want(tp, "tp", torch.uint8, shape=(n, None), device=dev)
+    T = int(tp.shape[1])
+    _lib.want(conf, "conf", torch.float32, shape=(n,), device=dev)
+    _lib.want(pred_cls, "pred_cls", torch.float32, shape=(n,), device=dev)
+    _lib.want(target_cls, "target_cls", torch.float32, shape=(None,), device=dev)
+    m = int(target_cls.shape[0])
+    if counts is not None:
+        _lib.want(counts, "counts", torch.int64, shape=(2,), device=dev)
+    size = ap_workspace_bytes(n, T, nc)
+    if workspace is None:
+        workspace = _lib.scratch(size, dev)
+    _lib.want(workspace, "workspace", torch.uint8, device=dev)
+    if out is None:
+        f64 = dict(dtype=torch.float64, device=dev)
+        out = (torch.empty((nc, _lib.AP_PX), **f64), torch.empty((nc, _lib.AP_PX), **f64), torch.empty((nc, T), **f64),
+               torch.empty((nc, _lib.AP_PX), **f64), torch.empty(nc, dtype=torch.int64, device=dev),
+               torch.empty(nc, dtype=torch.int64, device=dev), torch.empty(1, dtype=torch.int32, device=dev),
+               torch.empty(1, dtype=torch.int32, device=dev))
+    p, r, ap, f1, n_labels, n_pred, any_correct, status = out
+    for t, what, dtype, shape in ((p, "p", torch.float64, (nc, _lib.AP_PX)), (r, "r", torch.float64, (nc, _lib.AP_PX)),
+                                  (ap, "ap", torch.float64, (nc, T)), (f1, "f1", torch.float64, (nc, _lib.AP_PX)),
+                                  (n_labels, "n_labels", torch.int64, (nc,)), (n_pred, "n_pred", torch.int64, (nc,)),
+                                  (any_correct, "any_correct", torch.int32, (1,)), (status, "status", torch.int32, (1,))):
+        _lib.want(t, what, dtype, shape=shape, device=dev)
+    with torch.cuda.device(dev):
+        _lib.api().evrep_det_ap(_lib.ptr(tp) if n else None, _lib.ptr(conf) if n else None, _lib.ptr(pred_cls) if n else None,
+                                _lib.ptr(target_cls) if m else None, n, m, T, nc, _lib.ptr(counts), _lib.ptr(_ap_tables_device(dev)),
+                                _lib.ptr(p), _lib.ptr(r), _lib.ptr(f1), _lib.ptr(ap), _lib.ptr(n_labels), _lib.ptr(n_pred),
+                                _lib.ptr(any_correct), _lib.ptr(status), _lib.ptr(workspace), workspace.numel(), _lib.stream_ptr())
+    return out
+
+
+def _read_once(tensors):
+    """The tensors as numpy arrays through ONE device-to-host copy."""
+    if not tensors:
+        return []
+    flat = torch.cat([t.contiguous().reshape(-1).view(torch.uint8) for t in tensors]).cpu().numpy()
+    host, at = [], 0
+    for t in tensors:
+        nbytes = t.numel() * t.element_size()
+        host.append(flat[at:at + nbytes].view(torch.empty(0, dtype=t.dtype).numpy().dtype).reshape(tuple(t.shape)))
+        at += nbytes
+    return host
+
+
+def _raise_ap_status(status):
+    if status:
+        raise ValueError("%s (AP status %d)" % (", ".join(text for bit, text in _AP_STATUS_TEXT if status & bit), status))
+
+
+def _ap_per_class_device(tp, conf, pred_cls, target_cls, nc):
+    dev = next(v.device for v in (tp, conf, pred_cls) if isinstance(v, torch.Tensor) and v.is_cuda)
+    tp, conf, pred_cls = (torch.as_tensor(v).to(dev) for v in (tp, conf, pred_cls))
+    if nc is None:
+        t = target_cls.detach() if isinstance(target_cls, torch.Tensor) else np.asarray(target_cls)
+        top = float(t.max()) if len(t) else 0.0                       # (a device target_cls: the one scalar read)
+        if not 0 <= top < _lib.NMS_MAX_CLASSES:
+            raise ValueError("ap_per_class: the largest target class must lie in [0, %d)" % _lib.NMS_MAX_CLASSES)
+        nc = int(top) + 1
+    target_cls = torch.as_tensor(target_cls, dtype=torch.float32).to(dev).contiguous().reshape(-1)
+    out = ap_device(tp.contiguous(), conf.float().contiguous(), pred_cls.float().contiguous(), target_cls, nc)
+    p, r, ap, f1, n_labels, status = _read_once(list(out[:5]) + [out[7]])
+    # AP_ST_BAD_CLASS is not an error here: with nc taken from the targets a prediction of a class beyond them is a class
+    # without labels, which takes part in nothing in the reference either.  A NaN confidence leaves its class unspecified.
+    _raise_ap_status(int(status[0]) & AP_ST_NAN_CONF)
+    present = n_labels > 0
+    return p[present], r[present], ap[present], f1[present], np.flatnonzero(present).astype("int32")
+
+
+def _gather_host(batches, T):
+    """``compute()``'s compaction without its loop over images: the rows below each image's clamped count in (batch, image,
+    detection) order, and the classes of the targets whose image lies in [0, B)."""
+    tp, conf, pcls, tcls = [np.zeros((0, T), bool)], [np.zeros(0, F32)], [np.zeros(0, F32)], [np.zeros(0, F32)]
+    for correct, conf_cls, count, tgt, _ in batches:
+        B, max_det = correct.shape[0], correct.shape[1]
+        keep = np.arange(max_det)[None, :] < np.clip(count.astype(np.int64), 0, max_det)[:, None]
+        tp.append(correct[keep] != 0)
+        conf.append(conf_cls[keep][:, 0])
+        pcls.append(conf_cls[keep][:, 1])
+        t0 = tgt[:, 0]
+        tcls.append(tgt[(t0 >= 0) & (t0 < B) & (t0 == np.floor(t0)), 1])
+    return np.concatenate(tp, 0), np.concatenate(conf, 0), np.concatenate(pcls, 0), np.concatenate(tcls, 0)
 
 
 class DetectionEvaluator:
@@ -442,7 +669,7 @@ class DetectionEvaluator:
     def update(self, det, count, targets, img_shape, shapes):
         correct, _, n_labels, status = match_batch(det, count, targets, img_shape, shapes, self.iouv, self.confusion)
         targets = targets.to(det.device)
-        self._batches.append((correct, det[:, :, 4:6].contiguous(), count.to(det.device), targets[:, 0:2].contiguous(), status))
+        self.add_batch(correct, det[:, :, 4:6], count.to(det.device), targets[:, 0:2], status)
 
     def compute(self):
         T = self.iouv.size
@@ -472,3 +699,66 @@ class DetectionEvaluator:
                 tcls.append(tgt[tgt[:, 0] == F32(b), 1])
         stats = (np.concatenate(tp, 0), np.concatenate(conf, 0), np.concatenate(pcls, 0), np.concatenate(tcls, 0))
         return summarize(stats, self.nc, seen)
+
+    def add_batch(self, correct, conf_cls, count, targets, status):
+        """Keeps one already scored batch: correct (B, max_det, T) uint8, conf_cls (B, max_det, 2) float32 (columns 4 and 5 of
+        the detections), count (B,) int32, targets (n_t, 2) float32 (image, class), status (B,) int32 -- what ``update`` keeps
+        of ``match_batch``'s launch, and the one place that says what a kept batch is (``update`` ends here).  All five on one
+        device."""
+        if not isinstance(correct, torch.Tensor) or correct.dim() != 3 or correct.shape[2] != self.iouv.size:
+            raise ValueError("correct must be a (B, max_det, %d) tensor" % self.iouv.size)
+        dev, B, max_det = correct.device, int(correct.shape[0]), int(correct.shape[1])
+        conf_cls, targets = conf_cls.contiguous(), targets.contiguous()
+        _lib.want(correct, "correct", torch.uint8, shape=(B, max_det, self.iouv.size), device=dev)
+        _lib.want(conf_cls, "conf_cls", torch.float32, shape=(B, max_det, 2), device=dev)
+        _lib.want(count, "count", torch.int32, shape=(B,), device=dev)
+        _lib.want(targets, "targets", torch.float32, shape=(None, 2), device=dev)
+        _lib.want(status, "status", torch.int32, shape=(B,), device=dev)
+        if self._batches and self._batches[0][0].device != dev:
+            raise ValueError("the evaluator's batches live on %s" % self._batches[0][0].device)
+        self._batches.append((correct, conf_cls, count, targets, status))
+
+    def compute_device(self):
+        """``compute()`` with the compaction, the ordering and the AP on the batches' device (rules A1-A7): per batch two
+        launches of evrep_det_ap_gather, then evrep_det_ap, then ONE read-back of the result arrays and the status words; the
+        host works per batch, never per image or row.  Returns ``compute()``'s dict (tied confidences: in array order, the
+        declared rule), or ``(0.0, 0.0)`` when no prediction is correct.  Batches on the CPU take the same route through
+        ``ap_host``."""
+        T = self.iouv.size
+        if not self._batches:
+            return 0.0, 0.0
+        dev, seen = self._batches[0][0].device, sum(int(b[0].shape[0]) for b in self._batches)
+        words = [b[4] for b in self._batches]
+        if dev.type != "cuda":
+            host = [[t.numpy() for t in b] for b in self._batches]
+            result = ap_host(*_gather_host(host, T), self.nc)
+            p, r, ap, f1, n_labels, _, any_correct, ap_status = result
+            words = [b[4] for b in host]
+        else:
+            cap_n = sum(int(b[0].shape[0]) * int(b[0].shape[1]) for b in self._batches)
+            cap_m = sum(int(b[3].shape[0]) for b in self._batches)
+            tp = torch.empty((cap_n, T), dtype=torch.uint8, device=dev)
+            conf, pcls = torch.empty(cap_n, dtype=torch.float32, device=dev), torch.empty(cap_n, dtype=torch.float32, device=dev)
+            tcls = torch.empty(cap_m, dtype=torch.float32, device=dev)
+            cursor = torch.zeros(2, dtype=torch.int64, device=dev)
+            with torch.cuda.device(dev):
+                for correct, conf_cls, count, tgt, _ in self._batches:
+                    B, max_det, n_t = int(correct.shape[0]), int(correct.shape[1]), int(tgt.shape[0])
+                    _lib.api().evrep_det_ap_gather(_lib.ptr(correct), _lib.ptr(conf_cls), _lib.ptr(count), B, max_det, T,
+                                                   _lib.ptr(tgt) if n_t else None, n_t, _lib.ptr(tp), _lib.ptr(conf), _lib.ptr(pcls),
+                                                   cap_n, _lib.ptr(tcls) if cap_m else None, cap_m, _lib.ptr(cursor), _lib.stream_ptr())
+            out = ap_device(tp, conf, pcls, tcls, self.nc, counts=cursor)
+            host = _read_once([out[0], out[1], out[2], out[3], out[4], out[6], out[7]] + words)     # the one read-back
+            p, r, ap, f1, n_labels = host[:5]
+            any_correct, ap_status, words = int(host[5][0]), int(host[6][0]), host[7:]
+        if self.check:
+            for i, status in enumerate(words):
+                if status.any():
+                    b = int(np.flatnonzero(status)[0])
+                    what = ", ".join(text for bit, text in _STATUS_TEXT if int(status[b]) & bit)
+                    raise ValueError("batch %d, image %d: %s (status %d)" % (i, b, what, int(status[b])))
+            _raise_ap_status(ap_status)
+        if not any_correct:
+            return 0.0, 0.0
+        present = n_labels > 0
+        return _summary(p[present], r[present], ap[present], f1[present], np.flatnonzero(present).astype("int32"), n_labels, seen)

@@ -961,6 +961,80 @@ int evrep_det_match(const float *det, const int32_t *count, int32_t B, int32_t m
                     int64_t *matrix, int32_t nc, float conf, float iou_thres, uint8_t *correct, float *detn, float *tbox,
                     int32_t *n_labels, uint32_t *status, void *stream);
 
+/* Average precision on the device: yolov6/utils/metrics.py's ap_per_class and compute_ap (without the plots) for the rows a
+ * validation run left resident, with no host sort and no host loop.  tp DEVICE uint8 [n,T] (non-zero: true); conf DEVICE float
+ * [n]; pred_cls DEVICE float [n]; target_cls DEVICE float [m]; nc classes.  Every float64 statement below is ONE IEEE operation
+ * rounded on its own: nothing is contracted into a fused multiply-add (-ffp-contract=off, and the kernel file repeats it as a
+ * pragma), no float atomic, no reassociation; the result is the same bits from run to run.
+ *   A1 order    rows are ordered by DESCENDING conf; rows of equal conf keep array order (stable), and -0.0 equals +0.0.  Array
+ *               order is (batch, image, detection), the layout the evaluator builds.  This is the declared TIE rule: the
+ *               reference's argsort(-conf) is numpy's unstable sort and leaves the outcome open among equal confidences.
+ *   A2 classes  class c in [0, nc) owns the rows with pred_cls == c (float equality) and n_l[c] = the number of targets with
+ *               target_cls == c.  A prediction or target class outside [0, nc) or not integral (a NaN too) sets
+ *               EVREP_AP_ST_BAD_CLASS and takes part in nothing.  A NaN conf sets EVREP_AP_ST_NAN_CONF; what the rows of its
+ *               class hold is then unspecified.
+ *   A3 counts   for a class with n_p > 0 rows and n_l > 0 labels, at its k-th row (1-based, in A1's order): tpc[k,j] = the integer
+ *               count of true tp[.,j] among its first k rows (fpc = k - tpc), recall[k,j] = double(tpc) / double(n_l) (the
+ *               reference's n_l + 1e-16 IS n_l in float64), precision[k,j] = double(tpc) / double(k).  A class with n_p == 0 or
+ *               n_l == 0 has all-zero rows in every output.
+ *   A4 curves   px = numpy's linspace(0, 1, 1000), UPLOADED (tables), not recomputed.  r[c] = interp(-px, -conf_c, recall[:,0],
+ *               left = 0); p[c] = interp(-px, -conf_c, precision[:,0], left = 1); conf_c the class's confidences widened to
+ *               float64.
+ *   A5 interp   interp(x, xp, fp, left, right = fp[last]) is numpy's: x < xp[0] gives left; x > xp[last] gives right; otherwise
+ *               j is the LARGEST index with xp[j] <= x; j last gives fp[last]; xp[j] == x gives fp[j]; otherwise
+ *               ((fp[j+1] - fp[j]) / (xp[j+1] - xp[j])) * (x - xp[j]) + fp[j].  "Largest" is what makes repeated abscissae (tied
+ *               confidences, the flat runs of mrec) well defined.
+ *   A6 ap       per (class, threshold j): mrec = [0, recall[:,j], recall[last,j] + 0.01]; mpre = [1, precision[:,j], 0] replaced
+ *               by its running maximum taken from the right; y = interp(x, mrec, mpre) over x = linspace(0, 1, 101);
+ *               ap = sum over i = 0..99 of (d[i] * (y[i] + y[i+1])) / 2.0 with d = numpy's diff(x), added in ascending i, one
+ *               addition at a time (numpy's trapz adds the same terms pairwise: the two differ by rounding only).
+ *   A7 f1       f1 = ((2 * p) * r) / ((p + r) + 1e-16), elementwise.
+ * tables DEVICE double [1201]: px[1000], x[101], d[100].  counts_dev: NULL, or DEVICE int64 [2] = {n, m} as they are known on
+ * the device only (what evrep_det_ap_gather's cursor holds); then the arguments n and m are CAPACITIES: the arrays and the
+ * workspace are sized by them, each device number is clamped to [0, capacity], and nothing is read back.
+ * Outputs, all DEVICE, every byte written on every call: p, r, f1 double [nc,1000]; ap double [nc,T]; n_labels, n_pred int64
+ * [nc] (the targets and the rows of each class); any_correct uint32 [1] (1 iff any tp byte of the n rows is non-zero, rows of
+ * a bad class included: the reference's stats[0].any()); status uint32 [1].
+ * The launches: keys and class counts; one workgroup that scans the class counts; a stable LSD radix sort of (class, conf key)
+ * carrying the row index, eight bits a pass (count per tile of EVREP_AP_SORT_TILE rows, one workgroup's scan, scatter); the
+ * integer scan of tp over the sorted rows, the T thresholds of a row together (sums per tile of EVREP_AP_SCAN_TILE rows, one
+ * wave's scan, write); the running maximum from the right, segmented by class (heads, one wave's walk, write); the curves; the
+ * areas.  Every dependency between workgroups is a launch boundary: no workgroup waits for another inside a launch.
+ * PRACTICAL RANGE: the two one-wave steps (the scan of the tiles' tp sums, the walk of the tiles' maxima) visit the
+ * n / EVREP_AP_SCAN_TILE scan tiles one after the other, a dependent read and write each: about 2 000 steps at 10^6 rows (part
+ * of the 0.8 ms measured for scans, curves and areas), 4 M steps -- seconds -- at the formal limit below.  The limit is what
+ * the 32-bit positions allow; the step is built for validation runs of up to some 10^7 rows.
+ * 0 <= n, m < 2^31 (n == 0 or m == 0 is legal: zero curves, and no launch that indexes an empty array), 1 <= T <=
+ * EVREP_DETEVAL_MAX_T, 1 <= nc <= EVREP_NMS_MAX_CLASSES; pointers aligned to their element, workspace to 256 bytes, tp / conf /
+ * pred_cls may be NULL when n == 0 and target_cls when m == 0; anything else is EVREP_EINVAL before any launch.
+ * evrep_det_ap_workspace_bytes(n, T, nc) is the workspace (0 for a refused shape); a smaller workspace_bytes is EVREP_EWORKSPACE.
+ * The call writes nothing outside its outputs and the first evrep_det_ap_workspace_bytes bytes of workspace, does not allocate,
+ * does not wait for the device, reads nothing back.
+ *
+ * evrep_det_ap_gather compacts ONE scored batch into those rows: correct DEVICE uint8 [B,max_det,T] and count DEVICE int32 [B]
+ * as evrep_det_match wrote and read them, conf_cls DEVICE float [B,max_det,2] (columns 4 and 5 of det), targets DEVICE float
+ * [n_t,2] (image, class).  cursor DEVICE int64 [2], zeroed by the caller before the first batch.  The rows 0 .. clamp(count[b],
+ * 0, max_det) - 1 of image b go to tp / conf / pred_cls at cursor[0] + the clamped counts of the images in front of it: (batch,
+ * image, detection) order.  The class of every target row whose image is an integer in [0, B) (the rows the evaluator counts)
+ * goes to target_cls from cursor[1] on, in array order.  Then cursor moves by the two numbers.  Two launches (the cursor is
+ * moved by the second: a launch boundary behind every workgroup that read it), no scratch.  cap_n >= B * max_det rows must
+ * be free behind the cursor (the caller sizes the rows for every batch; a row that would not fit is not written); cap_n, cap_m
+ * < 2^31; 1 <= B <= 65535, 1 <= max_det <= EVREP_NMS_MAX_DET, 0 <= n_t <= EVREP_DETEVAL_MAX_TARGETS. */
+#define EVREP_AP_SORT_TILE 2048
+#define EVREP_AP_SCAN_TILE 512
+#define EVREP_AP_GATHER_CHUNK 1024  /* evrep_det_ap_gather's second launch: target rows, and images, per round of its one workgroup */
+#define EVREP_AP_GATHER_IMAGES 256  /* its first launch: the images in front of its own that a workgroup sums per round */
+#define EVREP_AP_ST_BAD_CLASS 1u
+#define EVREP_AP_ST_NAN_CONF 2u
+size_t evrep_det_ap_workspace_bytes(int64_t n, int32_t T, int32_t nc);
+int evrep_det_ap(const uint8_t *tp, const float *conf, const float *pred_cls, const float *target_cls, int64_t n, int64_t m,
+                 int32_t T, int32_t nc, const int64_t *counts_dev, const double *tables, double *p, double *r, double *f1,
+                 double *ap, int64_t *n_labels, int64_t *n_pred, uint32_t *any_correct, uint32_t *status, void *workspace,
+                 size_t workspace_bytes, void *stream);
+int evrep_det_ap_gather(const uint8_t *correct, const float *conf_cls, const int32_t *count, int32_t B, int32_t max_det, int32_t T,
+                        const float *targets, int64_t n_t, uint8_t *tp, float *conf, float *pred_cls, int64_t cap_n,
+                        float *target_cls, int64_t cap_m, int64_t *cursor, void *stream);
+
 /* The training targets: what ev-YOLOv6's ComputeLoss.__call__ does between the head's output and the loss terms
  * (yolov6/models/losses/loss.py:73-111) for the B images of a batch, with no (B, M, A) array in memory.
  *
