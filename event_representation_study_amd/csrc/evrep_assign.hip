@@ -8,8 +8,7 @@
 //   k_tal_prepare      grid (G, B): every value of the image's predictions and labels is looked at once; a non-finite one sets
 //                      EVREP_TAL_ST_NONFINITE in status[b].  Clears the per-anchor words and the per-row maxima of the scratch.
 //   k_tal_select       one workgroup per (image, row).  A valid row streams the A anchors in chunks of 256, a lane per anchor,
-//                      and keeps the first `topk` of the total order (key descending, anchor ascending) in LDS: a chunk's anchors
-//                      that beat the list's last entry are merged into it by counting, for each entry, the entries above it.
+//                      and keeps the first `topk` of the total order (key descending, anchor ascending) in LDS (TopkList below).
 //                      Every selected anchor whose centre lies in the box adds 1 to cnt[b, a] and takes min(first[b, a], m):
 //                      integer atomics, free of order.
 //   k_tal_resolve      a lane per (image, anchor): c = cnt; the row is first (c == 1) or the first row of greatest IoU over all M
@@ -34,7 +33,6 @@ namespace evrep {
 
 constexpr int kTalMaxTopk = EVREP_TAL_MAX_TOPK;
 constexpr int kTalSelectThreads = 256;                                 // k_tal_select: a chunk of anchors, a lane each
-static_assert(kTalMaxTopk <= kTalSelectThreads, "the list is merged by the lanes of one chunk");
 
 struct TalPadArgs {
     const float *targets;         // (n_t, 6)
@@ -59,7 +57,7 @@ struct TalArgs {
     uint32_t *cnt;                // scratch (B, A): the rows an anchor is a candidate of
     uint32_t *first;              // scratch (B, A): the lowest of them
     int32_t *row;                 // scratch (B, A): the assigned row, -1 for background
-    double *alv;                  // scratch (B, A): the assigned row's metric
+    double *val;                  // scratch (B, A): the assigned row's metric
     unsigned long long *pos_al;   // scratch (B, M): bits of the row's greatest metric
     unsigned long long *pos_ov;   // scratch (B, M): bits of the row's greatest IoU
     int32_t B, M, A, nc, topk, alpha, beta, f32_out;
@@ -164,46 +162,125 @@ __global__ __launch_bounds__(kDistThreads) void k_det_targets_pad(const TalPadAr
 }
 
 // ------------------------------------------------------------------------------------------------------------------- prepare
+// The pieces both assigners' prepare kernels are made of.  A non-finite value among ptr[start], ptr[start + step], ... below n:
+template <typename T>
+__device__ inline bool any_nonfinite(const T *ptr, size_t n, size_t start, size_t step) {
+    bool bad = false;
+    for (size_t e = start; e < n; e += step) bad = bad || !tal_finite(ptr[e]);
+    return bad;
+}
+
+// the claim words of image b's anchors: claimed by no row
+__device__ inline void claims_clear(uint32_t *cnt, uint32_t *first, int b, int A, size_t start, size_t step) {
+    for (size_t a = start; a < (size_t)A; a += step) {
+        cnt[(size_t)b * A + a] = 0u;
+        first[(size_t)b * A + a] = 0xFFFFFFFFu;
+    }
+}
+
+// EVREP_TAL_ST_NONFINITE into *status where a lane of the workgroup found a bad value.  Holds an LDS word and two barriers:
+// every lane of the workgroup calls it, outside divergent control flow.
+__device__ inline void raise_nonfinite(bool bad, uint32_t *status) {
+    __shared__ uint32_t s_bad;
+    if (threadIdx.x == 0) s_bad = 0u;
+    __syncthreads();
+    if (bad) s_bad = 1u;
+    __syncthreads();
+    if (threadIdx.x == 0 && s_bad != 0u) atomicOr(status, EVREP_TAL_ST_NONFINITE);
+}
+
 // grid (G, B), 256 threads; status[b] was zeroed by a memset ordered before this launch
 __global__ __launch_bounds__(kThreads) void k_tal_prepare(const TalArgs t) {
-    __shared__ uint32_t s_bad;
-    const int b = blockIdx.y, tid = threadIdx.x;
-    const size_t start = (size_t)blockIdx.x * kThreads + tid, step = (size_t)gridDim.x * kThreads;
-    if (tid == 0) s_bad = 0u;
-    __syncthreads();
-    bool bad = false;
+    const int b = blockIdx.y;
+    const size_t start = (size_t)blockIdx.x * kThreads + threadIdx.x, step = (size_t)gridDim.x * kThreads;
     const size_t n_s = (size_t)t.A * (size_t)t.nc, n_b = (size_t)t.A * 4u, n_g = (size_t)t.M * 5u;
-    const float *ps = t.pd_scores + (size_t)b * n_s;
-    for (size_t e = start; e < n_s; e += step) bad = bad || !tal_finite(ps[e]);
-    const float *pb = t.pd_bboxes + (size_t)b * n_b;
-    for (size_t e = start; e < n_b; e += step) bad = bad || !tal_finite(pb[e]);
-    const double *g = t.gt + (size_t)b * n_g;
-    for (size_t e = start; e < n_g; e += step) bad = bad || !tal_finite(g[e]);
-    for (size_t a = start; a < (size_t)t.A; a += step) {
-        t.cnt[(size_t)b * t.A + a] = 0u;
-        t.first[(size_t)b * t.A + a] = 0xFFFFFFFFu;
-    }
+    bool bad = any_nonfinite(t.pd_scores + (size_t)b * n_s, n_s, start, step);
+    bad = bad || any_nonfinite(t.pd_bboxes + (size_t)b * n_b, n_b, start, step);
+    bad = bad || any_nonfinite(t.gt + (size_t)b * n_g, n_g, start, step);
+    claims_clear(t.cnt, t.first, b, t.A, start, step);
     for (size_t m = start; m < (size_t)t.M; m += step) {
         t.pos_al[(size_t)b * t.M + m] = 0ull;
         t.pos_ov[(size_t)b * t.M + m] = 0ull;
     }
-    if (bad) s_bad = 1u;
-    __syncthreads();
-    if (tid == 0 && s_bad != 0u) atomicOr(&t.status[b], EVREP_TAL_ST_NONFINITE);
+    raise_nonfinite(bad, &t.status[b]);
 }
+
+// ------------------------------------------------------------------------------------------------------------ the top-k list
+// The first K <= MaxK entries of a total order, kept in LDS by a workgroup of Threads lanes that is offered its entries a
+// chunk at a time, a lane each.  An entry is the bits of a key and an index; Before(k1, i1, k2, i2) says that entry 1 comes
+// before entry 2, and no two entries offered are equal.  A chunk's entries that come before the list's last one are appended
+// behind the list; every entry is then ranked by counting the entries before it, and the first K are the new list.
+// Storage lies in LDS; the list itself (K and the length, equal in every lane) lives in registers.
+template <int MaxK, int Threads, typename Before>
+class TopkList {
+    static_assert(MaxK <= Threads, "the list is merged by the lanes of one chunk");
+
+public:
+    struct Storage {
+        unsigned long long k[MaxK + Threads], nk[MaxK];
+        uint32_t i[MaxK + Threads], ni[MaxK];
+        uint32_t scan[Threads / 64];
+    };
+
+    __device__ TopkList(Storage &s, int K) : s_(s), K_(K), L_(0) {}   // 1 <= K <= MaxK
+
+    // Every lane of the workgroup calls, `in` or not: the lane's entry of this chunk.
+    __device__ void offer(bool in, unsigned long long kb, uint32_t ib) {
+        const int tid = threadIdx.x, K = K_, L = L_;
+        const Before before;
+        // the list's last entry is read before anyone rewrites it: the barriers of the scan stand between
+        const bool cont = in && (L < K || before(kb, ib, s_.k[L - 1], s_.i[L - 1]));
+        uint32_t nc_;
+        const uint32_t ex = block_exclusive_scan<Threads / 64>(cont ? 1u : 0u, s_.scan, &nc_);
+        if (nc_ == 0u) return;                                         // (uniform)
+        if (cont) {
+            s_.k[L + ex] = kb;                                         // L + ex < K + Threads
+            s_.i[L + ex] = ib;
+        }
+        __syncthreads();
+        const int T = L + (int)nc_;
+        const int NL = T < K ? T : K;
+        for (int e = tid; e < T; e += Threads) {
+            const unsigned long long ke = s_.k[e];
+            const uint32_t ie = s_.i[e];
+            int rank = 0;
+            for (int j = 0; j < T; ++j) rank += before(s_.k[j], s_.i[j], ke, ie) ? 1 : 0;
+            if (rank < NL) {                                           // the entries are distinct: so are the ranks
+                s_.nk[rank] = ke;
+                s_.ni[rank] = ie;
+            }
+        }
+        __syncthreads();
+        if (tid < NL) {
+            s_.k[tid] = s_.nk[tid];
+            s_.i[tid] = s_.ni[tid];
+        }
+        L_ = NL;
+        __syncthreads();
+    }
+
+    __device__ int size() const { return L_; }                         // <= min(K, entries offered)
+    __device__ uint32_t index(int e) const { return s_.i[e]; }         // e < size(), in the order
+
+private:
+    Storage &s_;
+    const int K_;
+    int L_;
+};
 
 // -------------------------------------------------------------------------------------------------------------------- select
 // an entry of the order: the key's bits (non-negative doubles order as their bits) and A - 1 - anchor
-__device__ inline bool tal_above(unsigned long long k1, uint32_t i1, unsigned long long k2, uint32_t i2) {
-    return k1 > k2 || (k1 == k2 && i1 > i2);
-}
+struct TalAbove {
+    __device__ bool operator()(unsigned long long k1, uint32_t i1, unsigned long long k2, uint32_t i2) const {
+        return k1 > k2 || (k1 == k2 && i1 > i2);
+    }
+};
+using TalList = TopkList<kTalMaxTopk, kTalSelectThreads, TalAbove>;
 
 // grid (M, B), 256 threads
 __global__ __launch_bounds__(kTalSelectThreads) void k_tal_select(const TalArgs t) {
-    __shared__ unsigned long long s_k[kTalMaxTopk + kTalSelectThreads], s_nk[kTalMaxTopk];
-    __shared__ uint32_t s_i[kTalMaxTopk + kTalSelectThreads], s_ni[kTalMaxTopk];
-    __shared__ uint32_t s_scan[kTalSelectThreads / 64];
-    const int tid = threadIdx.x, m = blockIdx.x, b = blockIdx.y, A = t.A, K = t.topk;
+    __shared__ TalList::Storage s_list;
+    const int tid = threadIdx.x, m = blockIdx.x, b = blockIdx.y, A = t.A;
     if (t.status[b] & EVREP_TAL_ST_NONFINITE) return;                   // (uniform: written by the launch before this one)
     const TalRow r = tal_row(t.gt, b, t.M, m);
     if (!tal_row_valid(r)) return;
@@ -212,7 +289,7 @@ __global__ __launch_bounds__(kTalSelectThreads) void k_tal_select(const TalArgs 
         if (tid == 0) atomicOr(&t.status[b], EVREP_TAL_ST_BAD_CLASS);
         return;
     }
-    int L = 0;                                                         // entries of the list, <= min(K, anchors seen)
+    TalList list(s_list, t.topk);
     for (int a0 = 0; a0 < A; a0 += kTalSelectThreads) {
         const int a = a0 + tid;
         unsigned long long kb = 0ull;
@@ -223,39 +300,10 @@ __global__ __launch_bounds__(kTalSelectThreads) void k_tal_select(const TalArgs 
                 if (al > 0.0) kb = (unsigned long long)__double_as_longlong(al);   // (a NaN, a negative and -0 are key +0)
             }
         }
-        const uint32_t ic = (uint32_t)(A - 1 - (a < A ? a : A - 1));
-        // the list's last entry is read before anyone rewrites it: the barriers of the scan stand between
-        const bool cont = a < A && (L < K || tal_above(kb, ic, s_k[L - 1], s_i[L - 1]));
-        uint32_t nc_;
-        const uint32_t ex = block_exclusive_scan<kTalSelectThreads / 64>(cont ? 1u : 0u, s_scan, &nc_);
-        if (nc_ == 0u) continue;                                       // (uniform)
-        if (cont) {
-            s_k[L + ex] = kb;                                          // L + ex < K + 256
-            s_i[L + ex] = ic;
-        }
-        __syncthreads();
-        const int T = L + (int)nc_;
-        const int NL = T < K ? T : K;
-        for (int e = tid; e < T; e += kTalSelectThreads) {
-            const unsigned long long ke = s_k[e];
-            const uint32_t ie = s_i[e];
-            int rank = 0;
-            for (int j = 0; j < T; ++j) rank += tal_above(s_k[j], s_i[j], ke, ie) ? 1 : 0;
-            if (rank < NL) {                                           // the entries are distinct: so are the ranks
-                s_nk[rank] = ke;
-                s_ni[rank] = ie;
-            }
-        }
-        __syncthreads();
-        if (tid < NL) {
-            s_k[tid] = s_nk[tid];
-            s_i[tid] = s_ni[tid];
-        }
-        L = NL;
-        __syncthreads();
+        list.offer(a < A, kb, (uint32_t)(A - 1 - (a < A ? a : A - 1)));
     }
-    if (tid < L) {
-        const int a = A - 1 - (int)s_i[tid];                           // 0 <= a < A
+    if (tid < list.size()) {
+        const int a = A - 1 - (int)list.index(tid);                    // 0 <= a < A
         const double ax = (double)t.anc[(size_t)a * 2u], ay = (double)t.anc[(size_t)a * 2u + 1u];
         if (tal_in_gt(r, ax, ay)) {
             atomicAdd(&t.cnt[(size_t)b * A + a], 1u);
@@ -265,9 +313,10 @@ __global__ __launch_bounds__(kTalSelectThreads) void k_tal_select(const TalArgs 
 }
 
 // ------------------------------------------------------------------------------------------------------------------- resolve
-template <typename O>
-__device__ inline void tal_store(void *base, size_t at, double v) {
-    static_cast<O *>(base)[at] = (O)v;
+// base[at] = v in the output's width: float32 (one rounding) or float64
+__device__ inline void tal_store(void *base, int f32, size_t at, double v) {
+    if (f32) static_cast<float *>(base)[at] = (float)v;
+    else static_cast<double *>(base)[at] = v;
 }
 
 // grid (ceil(A / 256), B), 256 threads.  M == 0: the reference's early return
@@ -279,11 +328,8 @@ __global__ __launch_bounds__(kThreads) void k_tal_resolve(const TalArgs t) {
         t.labels[ba] = (int64_t)t.nc;
         t.fg[ba] = 0;
         t.row[ba] = -1;
-        t.alv[ba] = 0.0;
-        for (int e = 0; e < 4; ++e) {
-            if (t.f32_out) tal_store<float>(t.boxes, ba * 4u + e, 0.0);
-            else tal_store<double>(t.boxes, ba * 4u + e, 0.0);
-        }
+        t.val[ba] = 0.0;
+        for (int e = 0; e < 4; ++e) tal_store(t.boxes, t.f32_out, ba * 4u + e, 0.0);
         return;
     }
     const uint32_t c = t.cnt[ba];
@@ -315,12 +361,9 @@ __global__ __launch_bounds__(kThreads) void k_tal_resolve(const TalArgs t) {
     t.labels[ba] = (int64_t)(cl < 0 ? 0 : cl);
     t.fg[ba] = c != 0u ? 1 : 0;
     t.row[ba] = c != 0u ? g : -1;
-    t.alv[ba] = al;
+    t.val[ba] = al;
     const double box[4] = {r.x1, r.y1, r.x2, r.y2};
-    for (int e = 0; e < 4; ++e) {
-        if (t.f32_out) tal_store<float>(t.boxes, ba * 4u + e, box[e]);
-        else tal_store<double>(t.boxes, ba * 4u + e, box[e]);
-    }
+    for (int e = 0; e < 4; ++e) tal_store(t.boxes, t.f32_out, ba * 4u + e, box[e]);
 }
 
 // -------------------------------------------------------------------------------------------------------------------- scores
@@ -336,11 +379,9 @@ __global__ __launch_bounds__(kThreads) void k_tal_scores(const TalArgs t) {
         if (g >= 0 && (int64_t)c == t.labels[ba]) {
             const double pa = __longlong_as_double((long long)t.pos_al[(size_t)b * t.M + g]);
             const double po = __longlong_as_double((long long)t.pos_ov[(size_t)b * t.M + g]);
-            v = __ddiv_rn(__dmul_rn(t.alv[ba], po), __dadd_rn(pa, 1e-9));
+            v = __ddiv_rn(__dmul_rn(t.val[ba], po), __dadd_rn(pa, 1e-9));
         }
-        const size_t at = (size_t)b * n + e;
-        if (t.f32_out) tal_store<float>(t.scores, at, v);
-        else tal_store<double>(t.scores, at, v);
+        tal_store(t.scores, t.f32_out, (size_t)b * n + e, v);
     }
 }
 

@@ -8,7 +8,7 @@
 //                    EVREP_TAL_ST_NONFINITE in status[b].  Clears the per-anchor words of the scratch.
 //   k_atss_select    one workgroup per (image, row).  Per level a valid row streams the level's anchors in chunks of 256, a lane
 //                    per anchor (beginning at the chunk of the nearest anchor and going outwards), and keeps the first `topk` of the total order (centre distance ascending, anchor ascending) in
-//                    LDS, merged by counting as k_tal_select merges; the key is the distance's bits (non-negative doubles order
+//                    LDS (the TopkList of evrep_assign.hip, under this order); the key is the distance's bits (non-negative doubles order
 //                    as their bits).  The n_levels * topk <= 256 candidates then have a lane each: the lane computes the
 //                    candidate's IoU with the anchor box, every lane adds the values in the fixed order (level, place) to the
 //                    mean and the deviation, and a candidate above the threshold whose centre lies in the box adds 1 to
@@ -32,7 +32,6 @@ namespace evrep {
 constexpr int kAtssMaxTopk = EVREP_ATSS_MAX_TOPK;
 constexpr int kAtssMaxLevels = EVREP_ATSS_MAX_LEVELS;
 constexpr int kAtssThreads = 256;                                      // k_atss_select: a chunk of anchors, or the candidates, a lane each
-static_assert(kAtssMaxTopk <= kAtssThreads, "the list is merged by the lanes of one chunk");
 static_assert(EVREP_ATSS_MAX_CANDIDATES == kAtssThreads, "a candidate has a lane");
 
 struct AtssArgs {
@@ -88,40 +87,31 @@ __device__ inline double atss_distance(const TalRow &r, const AtssAnchor &n) {
 // ------------------------------------------------------------------------------------------------------------------- prepare
 // grid (G, B), 256 threads; status[b] was zeroed by a memset ordered before this launch
 __global__ __launch_bounds__(kThreads) void k_atss_prepare(const AtssArgs t) {
-    __shared__ uint32_t s_bad;
-    const int b = blockIdx.y, tid = threadIdx.x;
-    const size_t start = (size_t)blockIdx.x * kThreads + tid, step = (size_t)gridDim.x * kThreads;
-    if (tid == 0) s_bad = 0u;
-    __syncthreads();
-    bool bad = false;
+    const int b = blockIdx.y;
+    const size_t start = (size_t)blockIdx.x * kThreads + threadIdx.x, step = (size_t)gridDim.x * kThreads;
     const size_t n_b = (size_t)t.A * 4u, n_g = (size_t)t.M * 5u;
-    if (t.pd_bboxes) {
-        const float *pb = t.pd_bboxes + (size_t)b * n_b;
-        for (size_t e = start; e < n_b; e += step) bad = bad || !tal_finite(pb[e]);
-    }
-    const double *g = t.gt + (size_t)b * n_g;
-    for (size_t e = start; e < n_g; e += step) bad = bad || !tal_finite(g[e]);
-    for (size_t a = start; a < (size_t)t.A; a += step) {
-        t.cnt[(size_t)b * t.A + a] = 0u;
-        t.first[(size_t)b * t.A + a] = 0xFFFFFFFFu;
-    }
-    if (bad) s_bad = 1u;
-    __syncthreads();
-    if (tid == 0 && s_bad != 0u) atomicOr(&t.status[b], EVREP_TAL_ST_NONFINITE);
+    bool bad = t.pd_bboxes && any_nonfinite(t.pd_bboxes + (size_t)b * n_b, n_b, start, step);
+    bad = bad || any_nonfinite(t.gt + (size_t)b * n_g, n_g, start, step);
+    claims_clear(t.cnt, t.first, b, t.A, start, step);
+    raise_nonfinite(bad, &t.status[b]);
 }
 
 // -------------------------------------------------------------------------------------------------------------------- select
 // an entry of the order: the distance's bits and the anchor
-__device__ inline bool atss_before(unsigned long long k1, uint32_t i1, unsigned long long k2, uint32_t i2) {
-    return k1 < k2 || (k1 == k2 && i1 < i2);
-}
+struct AtssBefore {
+    __device__ bool operator()(unsigned long long k1, uint32_t i1, unsigned long long k2, uint32_t i2) const {
+        return k1 < k2 || (k1 == k2 && i1 < i2);
+    }
+};
+using AtssList = TopkList<kAtssMaxTopk, kAtssThreads, AtssBefore>;
 
 // the first entry of the order among a wave's lanes, in every lane
 __device__ inline void atss_wave_first(unsigned long long &k, uint32_t &i) {
+    const AtssBefore before;
     for (int d = 32; d >= 1; d >>= 1) {
         const uint32_t lo = __shfl_xor((uint32_t)k, d, 64), hi = __shfl_xor((uint32_t)(k >> 32), d, 64), oi = __shfl_xor(i, d, 64);
         const unsigned long long ok = ((unsigned long long)hi << 32) | lo;
-        if (atss_before(ok, oi, k, i)) {
+        if (before(ok, oi, k, i)) {
             k = ok;
             i = oi;
         }
@@ -130,11 +120,12 @@ __device__ inline void atss_wave_first(unsigned long long &k, uint32_t &i) {
 
 // grid (M, B), 256 threads; every level holds at least topk anchors and n_levels * topk <= 256 (held by the host)
 __global__ __launch_bounds__(kAtssThreads) void k_atss_select(const AtssArgs t) {
-    __shared__ unsigned long long s_k[kAtssMaxTopk + kAtssThreads], s_nk[kAtssMaxTopk];
-    __shared__ uint32_t s_i[kAtssMaxTopk + kAtssThreads], s_ni[kAtssMaxTopk];
-    __shared__ uint32_t s_scan[kAtssThreads / 64];
+    __shared__ AtssList::Storage s_list;
+    __shared__ unsigned long long s_wk[kAtssThreads / 64];             // a level's nearest anchor: the waves' entries
+    __shared__ uint32_t s_wi[kAtssThreads / 64];
     __shared__ uint32_t s_cand[kAtssThreads];
     __shared__ double s_v[kAtssThreads];
+    const AtssBefore before;
     const int tid = threadIdx.x, m = blockIdx.x, b = blockIdx.y, A = t.A, K = t.topk;
     if (t.status[b] & EVREP_TAL_ST_NONFINITE) return;                   // (uniform: written by the launch before this one)
     const TalRow r = tal_row(t.gt, b, t.M, m);
@@ -153,65 +144,35 @@ __global__ __launch_bounds__(kAtssThreads) void k_atss_select(const AtssArgs t) 
         for (int j = tid; j < n_l; j += kAtssThreads) {
             const uint32_t ia = (uint32_t)(s0 + j);                     // < A
             const unsigned long long kb = (unsigned long long)__double_as_longlong(atss_distance(r, atss_anchor(t.anchors, (int)ia)));
-            if (atss_before(kb, ia, bk, bi)) {
+            if (before(kb, ia, bk, bi)) {
                 bk = kb;
                 bi = ia;
             }
         }
         atss_wave_first(bk, bi);
-        if ((tid & 63) == 0) {                                         // (the merge's arrays are free between two levels)
-            s_nk[tid >> 6] = bk;
-            s_ni[tid >> 6] = bi;
+        if ((tid & 63) == 0) {
+            s_wk[tid >> 6] = bk;
+            s_wi[tid >> 6] = bi;
         }
         __syncthreads();
         for (int w = 0; w < kAtssThreads / 64; ++w) {
-            if (atss_before(s_nk[w], s_ni[w], bk, bi)) {
-                bk = s_nk[w];
-                bi = s_ni[w];
+            if (before(s_wk[w], s_wi[w], bk, bi)) {
+                bk = s_wk[w];
+                bi = s_wi[w];
             }
         }
         __syncthreads();
         const int n_ch = (n_l + kAtssThreads - 1) / kAtssThreads, c0 = ((int)bi - s0) / kAtssThreads;   // s0 <= bi < s0 + n_l: n_l >= 1
-        int L = 0;                                                     // entries of the list, <= min(K, anchors seen)
+        AtssList list(s_list, K);
         for (int i = 0; i < 2 * n_ch - 1; ++i) {                       // c0, c0 + 1, c0 - 1, c0 + 2, ...: every chunk once
             const int dd = (i + 1) >> 1, c = (i & 1) ? c0 + dd : c0 - dd;
             if (c < 0 || c >= n_ch) continue;                          // (uniform)
-            const int j0 = c * kAtssThreads;
-            const int j = j0 + tid;
+            const int j = c * kAtssThreads + tid;
             const bool in = j < n_l;
             const uint32_t ia = (uint32_t)(s0 + (in ? j : 0));          // < A
-            const unsigned long long kb = (unsigned long long)__double_as_longlong(atss_distance(r, atss_anchor(t.anchors, (int)ia)));
-            // the list's last entry is read before anyone rewrites it: the barriers of the scan stand between
-            const bool cont = in && (L < K || atss_before(kb, ia, s_k[L - 1], s_i[L - 1]));
-            uint32_t nc_;
-            const uint32_t ex = block_exclusive_scan<kAtssThreads / 64>(cont ? 1u : 0u, s_scan, &nc_);
-            if (nc_ == 0u) continue;                                   // (uniform)
-            if (cont) {
-                s_k[L + ex] = kb;                                      // L + ex < K + 256
-                s_i[L + ex] = ia;
-            }
-            __syncthreads();
-            const int T = L + (int)nc_;
-            const int NL = T < K ? T : K;
-            for (int e = tid; e < T; e += kAtssThreads) {
-                const unsigned long long ke = s_k[e];
-                const uint32_t ie = s_i[e];
-                int rank = 0;
-                for (int q = 0; q < T; ++q) rank += atss_before(s_k[q], s_i[q], ke, ie) ? 1 : 0;
-                if (rank < NL) {                                       // the entries are distinct: so are the ranks
-                    s_nk[rank] = ke;
-                    s_ni[rank] = ie;
-                }
-            }
-            __syncthreads();
-            if (tid < NL) {
-                s_k[tid] = s_nk[tid];
-                s_i[tid] = s_ni[tid];
-            }
-            L = NL;
-            __syncthreads();
+            list.offer(in, (unsigned long long)__double_as_longlong(atss_distance(r, atss_anchor(t.anchors, (int)ia))), ia);
         }
-        if (tid < K) s_cand[l * K + tid] = s_i[tid];                    // L == K: the level holds at least K anchors; l * K + tid < 256
+        if (tid < K) s_cand[l * K + tid] = list.index(tid);             // size() == K: the level holds at least K anchors; l * K + tid < 256
         __syncthreads();
     }
     const int n = t.n_levels * K;                                      // <= 256
@@ -278,10 +239,7 @@ __global__ __launch_bounds__(kThreads) void k_atss_resolve(const AtssArgs t) {
     t.fg[ba] = c != 0u ? 1 : 0;
     t.row[ba] = c != 0u ? g : -1;
     t.val[ba] = v;
-    for (int e = 0; e < 4; ++e) {
-        if (t.f32_boxes) tal_store<float>(t.boxes, ba * 4u + e, box[e]);
-        else tal_store<double>(t.boxes, ba * 4u + e, box[e]);
-    }
+    for (int e = 0; e < 4; ++e) tal_store(t.boxes, t.f32_boxes, ba * 4u + e, box[e]);
 }
 
 // -------------------------------------------------------------------------------------------------------------------- scores
@@ -293,9 +251,7 @@ __global__ __launch_bounds__(kThreads) void k_atss_scores(const AtssArgs t) {
         const uint32_t a = e / (uint32_t)t.nc, c = e - a * (uint32_t)t.nc;
         const size_t ba = (size_t)b * t.A + a;
         const double v = (t.row[ba] >= 0 && (int64_t)c == t.labels[ba]) ? t.val[ba] : 0.0;
-        const size_t at = (size_t)b * n + e;
-        if (t.f32_scores) tal_store<float>(t.scores, at, v);
-        else tal_store<double>(t.scores, at, v);
+        tal_store(t.scores, t.f32_scores, (size_t)b * n + e, v);
     }
 }
 

@@ -1,11 +1,15 @@
-// evrep_capi_detin.hip -- the extern "C" surface, part 10: the detector's input batch (evrep_detin.hip), its form for frames
-// of different sizes with the tap tables made on the device (evrep_detin_frames.hip), and the detector's output, the batched
-// non_max_suppression (evrep_nms.hip), the scoring of its detections against the labels (evrep_deteval.hip) with the average
-// precision behind it (evrep_detap.hip), and the training
-// targets, label padding and the task-aligned assigner (evrep_assign.hip) with the ATSS assigner of the warm-up epochs
-// (evrep_atss.hip), and the loss terms with their gradients
-// (evrep_detloss.hip), and the head's decode and tail in front of all of them (evrep_dethead.hip), and the parameter update
-// behind the backward pass (evrep_step.hip): argument checks and the launches of each entry point.  No plan, no workspace, no allocation, no wait for the device.
+// evrep_capi_detin.hip -- the extern "C" surface, part 10: the detector.  Argument checks and the launches of each entry
+// point; no plan, no allocation, no wait for the device.  The families, in the file's order:
+//   input batch        evrep_detector_input, and for frames of different sizes evrep_resize_tap_tables and
+//                      evrep_detector_input_frames (evrep_detin.hip, evrep_detin_frames.hip)
+//   detections         evrep_nms, the batched non_max_suppression (evrep_nms.hip)
+//   scoring            evrep_det_match against the labels (evrep_deteval.hip); evrep_det_ap_gather, evrep_det_ap (evrep_detap.hip)
+//   training targets   evrep_det_targets_pad, evrep_tal_assign (evrep_assign.hip); evrep_atss_assign of the warm-up epochs (evrep_atss.hip)
+//   loss terms         evrep_detloss_decode, evrep_detloss with the gradients (evrep_detloss.hip)
+//   distillation       evrep_detloss_distill, evrep_detloss_cwd and its typed form (evrep_detdistill.hip); evrep_cast16_host,
+//                      the 16-bit maps' conversions on the host
+//   head               evrep_dethead_predict / _train / _train_backward and their typed forms (evrep_dethead.hip)
+//   parameter update   evrep_train_step, evrep_ema_update (evrep_step.hip)
 #include <limits.h>
 
 #include "evrep_capi_shared.h"
@@ -36,6 +40,20 @@ static int detin_launch(const DetinArgs<double> &d, const void *rep, int32_t B, 
     k_detector_input<T><<<grid, kThreads, 0, stream>>>(a);
     LAUNCH_CHECK("k_detector_input");
     return EVREP_OK;
+}
+
+// The claim arrays, what both assigners keep per (image, anchor) at the head of their scratch: the rows that claim the anchor
+// (cnt), the lowest of them (first), the assigned row, and one double (val: TalArgs' metric, AtssArgs' score value).
+template <typename Args>
+static void claim_layout(Carver &c, int32_t B, int32_t A, Args *t) {
+    const size_t ba = (size_t)B * (size_t)A;
+    uint32_t *cnt = c.take<uint32_t>(ba * 4);
+    uint32_t *first = c.take<uint32_t>(ba * 4);
+    int32_t *row = c.take<int32_t>(ba * 4);
+    double *val = c.take<double>(ba * 8);
+    if (t) {
+        t->cnt = cnt; t->first = first; t->row = row; t->val = val;
+    }
 }
 
 extern "C" {
@@ -369,18 +387,34 @@ static inline bool tal_shape_ok(int32_t B, int32_t M, int32_t A) {
     return B >= 1 && B <= 65535 && M >= 0 && M <= EVREP_TAL_MAX_LABELS && A >= 1 && A <= EVREP_TAL_MAX_ANCHORS;
 }
 
-// the scratch of evrep_tal_assign: per (image, anchor) cnt, first, row and the metric; per (image, row) the two maxima
+// workgroups per image of a launch that could use `need` of them: B * G about 2048, at least one
+static inline unsigned groups_per_image(size_t need, int32_t B) {
+    const size_t cap = (2048 + (size_t)B - 1) / (size_t)B;
+    return (unsigned)(need < 1 ? 1 : (need < cap ? need : cap));
+}
+// the same for a grid-stride launch over `items` elements of an image, a lane each
+static inline unsigned groups_per_image_of(size_t items, int32_t B) {
+    return groups_per_image((items + kThreads - 1) / kThreads, B);
+}
+
+// what both assigners check alike of the label rows, the five outputs and the scratch: non-null (gt but for M == 0) and aligned
+static inline bool assign_ptrs_ok(const double *gt, int32_t M, const int64_t *labels, const void *boxes, uintptr_t elem_boxes,
+                                  const void *scores, uintptr_t elem_scores, const uint8_t *fg, const uint32_t *status,
+                                  const void *scratch) {
+    if (M > 0 ? bad_ptr(gt, 8) : misaligned(gt, 8)) return false;
+    if (bad_ptr(labels, 8) || bad_ptr(boxes, elem_boxes) || bad_ptr(scores, elem_scores) || bad_ptr(fg, 1)) return false;
+    return !(bad_ptr(status, 4) || bad_ptr(scratch, 256));
+}
+
+// the scratch of evrep_tal_assign: the claim arrays; per (image, row) the two maxima
 static size_t tal_layout(void *scratch, int32_t B, int32_t M, int32_t A, TalArgs *t) {
     Carver c(scratch);
-    const size_t ba = (size_t)B * (size_t)A, bm = (size_t)B * (size_t)M;
-    uint32_t *cnt = c.take<uint32_t>(ba * 4);
-    uint32_t *first = c.take<uint32_t>(ba * 4);
-    int32_t *row = c.take<int32_t>(ba * 4);
-    double *alv = c.take<double>(ba * 8);
+    const size_t bm = (size_t)B * (size_t)M;
+    claim_layout(c, B, A, t);
     unsigned long long *pos_al = c.take<unsigned long long>(bm * 8);
     unsigned long long *pos_ov = c.take<unsigned long long>(bm * 8);
     if (t) {
-        t->cnt = cnt; t->first = first; t->row = row; t->alv = alv; t->pos_al = pos_al; t->pos_ov = pos_ov;
+        t->pos_al = pos_al; t->pos_ov = pos_ov;
     }
     return c.off;
 }
@@ -399,9 +433,7 @@ int evrep_tal_assign(const float *pd_scores, const float *pd_bboxes, const float
     if (flags & ~(uint32_t)EVREP_TAL_F32_OUT) return EVREP_EINVAL;
     const uintptr_t elem = (flags & EVREP_TAL_F32_OUT) ? 4 : 8;
     if (bad_ptr(pd_scores, 4) || bad_ptr(pd_bboxes, 4) || bad_ptr(anc_points, 4)) return EVREP_EINVAL;
-    if (M > 0 ? bad_ptr(gt, 8) : misaligned(gt, 8)) return EVREP_EINVAL;
-    if (bad_ptr(target_labels, 8) || bad_ptr(target_bboxes, elem) || bad_ptr(target_scores, elem) || bad_ptr(fg, 1)) return EVREP_EINVAL;
-    if (bad_ptr(status, 4) || bad_ptr(scratch, 256)) return EVREP_EINVAL;
+    if (!assign_ptrs_ok(gt, M, target_labels, target_bboxes, elem, target_scores, elem, fg, status, scratch)) return EVREP_EINVAL;
     TalArgs t;
     memset(&t, 0, sizeof(t));
     t.pd_scores = pd_scores; t.pd_bboxes = pd_bboxes; t.anc = anc_points; t.gt = gt;
@@ -412,34 +444,23 @@ int evrep_tal_assign(const float *pd_scores, const float *pd_bboxes, const float
     hipStream_t stream = as_stream(stream_);
     int rc = hip_check(hipMemsetAsync(status, 0, (size_t)B * 4u, stream), "hipMemsetAsync(status)");
     if (rc != EVREP_OK) return rc;
-    const auto spread = [&](size_t work) {                              // workgroups per image: B * G about 2048
-        const size_t need = (work + kThreads - 1) / kThreads, cap = (2048 + (size_t)B - 1) / (size_t)B;
-        return (unsigned)(need < 1 ? 1 : (need < cap ? need : cap));
-    };
     if (M > 0) {
-        k_tal_prepare<<<dim3(spread((size_t)A * nc), (unsigned)B), kThreads, 0, stream>>>(t);
+        k_tal_prepare<<<dim3(groups_per_image_of((size_t)A * nc, B), (unsigned)B), kThreads, 0, stream>>>(t);
         LAUNCH_CHECK("k_tal_prepare");
         k_tal_select<<<dim3((unsigned)M, (unsigned)B), kTalSelectThreads, 0, stream>>>(t);
         LAUNCH_CHECK("k_tal_select");
     }
     k_tal_resolve<<<dim3((unsigned)((A + kThreads - 1) / kThreads), (unsigned)B), kThreads, 0, stream>>>(t);
     LAUNCH_CHECK("k_tal_resolve");
-    k_tal_scores<<<dim3(spread((size_t)A * nc), (unsigned)B), kThreads, 0, stream>>>(t);
+    k_tal_scores<<<dim3(groups_per_image_of((size_t)A * nc, B), (unsigned)B), kThreads, 0, stream>>>(t);
     LAUNCH_CHECK("k_tal_scores");
     return EVREP_OK;
 }
 
-// the scratch of evrep_atss_assign: per (image, anchor) cnt, first, row and the score value
+// the scratch of evrep_atss_assign: the claim arrays
 static size_t atss_layout(void *scratch, int32_t B, int32_t A, AtssArgs *t) {
     Carver c(scratch);
-    const size_t ba = (size_t)B * (size_t)A;
-    uint32_t *cnt = c.take<uint32_t>(ba * 4);
-    uint32_t *first = c.take<uint32_t>(ba * 4);
-    int32_t *row = c.take<int32_t>(ba * 4);
-    double *val = c.take<double>(ba * 8);
-    if (t) {
-        t->cnt = cnt; t->first = first; t->row = row; t->val = val;
-    }
+    claim_layout(c, B, A, t);
     return c.off;
 }
 
@@ -467,9 +488,7 @@ int evrep_atss_assign(const float *anchors, const int32_t *level_counts, int32_t
     if (total != A) return EVREP_EINVAL;
     const uintptr_t elem_b = (flags & EVREP_ATSS_F32_BOXES) ? 4 : 8, elem_s = (flags & EVREP_ATSS_F32_SCORES) ? 4 : 8;
     if (bad_ptr(anchors, 4) || misaligned(pd_bboxes, 4)) return EVREP_EINVAL;
-    if (M > 0 ? bad_ptr(gt, 8) : misaligned(gt, 8)) return EVREP_EINVAL;
-    if (bad_ptr(target_labels, 8) || bad_ptr(target_bboxes, elem_b) || bad_ptr(target_scores, elem_s) || bad_ptr(fg, 1)) return EVREP_EINVAL;
-    if (bad_ptr(status, 4) || bad_ptr(scratch, 256)) return EVREP_EINVAL;
+    if (!assign_ptrs_ok(gt, M, target_labels, target_bboxes, elem_b, target_scores, elem_s, fg, status, scratch)) return EVREP_EINVAL;
     t.anchors = anchors; t.pd_bboxes = pd_bboxes; t.gt = gt;
     t.labels = target_labels; t.boxes = target_bboxes; t.scores = target_scores; t.fg = fg; t.status = status;
     t.B = B; t.M = M; t.A = A; t.nc = nc; t.topk = topk; t.n_levels = n_levels;
@@ -479,19 +498,15 @@ int evrep_atss_assign(const float *anchors, const int32_t *level_counts, int32_t
     hipStream_t stream = as_stream(stream_);
     int rc = hip_check(hipMemsetAsync(status, 0, (size_t)B * 4u, stream), "hipMemsetAsync(status)");
     if (rc != EVREP_OK) return rc;
-    const auto spread = [&](size_t work) {                              // workgroups per image: B * G about 2048
-        const size_t need = (work + kThreads - 1) / kThreads, cap = (2048 + (size_t)B - 1) / (size_t)B;
-        return (unsigned)(need < 1 ? 1 : (need < cap ? need : cap));
-    };
     if (M > 0) {
-        k_atss_prepare<<<dim3(spread((size_t)A * 4u), (unsigned)B), kThreads, 0, stream>>>(t);
+        k_atss_prepare<<<dim3(groups_per_image_of((size_t)A * 4u, B), (unsigned)B), kThreads, 0, stream>>>(t);
         LAUNCH_CHECK("k_atss_prepare");
         k_atss_select<<<dim3((unsigned)M, (unsigned)B), kAtssThreads, 0, stream>>>(t);
         LAUNCH_CHECK("k_atss_select");
     }
     k_atss_resolve<<<dim3((unsigned)((A + kThreads - 1) / kThreads), (unsigned)B), kThreads, 0, stream>>>(t);
     LAUNCH_CHECK("k_atss_resolve");
-    k_atss_scores<<<dim3(spread((size_t)A * nc), (unsigned)B), kThreads, 0, stream>>>(t);
+    k_atss_scores<<<dim3(groups_per_image_of((size_t)A * nc, B), (unsigned)B), kThreads, 0, stream>>>(t);
     LAUNCH_CHECK("k_atss_scores");
     return EVREP_OK;
 }
@@ -505,31 +520,45 @@ static inline uint32_t detloss_n_tss(int32_t B, int32_t A) {
     const size_t chunks = ((size_t)B * (size_t)A + kThreads - 1) / kThreads;
     return (uint32_t)(chunks < (size_t)kDetlossSlices ? chunks : (size_t)kDetlossSlices);
 }
-static inline uint32_t detloss_gc(int32_t B, int32_t A, int32_t nc) {
-    const size_t need = ((size_t)A * (size_t)nc + kThreads - 1) / kThreads, cap = (2048 + (size_t)B - 1) / (size_t)B;
-    return (uint32_t)(need < cap ? need : cap);
-}
+static inline uint32_t detloss_gc(int32_t B, int32_t A, int32_t nc) { return groups_per_image_of((size_t)A * (size_t)nc, B); }
 static inline uint32_t detloss_ga(int32_t A) { return (uint32_t)((A + kThreads - 1) / kThreads); }
+// workgroups per image of the distilled class term: a tile of whole rows each, dealt round robin
+static inline uint32_t detdistill_gd(int32_t B, int32_t A, int32_t nc) {
+    const size_t rt = (size_t)distill_tile_rows(nc);
+    return groups_per_image(((size_t)A + rt - 1) / rt, B);
+}
 
-// the scratch of evrep_detloss: the rows' sums per (image, anchor), then the partial sums of the four launches
-static size_t detloss_layout(void *scratch, int32_t B, int32_t A, int32_t nc, DetlossArgs *t) {
+// the scratch of evrep_detloss: the rows' sums per (image, anchor), then the partial sums of the four launches.  That of
+// evrep_detloss_distill (`distill`) has three arrays per slice of the rows launch, not one, two per workgroup of its own class
+// launch, and four per workgroup of the box launch, not three.
+static size_t detloss_layout(void *scratch, int32_t B, int32_t A, int32_t nc, bool distill, DetlossArgs *t) {
     Carver c(scratch);
-    const size_t n_tss = detloss_n_tss(B, A), n_cls = (size_t)B * detloss_gc(B, A, nc), n_box = (size_t)B * detloss_ga(A);
+    const size_t n_tss = detloss_n_tss(B, A), n_box = (size_t)B * detloss_ga(A);
+    const size_t n_cls = (size_t)B * (distill ? detdistill_gd(B, A, nc) : detloss_gc(B, A, nc));
     double *w = c.take<double>((size_t)B * (size_t)A * 8);
     double *tss_part = c.take<double>(n_tss * 8);
+    double *wfg_part = distill ? c.take<double>(n_tss * 8) : nullptr;
+    double *nfg_part = distill ? c.take<double>(n_tss * 8) : nullptr;
     double *cls_part = c.take<double>(n_cls * 8);
+    double *dcls_part = distill ? c.take<double>(n_cls * 8) : nullptr;
     double *iou_part = c.take<double>(n_box * 8);
     double *dfl_part = c.take<double>(n_box * 8);
     double *cnt_part = c.take<double>(n_box * 8);
+    double *ddfl_part = distill ? c.take<double>(n_box * 8) : nullptr;
     if (t) {
-        t->w = w; t->tss_part = tss_part; t->cls_part = cls_part; t->iou_part = iou_part; t->dfl_part = dfl_part; t->cnt_part = cnt_part;
+        t->w = w; t->tss_part = tss_part; t->wfg_part = wfg_part; t->nfg_part = nfg_part; t->cls_part = cls_part; t->dcls_part = dcls_part;
+        t->iou_part = iou_part; t->dfl_part = dfl_part; t->cnt_part = cnt_part; t->ddfl_part = ddfl_part;
         t->n_tss = (uint32_t)n_tss; t->n_cls = (uint32_t)n_cls; t->n_box = (uint32_t)n_box;
     }
     return c.off;
 }
 
 size_t evrep_detloss_workspace_bytes(int32_t B, int32_t A, int32_t nc) {
-    return detloss_shape_ok(B, A, nc) ? detloss_layout(nullptr, B, A, nc, nullptr) : 0;
+    return detloss_shape_ok(B, A, nc) ? detloss_layout(nullptr, B, A, nc, false, nullptr) : 0;
+}
+
+size_t evrep_detloss_distill_workspace_bytes(int32_t B, int32_t A, int32_t nc) {
+    return detloss_shape_ok(B, A, nc) && nc <= EVREP_DISTILL_MAX_CLASSES ? detloss_layout(nullptr, B, A, nc, true, nullptr) : 0;
 }
 
 // R with DFL: 1..32 (the bins tl and tl + 1 of a target lie inside the R + 1 logits); without: 0..32, not read
@@ -554,10 +583,13 @@ int evrep_detloss_decode(const float *pred_distri, const float *anc_points, cons
     return EVREP_OK;
 }
 
-int evrep_detloss(const float *pred_scores, const float *pred_distri, const float *anc_points, const float *stride,
-                  const int64_t *target_labels, const void *target_bboxes, const void *target_scores, const uint8_t *fg, int32_t B,
-                  int32_t A, int32_t nc, int32_t R, double w_class, double w_iou, double w_dfl, uint32_t flags, double *losses,
-                  float *grad_scores, float *grad_distri, uint32_t *status, void *scratch, void *stream_) {
+// What evrep_detloss and evrep_detloss_distill share: the checks of the shape, the flags and the pointers both take, and *t
+// zeroed and filled from them -- all but the teacher's fields and the scratch, which the entry adds.
+static int detloss_args(const float *pred_scores, const float *pred_distri, const float *anc_points, const float *stride,
+                        const int64_t *target_labels, const void *target_bboxes, const void *target_scores, const uint8_t *fg,
+                        int32_t B, int32_t A, int32_t nc, int32_t R, double w_class, double w_iou, double w_dfl, uint32_t flags,
+                        double *losses, float *grad_scores, float *grad_distri, uint32_t *status, const void *scratch,
+                        DetlossArgs *t) {
     if (!detloss_shape_ok(B, A, nc)) return EVREP_EINVAL;
     if ((flags & ~(uint32_t)(EVREP_DETLOSS_USE_DFL | EVREP_DETLOSS_NO_GRAD | EVREP_DETLOSS_F32_TARGETS)) || !detloss_r_ok(R, flags))
         return EVREP_EINVAL;
@@ -568,20 +600,30 @@ int evrep_detloss(const float *pred_scores, const float *pred_distri, const floa
     if (grad ? (bad_ptr(grad_scores, 4) || bad_ptr(grad_distri, 4)) : (misaligned(grad_scores, 4) || misaligned(grad_distri, 4)))
         return EVREP_EINVAL;
     if (bad_ptr(losses, 8) || bad_ptr(status, 4) || bad_ptr(scratch, 256)) return EVREP_EINVAL;
+    memset(t, 0, sizeof(*t));
+    t->p = pred_scores; t->z = pred_distri; t->anc = anc_points; t->stride = stride;
+    t->labels = target_labels; t->tb = target_bboxes; t->ts = target_scores; t->fg = fg;
+    t->losses = losses; t->gs = grad ? grad_scores : nullptr; t->gz = grad ? grad_distri : nullptr; t->status = status;
+    t->wc = w_class; t->wi = w_iou; t->wd = w_dfl;
+    t->B = B; t->A = A; t->nc = nc; t->R = R;
+    t->use_dfl = (flags & EVREP_DETLOSS_USE_DFL) ? 1 : 0;
+    t->K = t->use_dfl ? R + 1 : 1;
+    t->f32_t = (flags & EVREP_DETLOSS_F32_TARGETS) ? 1 : 0;
+    t->grad = grad ? 1 : 0;
+    return EVREP_OK;
+}
+
+int evrep_detloss(const float *pred_scores, const float *pred_distri, const float *anc_points, const float *stride,
+                  const int64_t *target_labels, const void *target_bboxes, const void *target_scores, const uint8_t *fg, int32_t B,
+                  int32_t A, int32_t nc, int32_t R, double w_class, double w_iou, double w_dfl, uint32_t flags, double *losses,
+                  float *grad_scores, float *grad_distri, uint32_t *status, void *scratch, void *stream_) {
     DetlossArgs t;
-    memset(&t, 0, sizeof(t));
-    t.p = pred_scores; t.z = pred_distri; t.anc = anc_points; t.stride = stride;
-    t.labels = target_labels; t.tb = target_bboxes; t.ts = target_scores; t.fg = fg;
-    t.losses = losses; t.gs = grad ? grad_scores : nullptr; t.gz = grad ? grad_distri : nullptr; t.status = status;
-    t.wc = w_class; t.wi = w_iou; t.wd = w_dfl;
-    t.B = B; t.A = A; t.nc = nc; t.R = R;
-    t.use_dfl = (flags & EVREP_DETLOSS_USE_DFL) ? 1 : 0;
-    t.K = t.use_dfl ? R + 1 : 1;
-    t.f32_t = (flags & EVREP_DETLOSS_F32_TARGETS) ? 1 : 0;
-    t.grad = grad ? 1 : 0;
-    detloss_layout(scratch, B, A, nc, &t);
+    int rc = detloss_args(pred_scores, pred_distri, anc_points, stride, target_labels, target_bboxes, target_scores, fg, B, A, nc, R,
+                          w_class, w_iou, w_dfl, flags, losses, grad_scores, grad_distri, status, scratch, &t);
+    if (rc != EVREP_OK) return rc;
+    detloss_layout(scratch, B, A, nc, false, &t);
     hipStream_t stream = as_stream(stream_);
-    int rc = hip_check(hipMemsetAsync(status, 0, (size_t)B * 4u, stream), "hipMemsetAsync(status)");
+    rc = hip_check(hipMemsetAsync(status, 0, (size_t)B * 4u, stream), "hipMemsetAsync(status)");
     if (rc != EVREP_OK) return rc;
     k_detloss_rows<false><<<t.n_tss, kThreads, 0, stream>>>(t);
     LAUNCH_CHECK("k_detloss_rows");
@@ -594,71 +636,23 @@ int evrep_detloss(const float *pred_scores, const float *pred_distri, const floa
     return EVREP_OK;
 }
 
-// workgroups per image of the distilled class term: a tile of whole rows each, dealt round robin
-static inline uint32_t detdistill_gd(int32_t B, int32_t A, int32_t nc) {
-    const size_t rt = (size_t)distill_tile_rows(nc), need = ((size_t)A + rt - 1) / rt, cap = (2048 + (size_t)B - 1) / (size_t)B;
-    return (uint32_t)(need < cap ? need : cap);
-}
-
-// the scratch of evrep_detloss_distill: the rows' sums, three arrays per slice of the rows launch, two per workgroup of the
-// class launch, four per workgroup of the box launch
-static size_t detdistill_layout(void *scratch, int32_t B, int32_t A, int32_t nc, DetlossArgs *t) {
-    Carver c(scratch);
-    const size_t n_tss = detloss_n_tss(B, A), n_cls = (size_t)B * detdistill_gd(B, A, nc), n_box = (size_t)B * detloss_ga(A);
-    double *w = c.take<double>((size_t)B * (size_t)A * 8);
-    double *tss_part = c.take<double>(n_tss * 8);
-    double *wfg_part = c.take<double>(n_tss * 8);
-    double *nfg_part = c.take<double>(n_tss * 8);
-    double *cls_part = c.take<double>(n_cls * 8);
-    double *dcls_part = c.take<double>(n_cls * 8);
-    double *iou_part = c.take<double>(n_box * 8);
-    double *dfl_part = c.take<double>(n_box * 8);
-    double *cnt_part = c.take<double>(n_box * 8);
-    double *ddfl_part = c.take<double>(n_box * 8);
-    if (t) {
-        t->w = w; t->tss_part = tss_part; t->wfg_part = wfg_part; t->nfg_part = nfg_part; t->cls_part = cls_part; t->dcls_part = dcls_part;
-        t->iou_part = iou_part; t->dfl_part = dfl_part; t->cnt_part = cnt_part; t->ddfl_part = ddfl_part;
-        t->n_tss = (uint32_t)n_tss; t->n_cls = (uint32_t)n_cls; t->n_box = (uint32_t)n_box;
-    }
-    return c.off;
-}
-
-size_t evrep_detloss_distill_workspace_bytes(int32_t B, int32_t A, int32_t nc) {
-    return detloss_shape_ok(B, A, nc) && nc <= EVREP_DISTILL_MAX_CLASSES ? detdistill_layout(nullptr, B, A, nc, nullptr) : 0;
-}
-
 int evrep_detloss_distill(const float *pred_scores, const float *pred_distri, const float *t_pred_scores, const float *t_pred_distri,
                           const float *anc_points, const float *stride, const int64_t *target_labels, const void *target_bboxes,
                           const void *target_scores, const uint8_t *fg, int32_t B, int32_t A, int32_t nc, int32_t R, double w_class,
                           double w_iou, double w_dfl, double temperature, double k_class, double k_dfl, uint32_t flags, double *losses,
                           float *grad_scores, float *grad_distri, uint32_t *status, void *scratch, void *stream_) {
-    if (!detloss_shape_ok(B, A, nc) || nc > EVREP_DISTILL_MAX_CLASSES) return EVREP_EINVAL;
-    if ((flags & ~(uint32_t)(EVREP_DETLOSS_USE_DFL | EVREP_DETLOSS_NO_GRAD | EVREP_DETLOSS_F32_TARGETS)) || !detloss_r_ok(R, flags))
-        return EVREP_EINVAL;
+    if (nc > EVREP_DISTILL_MAX_CLASSES) return EVREP_EINVAL;
     if (!(temperature > 0.0) || !(temperature - temperature == 0.0)) return EVREP_EINVAL;   // NaN, inf, <= 0
-    const uintptr_t elem = (flags & EVREP_DETLOSS_F32_TARGETS) ? 4 : 8;
-    const bool grad = !(flags & EVREP_DETLOSS_NO_GRAD);
-    if (bad_ptr(pred_scores, 4) || bad_ptr(pred_distri, 4) || bad_ptr(t_pred_scores, 4) || bad_ptr(t_pred_distri, 4)) return EVREP_EINVAL;
-    if (bad_ptr(anc_points, 4) || bad_ptr(stride, 4)) return EVREP_EINVAL;
-    if (bad_ptr(target_labels, 8) || bad_ptr(target_bboxes, elem) || bad_ptr(target_scores, elem) || bad_ptr(fg, 1)) return EVREP_EINVAL;
-    if (grad ? (bad_ptr(grad_scores, 4) || bad_ptr(grad_distri, 4)) : (misaligned(grad_scores, 4) || misaligned(grad_distri, 4)))
-        return EVREP_EINVAL;
-    if (bad_ptr(losses, 8) || bad_ptr(status, 4) || bad_ptr(scratch, 256)) return EVREP_EINVAL;
+    if (bad_ptr(t_pred_scores, 4) || bad_ptr(t_pred_distri, 4)) return EVREP_EINVAL;
     DetlossArgs t;
-    memset(&t, 0, sizeof(t));
-    t.p = pred_scores; t.z = pred_distri; t.tp = t_pred_scores; t.tz = t_pred_distri; t.anc = anc_points; t.stride = stride;
-    t.labels = target_labels; t.tb = target_bboxes; t.ts = target_scores; t.fg = fg;
-    t.losses = losses; t.gs = grad ? grad_scores : nullptr; t.gz = grad ? grad_distri : nullptr; t.status = status;
-    t.wc = w_class; t.wi = w_iou; t.wd = w_dfl;
+    int rc = detloss_args(pred_scores, pred_distri, anc_points, stride, target_labels, target_bboxes, target_scores, fg, B, A, nc, R,
+                          w_class, w_iou, w_dfl, flags, losses, grad_scores, grad_distri, status, scratch, &t);
+    if (rc != EVREP_OK) return rc;
+    t.tp = t_pred_scores; t.tz = t_pred_distri;
     t.T = temperature; t.k_class = k_class; t.k_dfl = k_dfl;
-    t.B = B; t.A = A; t.nc = nc; t.R = R;
-    t.use_dfl = (flags & EVREP_DETLOSS_USE_DFL) ? 1 : 0;
-    t.K = t.use_dfl ? R + 1 : 1;
-    t.f32_t = (flags & EVREP_DETLOSS_F32_TARGETS) ? 1 : 0;
-    t.grad = grad ? 1 : 0;
-    detdistill_layout(scratch, B, A, nc, &t);
+    detloss_layout(scratch, B, A, nc, true, &t);
     hipStream_t stream = as_stream(stream_);
-    int rc = hip_check(hipMemsetAsync(status, 0, (size_t)B * 4u, stream), "hipMemsetAsync(status)");
+    rc = hip_check(hipMemsetAsync(status, 0, (size_t)B * 4u, stream), "hipMemsetAsync(status)");
     if (rc != EVREP_OK) return rc;
     k_detloss_rows<true><<<t.n_tss, kThreads, 0, stream>>>(t);
     LAUNCH_CHECK("k_detloss_rows<distill>");

@@ -269,6 +269,41 @@ def preprocess(targets, batch_size, width, height, max_labels=None, return_statu
     return (gt, n_labels, status) if return_status else gt
 
 
+def _targets_on(targets, B, dev, max_labels):
+    """``(M, targets on dev)`` for either assigner: a CPU ``targets`` gives the reference's M, counted on the host, unless
+    ``max_labels`` states it; a CUDA one needs ``max_labels``."""
+    if not targets.is_cuda:
+        return (_count_labels(targets.detach().float(), B) if max_labels is None else int(max_labels)), targets.to(dev)
+    if max_labels is None:
+        raise ValueError("a CUDA targets tensor needs max_labels: M cannot be read from the device without a wait")
+    return int(max_labels), targets
+
+
+def _shape_limits(B, A, nc, M):
+    """The limits of ``evrep_tal_assign`` and ``evrep_atss_assign`` (ValueError)."""
+    if not (1 <= B <= 65535 and 1 <= A <= _lib.TAL_MAX_ANCHORS and 1 <= nc <= MAX_CLASSES and A * nc < 2 ** 31 and 0 <= M <= MAX_LABELS):
+        raise ValueError("the assigner takes 1 <= B <= 65535, 1 <= nc <= %d, A * nc < 2^31 and M <= %d" % (MAX_CLASSES, MAX_LABELS))
+
+
+def _outputs(B, A, nc, boxes_dtype, scores_dtype, dev):
+    """What an assigner's C entry writes: ``(labels, boxes, scores, fg uint8, status int32)``, uninitialised."""
+    labels = torch.empty((B, A), dtype=torch.int64, device=dev)
+    boxes = torch.empty((B, A, 4), dtype=boxes_dtype, device=dev)
+    out = torch.empty((B, A, nc), dtype=scores_dtype, device=dev)
+    fg = torch.empty((B, A), dtype=torch.uint8, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    return labels, boxes, out, fg, status
+
+
+def _finish(outputs, st_pad, check):
+    """The tail of ``assign_batch`` / ``atss_assign_batch``: the padding's status into the assigner's, ``check``, fg as bool."""
+    labels, boxes, out, fg, st = outputs
+    status = torch.bitwise_or(st, st_pad)
+    if check:
+        check_status(status)
+    return labels, boxes, out, fg.bool(), status
+
+
 def _assign_device(pd_scores, pd_bboxes, anc_points, gt, topk, alpha, beta, out_dtype):
     dev = pd_scores.device
     if pd_scores.dtype != torch.float32 or pd_bboxes.dtype != torch.float32:
@@ -277,8 +312,7 @@ def _assign_device(pd_scores, pd_bboxes, anc_points, gt, topk, alpha, beta, out_
         raise ValueError("pd_scores must be (B, A, nc) and pd_bboxes (B, A, 4)")
     B, A, nc = (int(v) for v in pd_scores.shape)
     M = int(gt.shape[1])
-    if not (1 <= B <= 65535 and 1 <= A <= _lib.TAL_MAX_ANCHORS and 1 <= nc <= MAX_CLASSES and A * nc < 2 ** 31 and 0 <= M <= MAX_LABELS):
-        raise ValueError("the assigner takes 1 <= B <= 65535, 1 <= nc <= %d, A * nc < 2^31 and M <= %d" % (MAX_CLASSES, MAX_LABELS))
+    _shape_limits(B, A, nc, M)
     if not 1 <= int(topk) <= MAX_TOPK:
         raise ValueError("topk must be in 1..%d" % MAX_TOPK)
     _np_dtype(out_dtype)
@@ -286,11 +320,7 @@ def _assign_device(pd_scores, pd_bboxes, anc_points, gt, topk, alpha, beta, out_
     pd_bboxes = _lib.want(pd_bboxes.detach().contiguous(), "pd_bboxes", torch.float32, shape=(B, A, 4), device=dev)
     anc = _lib.want(anc_points.detach().to(dev).float().contiguous(), "anc_points", torch.float32, shape=(A, 2), device=dev)
     gt = _lib.want(gt.detach().contiguous(), "gt", torch.float64, shape=(B, M, 5), device=dev)
-    labels = torch.empty((B, A), dtype=torch.int64, device=dev)
-    boxes = torch.empty((B, A, 4), dtype=out_dtype, device=dev)
-    out = torch.empty((B, A, nc), dtype=out_dtype, device=dev)
-    fg = torch.empty((B, A), dtype=torch.uint8, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    labels, boxes, out, fg, status = _outputs(B, A, nc, out_dtype, out_dtype, dev)
     with torch.cuda.device(dev):
         api = _lib.api()
         scratch = _lib.scratch(api.evrep_tal_workspace_bytes(B, M, A), dev)
@@ -320,20 +350,10 @@ def assign_batch(pd_scores, pd_bboxes, anc_points, targets, img_hw, num_classes,
     if int(pd_scores.shape[-1]) != int(num_classes):
         raise ValueError("pd_scores has %d classes, num_classes is %d" % (pd_scores.shape[-1], num_classes))
     alpha, beta = _power(alpha, "alpha"), _power(beta, "beta")
-    B, dev = int(pd_scores.shape[0]), pd_scores.device
-    if not targets.is_cuda:
-        M = _count_labels(targets.detach().float(), B) if max_labels is None else int(max_labels)
-        targets = targets.to(dev)
-    elif max_labels is None:
-        raise ValueError("a CUDA targets tensor needs max_labels: M cannot be read from the device without a wait")
-    else:
-        M = int(max_labels)
+    B = int(pd_scores.shape[0])
+    M, targets = _targets_on(targets, B, pd_scores.device, max_labels)
     gt, _, st_pad = _pad_device(targets, B, M, img_hw[1], img_hw[0])
-    labels, boxes, out, fg, st = _assign_device(pd_scores, pd_bboxes, anc_points, gt, topk, alpha, beta, out_dtype)
-    status = torch.bitwise_or(st, st_pad)
-    if check:
-        check_status(status)
-    return labels, boxes, out, fg.bool(), status
+    return _finish(_assign_device(pd_scores, pd_bboxes, anc_points, gt, topk, alpha, beta, out_dtype), st_pad, check)
 
 
 class TaskAlignedAssigner(torch.nn.Module):
@@ -516,7 +536,6 @@ def atss_host(anchors, level_counts, gt, pd_bboxes=None, topk=9, num_classes=80,
 
 def _atss_device(anchors, level_counts, gt, pd_bboxes, nc, topk, boxes_dtype, scores_dtype):
     """The C entry on CUDA tensors: ``(labels, boxes, scores, fg uint8, status int32)``."""
-    import ctypes
     dev = gt.device
     if anchors.dtype != torch.float32 or anchors.dim() != 2 or anchors.shape[1] != 4:
         raise ValueError("the anchor boxes must be a float32 (A, 4) tensor, got %s %s" % (anchors.dtype, tuple(anchors.shape)))
@@ -525,24 +544,19 @@ def _atss_device(anchors, level_counts, gt, pd_bboxes, nc, topk, boxes_dtype, sc
     A, nc, topk = int(anchors.shape[0]), int(nc), int(topk)
     B, M = int(gt.shape[0]), int(gt.shape[1])
     counts = _levels(level_counts, A, topk)
-    if not (1 <= B <= 65535 and 1 <= A <= _lib.TAL_MAX_ANCHORS and 1 <= nc <= MAX_CLASSES and A * nc < 2 ** 31 and 0 <= M <= MAX_LABELS):
-        raise ValueError("the assigner takes 1 <= B <= 65535, 1 <= nc <= %d, A * nc < 2^31 and M <= %d" % (MAX_CLASSES, MAX_LABELS))
+    _shape_limits(B, A, nc, M)
     _np_dtype(boxes_dtype)
     _np_dtype(scores_dtype)
     anc = _lib.want(anchors.detach().to(dev).contiguous(), "anchors", torch.float32, shape=(A, 4), device=dev)
     gt = _lib.want(gt.detach().contiguous(), "gt", torch.float64, shape=(B, M, 5), device=dev)
     if pd_bboxes is not None:
         pd_bboxes = _lib.want(pd_bboxes.detach().contiguous(), "pd_bboxes", torch.float32, shape=(B, A, 4), device=dev)
-    labels = torch.empty((B, A), dtype=torch.int64, device=dev)
-    boxes = torch.empty((B, A, 4), dtype=boxes_dtype, device=dev)
-    out = torch.empty((B, A, nc), dtype=scores_dtype, device=dev)
-    fg = torch.empty((B, A), dtype=torch.uint8, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    labels, boxes, out, fg, status = _outputs(B, A, nc, boxes_dtype, scores_dtype, dev)
     flags = (_lib.ATSS_F32_BOXES if boxes_dtype == torch.float32 else 0) | (_lib.ATSS_F32_SCORES if scores_dtype == torch.float32 else 0)
     with torch.cuda.device(dev):
         api = _lib.api()
         scratch = _lib.scratch(api.evrep_atss_workspace_bytes(B, M, A), dev)
-        api.evrep_atss_assign(_lib.ptr(anc), (ctypes.c_int32 * len(counts))(*counts), len(counts), _lib.ptr(gt) if M else None,
+        api.evrep_atss_assign(_lib.ptr(anc), _lib.int32_array(counts), len(counts), _lib.ptr(gt) if M else None,
                               None if pd_bboxes is None else _lib.ptr(pd_bboxes), B, M, A, nc, topk, flags, _lib.ptr(labels),
                               _lib.ptr(boxes), _lib.ptr(out), _lib.ptr(fg), _lib.ptr(status), _lib.ptr(scratch), _lib.stream_ptr())
     return labels, boxes, out, fg, status
@@ -559,21 +573,11 @@ def atss_assign_batch(anchors, n_anchors_list, pred_bboxes_px, targets, img_hw, 
     if not (isinstance(pred_bboxes_px, torch.Tensor) and pred_bboxes_px.is_cuda and pred_bboxes_px.dim() == 3):
         raise ValueError("atss_assign_batch: pred_bboxes_px must be a CUDA (B, A, 4) tensor (CPU tensors, or no predicted boxes, go "
                          "through ATSSAssigner / atss_host)")
-    B, dev = int(pred_bboxes_px.shape[0]), pred_bboxes_px.device
-    if not targets.is_cuda:
-        M = _count_labels(targets.detach().float(), B) if max_labels is None else int(max_labels)
-        targets = targets.to(dev)
-    elif max_labels is None:
-        raise ValueError("a CUDA targets tensor needs max_labels: M cannot be read from the device without a wait")
-    else:
-        M = int(max_labels)
+    B = int(pred_bboxes_px.shape[0])
+    M, targets = _targets_on(targets, B, pred_bboxes_px.device, max_labels)
     _levels(n_anchors_list, anchors.shape[0], topk)                     # (refused before the padding launch)
     gt, _, st_pad = _pad_device(targets, B, M, img_hw[1], img_hw[0])
-    labels, boxes, out, fg, st = _atss_device(anchors, n_anchors_list, gt, pred_bboxes_px, num_classes, topk, out_dtype, out_dtype)
-    status = torch.bitwise_or(st, st_pad)
-    if check:
-        check_status(status)
-    return labels, boxes, out, fg.bool(), status
+    return _finish(_atss_device(anchors, n_anchors_list, gt, pred_bboxes_px, num_classes, topk, out_dtype, out_dtype), st_pad, check)
 
 
 class ATSSAssigner(torch.nn.Module):

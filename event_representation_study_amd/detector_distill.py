@@ -197,21 +197,8 @@ def _distill_device(pred_scores, pred_distri, t_pred_scores, t_pred_distri, anc_
     tp = _lib.want(t_pred_scores.detach().contiguous(), "t_pred_scores", torch.float32, shape=(B, A, nc), device=dev)
     tz = _lib.want(t_pred_distri.detach().contiguous(), "t_pred_distri", torch.float32, shape=(B, A, 4 * K), device=dev)
     anc, st = _dl._anchors_on(dev, anc_points, stride, A)
-    tdt = target_scores.dtype
-    if tdt not in (torch.float64, torch.float32) or target_bboxes.dtype != tdt:
-        raise ValueError("target_bboxes and target_scores must both be float64 (what assign_batch returns) or both float32")
-    labels = _lib.want(target_labels.detach().contiguous(), "target_labels", torch.int64, shape=(B, A), device=dev)
-    tb = _lib.want(target_bboxes.detach().contiguous(), "target_bboxes", tdt, shape=(B, A, 4), device=dev)
-    ts = _lib.want(target_scores.detach().contiguous(), "target_scores", tdt, shape=(B, A, nc), device=dev)
-    fg = fg_mask.detach()
-    fg = (fg.view(torch.uint8) if fg.dtype == torch.bool else fg.to(torch.uint8)).contiguous()
-    fg = _lib.want(fg, "fg_mask", torch.uint8, shape=(B, A), device=dev)
-    flags = (_lib.DETLOSS_USE_DFL if use_dfl else 0) | (0 if grad else _lib.DETLOSS_NO_GRAD) | \
-        (_lib.DETLOSS_F32_TARGETS if tdt == torch.float32 else 0)
-    losses = torch.empty((8,), dtype=torch.float64, device=dev)
-    gs = torch.empty((B, A, nc), dtype=torch.float32, device=dev) if grad else None
-    gz = torch.empty((B, A, 4 * K), dtype=torch.float32, device=dev) if grad else None
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    labels, tb, ts, fg, flags = _dl._targets_on(dev, target_labels, target_bboxes, target_scores, fg_mask, B, A, nc, use_dfl, grad)
+    losses, gs, gz, status = _dl._outputs(dev, 8, B, A, nc, K, grad)
     with torch.cuda.device(dev):
         api = _lib.api()
         scratch = _lib.scratch(api.evrep_detloss_distill_workspace_bytes(B, A, nc), dev)
@@ -254,8 +241,7 @@ def distill_batch(pred_scores, pred_distri, t_pred_scores, t_pred_distri, anc_po
     _same_shape(pred_scores, t_pred_scores, "t_pred_scores")
     _same_shape(pred_distri, t_pred_distri, "t_pred_distri")
     T = _temperature(temperature)
-    lw = DEFAULT_WEIGHT if loss_weight is None else loss_weight
-    weights = (float(lw["class"]), float(lw["iou"]), float(lw["dfl"]))
+    weights = _dl._weights(loss_weight)                                 # (the defaults of the three terms are detector_loss's)
     dw = DEFAULT_DISTILL_WEIGHT if distill_weight is None else distill_weight
     dec = decay(epoch_num, max_epoch)
     k_class, k_dfl = dec * float(dw["class"]), dec * float(dw["dfl"])
@@ -268,14 +254,9 @@ def distill_batch(pred_scores, pred_distri, t_pred_scores, t_pred_distri, anc_po
                            t_pred_distri.detach().numpy(), anc_points.detach().float().numpy(), stride.detach().float().numpy(),
                            target_labels.numpy(), target_bboxes.numpy(), target_scores.numpy(), fg_mask.numpy(), T, k_class, k_dfl, R,
                            use_dfl, dict(zip(("class", "iou", "dfl"), weights)))
-        losses, status = torch.from_numpy(out[0]), torch.from_numpy(out[3].view(np.int32))
-        gs, gz = (torch.from_numpy(out[1]), torch.from_numpy(out[2])) if grad else (None, None)
+        losses, gs, gz, status = _dl._from_host(out, grad)
     loss, items = _combine(losses, weights, k_class, k_dfl)
-    if grad:
-        loss = _dl._Weighted.apply(pred_scores, pred_distri, loss, gs, gz)
-    if check:
-        _dl.check_status(status)
-    return (loss, items, status) if return_status else (loss, items)
+    return _dl._finish(pred_scores, pred_distri, loss, items, gs, gz, status, grad, check, return_status)
 
 
 class _CwNode(torch.autograd.Function):

@@ -275,16 +275,9 @@ def decode_boxes(pred_distri, anc_points, stride, reg_max=16, use_dfl=True):
     return boxes_s, boxes_px
 
 
-def _loss_device(pred_scores, pred_distri, anc_points, stride, target_labels, target_bboxes, target_scores, fg_mask, R, K, use_dfl,
-                 weights, grad):
-    """The C entry on CUDA tensors: ``(losses float64 (5,), grad_scores, grad_distri (None without grad), status int32 (B,))``."""
-    dev = pred_scores.device
-    B, A, nc = (int(v) for v in pred_scores.shape)
-    if not (1 <= B <= 65535 and 1 <= A <= _lib.TAL_MAX_ANCHORS and 1 <= nc <= _lib.TAL_MAX_CLASSES and A * nc < 2 ** 31):
-        raise ValueError("the loss takes 1 <= B <= 65535, 1 <= A <= 2^24, 1 <= nc <= %d and A * nc < 2^31" % _lib.TAL_MAX_CLASSES)
-    p = pred_scores.detach().contiguous()
-    z = _lib.want(pred_distri.detach().contiguous(), "pred_distri", torch.float32, shape=(B, A, 4 * K), device=dev)
-    anc, st = _anchors_on(dev, anc_points, stride, A)
+def _targets_on(dev, target_labels, target_bboxes, target_scores, fg_mask, B, A, nc, use_dfl, grad):
+    """The four targets held to their dtypes and shapes on ``dev``, and the flags word ``evrep_detloss`` and
+    ``evrep_detloss_distill`` take: ``(labels, tb, ts, fg uint8, flags)``."""
     tdt = target_scores.dtype
     if tdt not in (torch.float64, torch.float32) or target_bboxes.dtype != tdt:
         raise ValueError("target_bboxes and target_scores must both be float64 (what assign_batch returns) or both float32")
@@ -296,10 +289,30 @@ def _loss_device(pred_scores, pred_distri, anc_points, stride, target_labels, ta
     fg = _lib.want(fg, "fg_mask", torch.uint8, shape=(B, A), device=dev)
     flags = (_lib.DETLOSS_USE_DFL if use_dfl else 0) | (0 if grad else _lib.DETLOSS_NO_GRAD) | \
         (_lib.DETLOSS_F32_TARGETS if tdt == torch.float32 else 0)
-    losses = torch.empty((5,), dtype=torch.float64, device=dev)
+    return labels, tb, ts, fg, flags
+
+
+def _outputs(dev, n_losses, B, A, nc, K, grad):
+    """What the two C entries write: ``(losses float64 (n_losses,), grad_scores, grad_distri (None without grad), status)``."""
+    losses = torch.empty((n_losses,), dtype=torch.float64, device=dev)
     gs = torch.empty((B, A, nc), dtype=torch.float32, device=dev) if grad else None
     gz = torch.empty((B, A, 4 * K), dtype=torch.float32, device=dev) if grad else None
     status = torch.empty((B,), dtype=torch.int32, device=dev)
+    return losses, gs, gz, status
+
+
+def _loss_device(pred_scores, pred_distri, anc_points, stride, target_labels, target_bboxes, target_scores, fg_mask, R, K, use_dfl,
+                 weights, grad):
+    """The C entry on CUDA tensors: ``(losses float64 (5,), grad_scores, grad_distri (None without grad), status int32 (B,))``."""
+    dev = pred_scores.device
+    B, A, nc = (int(v) for v in pred_scores.shape)
+    if not (1 <= B <= 65535 and 1 <= A <= _lib.TAL_MAX_ANCHORS and 1 <= nc <= _lib.TAL_MAX_CLASSES and A * nc < 2 ** 31):
+        raise ValueError("the loss takes 1 <= B <= 65535, 1 <= A <= 2^24, 1 <= nc <= %d and A * nc < 2^31" % _lib.TAL_MAX_CLASSES)
+    p = pred_scores.detach().contiguous()
+    z = _lib.want(pred_distri.detach().contiguous(), "pred_distri", torch.float32, shape=(B, A, 4 * K), device=dev)
+    anc, st = _anchors_on(dev, anc_points, stride, A)
+    labels, tb, ts, fg, flags = _targets_on(dev, target_labels, target_bboxes, target_scores, fg_mask, B, A, nc, use_dfl, grad)
+    losses, gs, gz, status = _outputs(dev, 5, B, A, nc, K, grad)
     with torch.cuda.device(dev):
         api = _lib.api()
         scratch = _lib.scratch(api.evrep_detloss_workspace_bytes(B, A, nc), dev)
@@ -339,6 +352,21 @@ def check_status(status):
         raise ValueError("image %d: a foreground anchor's label outside [0, num_classes) (status %d)" % (b, st[b]))
 
 
+def _from_host(out, grad):
+    """What ``loss_host`` / ``distill_host`` return, as the tensors the device route returns: ``(losses, gs, gz, status)``."""
+    gs, gz = (torch.from_numpy(out[1]), torch.from_numpy(out[2])) if grad else (None, None)
+    return torch.from_numpy(out[0]), gs, gz, torch.from_numpy(out[3].view(np.int32))
+
+
+def _finish(pred_scores, pred_distri, loss, items, gs, gz, status, grad, check, return_status):
+    """The tail of ``loss_batch`` / ``distill_batch``: the autograd node, ``check``, the return tuple."""
+    if grad:
+        loss = _Weighted.apply(pred_scores, pred_distri, loss, gs, gz)
+    if check:
+        check_status(status)
+    return (loss, items, status) if return_status else (loss, items)
+
+
 def loss_batch(pred_scores, pred_distri, anc_points, stride, target_labels, target_bboxes, target_scores, fg_mask, num_classes,
                reg_max=16, use_dfl=True, loss_weight=None, check=False, return_status=False):
     """loss.py:176-217: ``(loss, loss_items)``.  pred_scores (B, A, nc) and pred_distri (B, A, 4 * (reg_max + 1)) float32, anc_points
@@ -362,14 +390,9 @@ def loss_batch(pred_scores, pred_distri, anc_points, stride, target_labels, targ
         out = loss_host(pred_scores.detach().numpy(), pred_distri.detach().numpy(), anc_points.detach().float().numpy(),
                         stride.detach().float().numpy(), target_labels.numpy(), target_bboxes.numpy(), target_scores.numpy(),
                         fg_mask.numpy(), R, use_dfl, dict(zip(("class", "iou", "dfl"), weights)))
-        losses, status = torch.from_numpy(out[0]), torch.from_numpy(out[3].view(np.int32))
-        gs, gz = (torch.from_numpy(out[1]), torch.from_numpy(out[2])) if grad else (None, None)
+        losses, gs, gz, status = _from_host(out, grad)
     loss, items = _combine(losses, weights)
-    if grad:
-        loss = _Weighted.apply(pred_scores, pred_distri, loss, gs, gz)
-    if check:
-        check_status(status)
-    return (loss, items, status) if return_status else (loss, items)
+    return _finish(pred_scores, pred_distri, loss, items, gs, gz, status, grad, check, return_status)
 
 
 class ComputeLoss:

@@ -4,8 +4,8 @@ dtypes -- and against the golden recorded from the reference's own ComputeLoss.p
 No tolerance between device and host: they perform the same float64 statements (and the one float32 area).
 
 Shapes: the select launch streams the anchors in chunks of 256 and merges into a list of topk <= 64; the label listing runs in
-rounds of 1024 rows.  A is 21 (below topk = 64), 84, 336 and 8400; M sits on both sides of 1, 64 and 256; topk is 1, 13, 64;
-B is 1 and 5.  The small cases are the dense ones: ties and multiply-claimed anchors are frequent at A = 84."""
+rounds of 1024 rows.  A is 21 (below topk = 64), 84, 336 and 8400, and sits on both sides of 256 and 512 with topk = 64 (the
+list at its largest merged across chunks); M sits on both sides of 1, 64 and 256; topk is 1, 13, 64; B is 1 and 5.  The small cases are the dense ones: ties and multiply-claimed anchors are frequent at A = 84."""
 import ctypes
 
 import numpy as np
@@ -145,17 +145,48 @@ def test_label_counts_around_1_64_and_256(M):
 
 
 @pytest.mark.parametrize("topk", [1, 13, 64])
-@pytest.mark.parametrize("S", [32, 64])
+@pytest.mark.parametrize("S", [32, 64, 128])
 def test_topk_1_13_64_and_above_the_anchor_count(S, topk):
-    """S = 32 has 21 anchors: topk = 64 selects them all, and every in-box anchor is a candidate."""
+    """S = 32 has 21 anchors: topk = 64 selects them all, and every in-box anchor is a candidate.  S = 128 has 336: two
+    chunks, the second partial, merged into a list of up to 64."""
     scores, boxes, anc = cases.head(800 + topk, 3, S, 2)
     gt = _da().preprocess_host(cases.targets(810 + topk, [4, 0, 7], 2, lo=0.2, hi=0.8), 3, S, S)[0]
-    assert len(anc) == (21 if S == 32 else 84)
+    assert len(anc) == {32: 21, 64: 84, 128: 336}[S]
     out = check(scores, boxes, anc, gt, "topk %d" % topk, topk=topk)
     assert out[3][0].any() and not out[3][1].any()
     if topk > len(anc):
         inside = _da()._in_gt_host(gt[0, :, 1:], anc).any(0)
         assert np.array_equal(out[3][0], inside)
+
+
+@pytest.mark.parametrize("topk", [13, 64])
+@pytest.mark.parametrize("A", [255, 256, 257, 512, 513])
+def test_anchor_counts_at_the_chunk_edges(A, topk):
+    """The first A anchors of a 525-anchor head: one chunk short of full, full, and one anchor into the next, at one and at
+    two chunks; the list of topk = 64 is merged with whole and with one-anchor chunks."""
+    scores, boxes, anc = cases.head(950, 2, 160, 2)
+    assert len(anc) == 525
+    scores, boxes, anc = (np.ascontiguousarray(v) for v in (scores[:, :A], boxes[:, :A], anc[:A]))
+    gt = _da().preprocess_host(cases.targets(951, [5, 3], 2, lo=0.3, hi=0.9), 2, 160, 160)[0]
+    out = check(scores, boxes, anc, gt, "A %d topk %d" % (A, topk), topk=topk)
+    assert out[3][0].any() and out[3][1].any() and not out[4].any()
+
+
+@pytest.mark.parametrize("topk", [1, 13, 64])
+def test_displacement_and_ties_across_chunks(topk):
+    """513 anchors, one label over the whole frame, every predicted box the label's box: the key is the class score times one
+    constant.  Rising scores: every chunk displaces the whole list and the last topk anchors remain.  Equal scores: no later
+    chunk enters and the first topk anchors remain."""
+    A, S = 513, 160
+    anc = np.ascontiguousarray(cases.head(950, 1, S, 2)[2][:A])
+    gt = _da().preprocess_host(cases.xyxy_rows(0, [(1, 0, 0, S, S)], S), 1, S, S)[0]
+    assert gt[0, 0].tolist() == [1, 0, 0, S, S] and _da()._in_gt_host(gt[0, :, 1:], anc).all()
+    boxes = np.ascontiguousarray(np.broadcast_to(gt[0, 0, 1:].astype(F32), (1, A, 4)))
+    rising = np.full((1, A, 2), 0.5, F32)
+    rising[0, :, 1] = (np.arange(A) + 1).astype(F32) / F32(A)
+    for scores, first, what in ((rising, A - topk, "rising"), (np.full((1, A, 2), 0.5, F32), 0, "equal")):
+        out = check(scores, boxes, anc, gt, "%s topk %d" % (what, topk), topk=topk)
+        assert np.flatnonzero(out[3][0]).tolist() == list(range(first, first + topk)) and not out[4].any()
 
 
 def test_other_exponents():
